@@ -2,12 +2,16 @@
 """bench.py -- clump*steps/s of the MI355X-native DEM hot path on BASELINE.json configs[1]
 (1M three-sphere clumps in a box, gravity settling), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over the whole bed: (contact detection every --cd-freq steps:
 margins, binning, bin-sorted sweep, history map) + contact forces + fused accumulation/integration.
 State is resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs: set-up and pre-settling, warm-up, the timed steps, the outputs of the last
+step when --dump-outputs is given, the JSON line.  --full adds the side measurements: the CPU baseline (`cpu_baseline`) and
+the attainable HBM copy rate (`roofline.attainable_copy_GBs`); --no-cpu-baseline leaves both out of a --full run again.
 
 N > 1 (weak scaling): ONE bed N times as long in x is cut into N slabs (dem-engine_amd/decomp.py); each rank
 steps its slab and, every step, exchanges ghost-clump records (56 B each: pose, velocities) with its face
@@ -91,6 +95,46 @@ def force_kernel_bytes(n_owners, n_spheres, n_contacts, n_w):
     once each).  The per-contact contribution records this design writes instead of atomics are
     implementation traffic and are NOT counted."""
     return n_contacts * (9 + 8 * n_w) + n_owners * 57 + n_spheres * 7
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 18  # owners / contacts written by --dump-outputs: a fixed, seeded sample of larger outputs
+DUMP_SEED = 20240901
+
+
+def _dump_sample(n, seed):
+    """sorted indices of a fixed, seeded sample of DUMP_SAMPLE out of n (all of them when n is not larger)"""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(pkg, ctx, p, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as DIR/<name>.npy in float32 / float64.
+    Owner state (positions decoded to float64 metres, orientation, velocities, accelerations) of a seeded sample of owners;
+    the contact list in a canonical order (ascending A id, B id, type) with its per-contact wildcards (the contact history),
+    a seeded sample of it.  Returns {name: bytes}."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = ctx.download_state()
+    io = _dump_sample(len(st["voxelID"]), DUMP_SEED)
+    pos = pkg.model.decode_positions(st["voxelID"][io], st["locX"][io], st["locY"][io], st["locZ"][io], p.nvXp2, p.nvYp2,
+                                     p.voxelSize, p.l)
+    out = {"owner_pos": pos.astype(np.float64)}
+    for name, keys in (("owner_oriQ", ("oriQw", "oriQx", "oriQy", "oriQz")), ("owner_vel", ("vX", "vY", "vZ")),
+                       ("owner_omgBar", ("omgBarX", "omgBarY", "omgBarZ")), ("owner_acc", ("aX", "aY", "aZ")),
+                       ("owner_alpha", ("alphaX", "alphaY", "alphaZ"))):
+        out[name] = np.stack([st[k][io] for k in keys], 1).astype(np.float32)
+    a, b, t, _ = ctx.contacts()
+    order = np.lexsort((t, b, a))
+    ic = order[_dump_sample(len(order), DUMP_SEED + 1)]
+    out["contact_ids"] = np.stack([a[ic], b[ic], t[ic]], 1).astype(np.float64)  # (ids < 2^32: exact in float64)
+    nW = int(p.nContactWildcards)
+    out["contact_wildcards"] = (np.stack([ctx.wildcard(w)[ic] for w in range(nW)], 1) if nW else np.zeros((len(ic), 0))).astype(np.float32)
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} B (limit {DUMP_MAX_BYTES})"
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {name: int(v.nbytes) for name, v in out.items()}
 
 
 def _time_oracle(sim, orc, threads, budget_s, chunk, max_steps):
@@ -463,7 +507,13 @@ def main():
     ap.add_argument("--drift", type=float, default=0.0, metavar="VX",
                     help="give every clump this lateral velocity [m/s] after the pre-settling, so that clumps really cross the cuts "
                          "(with --migrate-every)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the side measurements: the CPU baseline and the attainable HBM copy rate (off by default: a "
+                         "plain run times the steps and nothing else)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline and the copy rate out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what their last step computed (owner state and contact list of rank 0, "
+                         "a fixed seeded sample of each) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--state-cache", default="",
                     help="profiling aid (1 GPU): file that keeps the pre-settled bed (owner state, contact list, wildcards) so "
                          "that repeated rocprofv3 passes of the same command skip the 30 000 untimed steps; created when absent")
@@ -781,6 +831,8 @@ def main():
     dt_local = time.perf_counter() - t0  # this rank's own clock, before it waits for the others (reported per rank; not the metric)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pkg, ctx, p, args.dump_outputs)
     total_clumps = n_own
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=red_dev)
@@ -837,7 +889,7 @@ def main():
     # (deme_copy_rate_probe; 1 GiB each way, beyond the 256 MiB Infinity Cache); the guide's figure for such a copy is 6.29 TB/s.
     # (Round 4 used torch's device-to-device copy here, which reaches 4.7-5.4 TB/s: a fraction of THAT flattered the kernel.)
     copy_gbs = None
-    if rank == 0 and not args.no_cpu_baseline:  # (profiling and A/B runs pass --no-cpu-baseline: their traces hold the bench's kernels only)
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # (profiling and A/B runs pass --no-cpu-baseline: their traces hold the bench's kernels only)
         try:
             copy_gbs = pkg.abi.copy_rate_probe(local_rank)
         except Exception as e:  # (a box short of 2 GiB of free HBM)
@@ -908,9 +960,10 @@ def main():
         pmc_calibration(torch)
     if rank == 0:
         main_bed = None
-        if not args.no_cpu_baseline and world == 1 and group is None and not (args.config5 or args.custom_model or args.mesh_triangles):
+        with_cpu = args.full and not args.no_cpu_baseline and world == 1
+        if with_cpu and group is None and not (args.config5 or args.custom_model or args.mesh_triangles):
             main_bed = (p, sc, ctx.download_state())
-        out["cpu_baseline"] = cpu_baseline(pkg, args.seed, args.cd_freq, main=main_bed) if (not args.no_cpu_baseline and world == 1) else None
+        out["cpu_baseline"] = cpu_baseline(pkg, args.seed, args.cd_freq, main=main_bed) if with_cpu else None
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1:
         dist.barrier()
