@@ -58,19 +58,10 @@ __device__ inline f3 faxpy(float s, f3 a, f3 b) { return mk3(s * a.x + b.x, s * 
 // streamed-once data (gather records, history, contribution records) can bypass the caches' retention so that the owner records
 // several contacts share stay resident: non-temporal loads and stores for the streams (measured: force pass -2.3 %, the integrator that
 // gathers the B-side records afterwards -2 %)
-#ifndef DEME_FAST_NT
-#define DEME_FAST_NT 1
-#endif
-#ifndef DEME_REC24
-#define DEME_REC24 1  // 1: the tile sums and the crossing contacts' records are 24 bytes (six floats as three 8-byte pieces) instead of
-                      // two 16-byte pieces with two unused floats: -22 MB written by the force pass and -22 MB read by the integrator at
-                      // 1e6 clumps (the integrator moves its bytes at the copy rate; the force pass answers to bytes with ~0.3)
-#endif
 typedef unsigned int nt_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned int nt_u2 __attribute__((ext_vector_type(2)));
 template <typename T>
 __device__ inline T stream_load(const T* p) {
-#if DEME_FAST_NT
     static_assert(sizeof(T) == 16 || sizeof(T) == 8 || sizeof(T) == 4, "16-, 8- or 4-byte records");
     T out;
     if constexpr (sizeof(T) == 16) {
@@ -84,13 +75,9 @@ __device__ inline T stream_load(const T* p) {
         __builtin_memcpy(&out, &v, 8);
     }
     return out;
-#else
-    return *p;
-#endif
 }
 template <typename T>
 __device__ inline void stream_store(T* p, T v) {
-#if DEME_FAST_NT
     if constexpr (sizeof(T) == 16) {
         nt_u4 w;
         __builtin_memcpy(&w, &v, 16);
@@ -104,9 +91,6 @@ __device__ inline void stream_store(T* p, T v) {
         __builtin_memcpy(&w, &v, 8);
         __builtin_nontemporal_store(w, reinterpret_cast<nt_u2*>(p));
     }
-#else
-    *p = v;
-#endif
 }
 __device__ inline float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ inline float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
@@ -120,51 +104,31 @@ __device__ inline void pos_units(const OwnerRec& r, const DevParams& p, int64_t&
     uz = (int64_t)(((id >> (p.nvXp2 + p.nvYp2)) << 16) | r.locZ);
 }
 
-// Cooperative fetch of the 2 x 64 owner records a wavefront needs (A's and B's owner of each lane's contact): four lanes per
-// record, all eight load instructions issued before anything waits, then two transposes through the wavefront's LDS area.
+// The owner records a wavefront needs: B's owner of each lane's contact by a cooperative fetch -- four lanes per record, all four
+// load instructions issued before anything waits, then a transpose through the wavefront's LDS area --, A's owner directly (the
+// list is sorted by A: ~15 distinct records per wavefront).
 // Every lane of the wavefront must call; lanes without a contact pass owner 0.
 __device__ inline void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // LDS operations of one wavefront complete in order: only the
     __builtin_amdgcn_wave_barrier();                         // compiler has to be kept from reordering
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-#ifndef DEME_FAST_STAGE_A
-#define DEME_FAST_STAGE_A 0  // A's owners: ~15 distinct records per wavefront (the list is sorted by A), loaded directly
-#endif
 __device__ inline void stage_owner_records(const OwnerRec* owners, uint32_t ownerA, uint32_t ownerB, uint4* stage, OwnerRec& OA,
                                            OwnerRec& OB) {
     const uint32_t lane = threadIdx.x & 63u, piece = lane & 3u, sub = lane >> 2;
     uint4 vb[4];
-#if DEME_FAST_STAGE_A
-    uint4 va[4];
-#endif
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const uint32_t ob = (uint32_t)__shfl((int)ownerB, (int)(16 * k + sub));
         vb[k] = reinterpret_cast<const uint4*>(owners + ob)[piece];
-#if DEME_FAST_STAGE_A
-        const uint32_t oa = (uint32_t)__shfl((int)ownerA, (int)(16 * k + sub));
-        va[k] = reinterpret_cast<const uint4*>(owners + oa)[piece];
-#endif
     }
     const uint4* mine = stage + lane * DEME_REC_LDS_STRIDE;
-    uint4* q;
-#if DEME_FAST_STAGE_A
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        stage[(16 * k + sub) * DEME_REC_LDS_STRIDE + piece] = va[k];
-    wave_lds_fence();
-    q = reinterpret_cast<uint4*>(&OA);
-    q[0] = mine[0], q[1] = mine[1], q[2] = mine[2], q[3] = mine[3];
-    wave_lds_fence();
-#else
     OA = load_owner(owners, ownerA);
-#endif
 #pragma unroll
     for (int k = 0; k < 4; k++)
         stage[(16 * k + sub) * DEME_REC_LDS_STRIDE + piece] = vb[k];
     wave_lds_fence();
-    q = reinterpret_cast<uint4*>(&OB);
+    uint4* const q = reinterpret_cast<uint4*>(&OB);
     q[0] = mine[0], q[1] = mine[1], q[2] = mine[2], q[3] = mine[3];
 }
 

@@ -43,12 +43,6 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_jit.h"
 #include "deme_kernels.h"
 #include "deme_tile.h"
-#ifndef DEME_TILE_P_PARTS
-#define DEME_TILE_P_PARTS 32u  // (deme_tile_p.h)
-#endif
-namespace deme_dev {
-int launch_tile_forces_p(int which, unsigned nCU, unsigned ldsBytes, hipStream_t st, const DevParams& dp, const TileArgs& ta);  // deme_tile_p.hip
-}
 #include "deme_tile_step.h"
 #include "deme_migrate.h"
 #include "deme_mesh_kernels.h"
@@ -77,7 +71,6 @@ struct TimerSlot {
 
 struct deme_ctx {
     int device = 0;
-    int nCU = 256;  // compute units of the device (how many persistent workgroups a launch holds)
     hipStream_t stream = nullptr;
     bool ownStream = true;
     std::string err;
@@ -97,7 +90,6 @@ struct deme_ctx {
     uint32_t nHeavy = 0, nHeavyFree = 0, nSA = 0, nSM = 0;
     DevBuf info;
     // owner-tile form of the force pass (deme_tile.h), rebuilt per detection
-    DevBuf tileCtr;  // k_tile_forces_p: (tiles handed out, workgroups through) per pass; zero between launches
     DevBuf tileBig, bigList, tInfo, hList, hCount, tileMode, tileOrg, rIdx, rStart, remKey[2], remVal, lPos, lOff, lCount, tileRem, tileBase, rankC, rec32;
     // the heavy-owner counts of a tiled list are fetched without stopping the stream: the copy lands in pinned memory, the first
     // reader (launch_reduce_heavy, one force launch later) waits for its event
@@ -110,7 +102,6 @@ struct deme_ctx {
     bool legacyLists = false;  // the B-sorted list of the round-2 kernels exists for the current contact list (built on demand when the list has tile structures)
     bool tileActive = false;  // the current list has tile structures (built-in model, fast mode, every halo fits)
     bool conTile = false;     // the contributions in memory were written by the tile kernel
-    int tileEnable = 1;       // DEME_TILE=0 keeps the round-2 kernels (A/B measurements)
     // the whole step in one kernel (deme_tile_step.h): closed tiles -- a contact that straddles two tiles is evaluated by both --
     // integrate their own owners; owners and history are double-buffered
 #define DEME_FUSED_AUTO_MAX_OWNERS 100000u  // deme_set_fused_step(ctx, 2): the one-kernel step where it was measured faster (header)
@@ -169,12 +160,8 @@ struct deme_ctx {
     bool pairsOnce = false;
     PrescArgs laterPa{nullptr, nullptr};  // the prescription records of the step whose integration is split (launch_integrate_later)
     bool crossStale = false;  // a scene was uploaded while the group evaluates cross-cut contacts once: rev_setup_slab runs again first
-    hipEvent_t evPass1 = nullptr;
     char* pin = nullptr;       // 16 KB of pinned host memory: where the detection's read-backs land
     int spinSync = 1;          // DEME_SPIN_SYNC=0: blocking waits at the detection's read-backs
-    int pass1Beside = 0;       // DEME_PASS1_BESIDE=1: the ghost-dependent force pass on the halo stream, beside the tail of the interior
-                               // pass (off: on the one-GPU harness -- two slabs competing for one GPU -- it costs 5 %; not measured with
-                               // one slab per GPU, where the interior pass leaves the GPU to a few per cent of the tiles)
     bool listOwnersSnap = false;  // (asynchronous detection) part 2 runs beside the steps too: it reads the snapshot, writes the spare set
     DevBuf spare[40];              // the second set of the list structures (list_set): the steps in flight read one, part 2 builds the other
     bool snapPending = false;  // (slab group) take the owner snapshot of an asynchronous detection in this step, once the ghosts are in place
@@ -847,7 +834,7 @@ int build_legacy_lists(deme_ctx* c) {
 
 void resolve_heavy_counts(deme_ctx* c);
 // a list built with tile structures that the round-2 kernels evaluate after all (contact recording switched on, the arithmetic
-// mode changed, DEME_TILE=0 set between detections ...): its B-sorted form is built now
+// mode changed ...): its B-sorted form is built now
 int ensure_legacy_lists(deme_ctx* c) {
     if (c->legacyLists || !c->haveList)
         return DEME_OK;
@@ -874,7 +861,7 @@ int detect_part2(deme_ctx* c, uint64_t nC) {
         }
         // per-owner gather lists for the atomics-free accumulation
         HIPCK(hipMemsetAsync(c->rangeCtr.p, 0, sizeof(RangeCounters), c->stream));
-        const bool tileEligible = c->tileEnable && nC && c->arith == DEME_ARITH_FAST &&
+        const bool tileEligible = nC && c->arith == DEME_ARITH_FAST &&
                                   (c->hp.forceModel != DEME_FORCE_CUSTOM ||
                                    (c->customTileFn[0] && nC >= (uint64_t)c->tileMinContactsCustom * ((c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB))) &&
                                   c->hShared.empty() && c->nMat <= 16 && c->nAnal <= 65535 && c->nComp <= 65535 &&
@@ -1122,16 +1109,13 @@ void launch_reduce_heavy(deme_ctx* c, bool skipFixed) {
 // (160 KB of LDS per CU, allocated in 512-byte blocks; the kernels' registers allow four workgroups)
 static uint32_t tile_record_stride(uint32_t hCap, uint32_t lCap, uint32_t tabBytes, int model) {
     const uint32_t base = tile_rec16(model);
-    static const int padEnv = getenv("DEME_TILE_PAD_RECORDS") ? atoi(getenv("DEME_TILE_PAD_RECORDS")) : 1;
-    if (model == 2 || !padEnv)  // (80-byte records start on 16 banks already)
+    if (model == 2)  // (80-byte records start on 16 banks already)
         return base;
     auto groups = [&](uint32_t rs) { return std::min<uint32_t>(4u, 163840u / ((tile_lds_bytes(hCap, lCap, tabBytes, rs) + 511u) & ~511u)); };
     return groups(base + 1u) == groups(base) ? base + 1u : base;
 }
 // pass: -1 everything in one launch; 0 / 1 the two halves of a split step (contacts that read no ghost owner / the rest)
-// `fs`: the stream of a tile-form launch when it is not the context's (the ghost-dependent pass of a split step runs on the halo
-// stream, beside the tail of the interior pass)
-int launch_forces(deme_ctx* c, int pass = -1, hipStream_t fs = nullptr) {
+int launch_forces(deme_ctx* c, int pass = -1) {
     c->fusedPrevValid = false;
     if (c->nContacts == 0) {
         c->conValid = true;
@@ -1174,7 +1158,7 @@ int launch_forces(deme_ctx* c, int pass = -1, hipStream_t fs = nullptr) {
     // through the general kernel
     const bool fastKernel = fastMode && c->hp.forceModel != DEME_FORCE_CUSTOM;
     const bool customTile = fastMode && !c->record && c->hp.forceModel == DEME_FORCE_CUSTOM && c->customTileFn[0];
-    if ((fastKernel || customTile) && c->tileActive && c->tileEnable) {  // owner tiles: deme_tile.h
+    if ((fastKernel || customTile) && c->tileActive) {  // owner tiles: deme_tile.h
         if (c->fusedList && !c->fusedChecked)
             resolve_heavy_counts(c);
         TileArgs ta{};
@@ -1210,16 +1194,11 @@ int launch_forces(deme_ctx* c, int pass = -1, hipStream_t fs = nullptr) {
         ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (c->tileMaxHalo + 15u) & ~15u);
         ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (c->tileMaxList + 15u) & ~15u);
         ta.nComp = c->nComp, ta.nAnal = c->nAnal, ta.nMass = c->nMassProps;
-        static const uint32_t ldsPad = getenv("DEME_TILE_LDS_PAD") ? (uint32_t)atoi(getenv("DEME_TILE_LDS_PAD")) : 0u;  // occupancy experiments
         const uint32_t tabBytes = tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial);
         ta.rs16 = tile_record_stride(ta.hCap, ta.lCap, tabBytes, customTile ? 2 : 0);
-        static const int swzEnv = getenv("DEME_TILE_SWIZZLE") ? atoi(getenv("DEME_TILE_SWIZZLE")) : 1;  // (2: rotate instead of padding everywhere)
-        if (swzEnv == 2 && !customTile)
-            ta.rs16 = tile_rec16(0);
-        ta.swz = (swzEnv && !customTile && ta.rs16 == tile_rec16(0)) ? 1u : 0u;
-        const uint32_t ldsBytes = tile_lds_bytes(ta.hCap, ta.lCap, tabBytes, ta.rs16) + ldsPad;
-        hipStream_t st = fs ? fs : c->stream;
-        ScopedTimer tm(c, "calc_forces", false, st);
+        ta.swz = (!customTile && ta.rs16 == tile_rec16(0)) ? 1u : 0u;
+        const uint32_t ldsBytes = tile_lds_bytes(ta.hCap, ta.lCap, tabBytes, ta.rs16);
+        ScopedTimer tm(c, "calc_forces");
         const bool mesh = c->nTri > 0 && c->nSM > 0;
         if (mesh) {
             ta.conA4 = a.conA4, ta.conA2 = a.conA2, ta.conB4 = a.conB4, ta.conB2 = a.conB2;
@@ -1236,61 +1215,19 @@ int launch_forces(deme_ctx* c, int pass = -1, hipStream_t fs = nullptr) {
             }
         }
         const unsigned nBig = c->nBigTiles;  // tiles that do not fit LDS: one workgroup each, the same outputs (deme_tile.h)
-#if DEME_TILE_STAMPS
-        // measurement builds: DEME_TILE_STAMPS_FILE=path[:launch] -- the phase stamps of every tile of that launch (default the 100th), 16 words per tile
-        static const char* stampEnv = getenv("DEME_TILE_STAMPS_FILE");
-        static unsigned long long* stampBuf = nullptr;
-        static int stampLaunch = 0, stampAt = 100;
-        static std::string stampPath;
-        if (stampEnv && !stampBuf && !customTile) {
-            stampPath = stampEnv;
-            const size_t colon = stampPath.rfind(':');
-            if (colon != std::string::npos)
-                stampAt = atoi(stampPath.c_str() + colon + 1), stampPath.resize(colon);
-            HIPCK(hipMalloc(&stampBuf, (size_t)ta.nTiles * 16 * 8));
-            HIPCK(hipMemset(stampBuf, 0, (size_t)ta.nTiles * 16 * 8));
-        }
-        const bool stampNow = stampBuf && ++stampLaunch == stampAt;
-        ta.stamps = stampNow ? stampBuf : nullptr;
-        struct StampDump {
-            bool on; hipStream_t st; unsigned long long* buf; size_t n; const std::string& path;
-            ~StampDump() {
-                if (!on) return;
-                hipStreamSynchronize(st);
-                std::vector<unsigned long long> h(n);
-                hipMemcpy(h.data(), buf, n * 8, hipMemcpyDeviceToHost);
-                if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(h.data(), 8, n, f); fclose(f); }
-            }
-        } stampDump{stampNow, st, stampBuf, (size_t)ta.nTiles * 16, stampPath};
-#endif
         if (customTile) {  // the same kernels compiled at run time around the user's statements (deme_jit.h)
             void* argsT[] = {&c->dp, &ta};
-            HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 1 : 0], nBlk, 1, 1, DEME_TILE_T, 1, 1, ldsBytes, st, argsT, nullptr));
+            HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 1 : 0], nBlk, 1, 1, DEME_TILE_T, 1, 1, ldsBytes, c->stream, argsT, nullptr));
             if (nBig)
-                HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 3 : 2], nBig, 1, 1, DEME_TILE_T, 1, 1, 0, st, argsT, nullptr));
+                HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 3 : 2], nBig, 1, 1, DEME_TILE_T, 1, 1, 0, c->stream, argsT, nullptr));
         } else {
             // (model, mesh records, recording) -> the instance of the two kernels
             const int model = c->hp.forceModel == DEME_FORCE_HERTZIAN ? 0 : 1;
             const int which = model * 4 + (mesh ? 2 : 0) + (c->record ? 1 : 0);
-            // persistent workgroups (deme_tile_p.h): as many as the chip holds at once, each taking tile after tile from a counter
-            static const int persistEnv = getenv("DEME_TILE_PERSIST") ? atoi(getenv("DEME_TILE_PERSIST")) : 0;
-            if (persistEnv) {
-                const size_t ctrWords = ((size_t)DEME_TILE_P_PARTS + 1u) * 32u;  // (deme_tile_p.h: one set per pass)
-                if (!c->tileCtr.p) {
-                    if (int rc = ensure(c, c->tileCtr, 3 * ctrWords * 4))
-                        return rc;
-                    HIPCK(hipMemset(c->tileCtr.p, 0, 3 * ctrWords * 4));
-                }
-                ta.tileCtr = c->tileCtr.as<uint32_t>() + ctrWords * (size_t)(pass + 1);
-            }
-            hipError_t perr = hipSuccess;
             auto go = [&](auto tileK, auto bigK) {
-                if (persistEnv)
-                    perr = (hipError_t)launch_tile_forces_p(which, (unsigned)c->nCU, ldsBytes, st, c->dp, ta);
-                else
-                    hipLaunchKernelGGL(tileK, dim3(nBlk), dim3(DEME_TILE_T), ldsBytes, st, c->dp, ta);
+                hipLaunchKernelGGL(tileK, dim3(nBlk), dim3(DEME_TILE_T), ldsBytes, c->stream, c->dp, ta);
                 if (nBig)
-                    hipLaunchKernelGGL(bigK, dim3(nBig), dim3(DEME_TILE_T), 0, st, c->dp, ta);
+                    hipLaunchKernelGGL(bigK, dim3(nBig), dim3(DEME_TILE_T), 0, c->stream, c->dp, ta);
             };
             switch (which) {
                 case 0: go(k_tile_forces<0, false, false>, k_tile_forces_big<0, false, false>); break;
@@ -1302,8 +1239,6 @@ int launch_forces(deme_ctx* c, int pass = -1, hipStream_t fs = nullptr) {
                 case 6: go(k_tile_forces<1, true, false>, k_tile_forces_big<1, true, false>); break;
                 default: go(k_tile_forces<1, true, true>, k_tile_forces_big<1, true, true>); break;
             }
-            if (perr != hipSuccess)
-                return fail(c, DEME_ERR_HIP, "k_tile_forces_p: %s", hipGetErrorString(perr));
         }
         c->conValid = true;
         c->conTile = true;
@@ -1356,7 +1291,7 @@ int launch_forces(deme_ctx* c, int pass = -1, hipStream_t fs = nullptr) {
 // The whole step in one launch (deme_tile_step.h).  dry: replay the force evaluation of the step just taken on the buffers of its
 // start and leave a / alpha (state downloads).
 bool fused_ready(deme_ctx* c) {
-    if (!c->fusedList || !c->tileActive || !c->tileEnable || c->arith != DEME_ARITH_FAST || c->record || c->hp.forceModel == DEME_FORCE_CUSTOM ||
+    if (!c->fusedList || !c->tileActive || c->arith != DEME_ARITH_FAST || c->record || c->hp.forceModel == DEME_FORCE_CUSTOM ||
         c->prescFn || c->rulesFn || c->nContacts == 0)
         return false;
     if (!c->fusedChecked)
@@ -1540,8 +1475,6 @@ int deme_ctx_create(int device, deme_ctx** out) {
         return DEME_ERR_HIP;
     deme_ctx* c = new deme_ctx();
     c->device = device;
-    if (hipDeviceGetAttribute(&c->nCU, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->nCU <= 0)
-        c->nCU = 256;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return DEME_ERR_HIP;
@@ -1559,12 +1492,8 @@ int deme_ctx_create(int device, deme_ctx** out) {
         c->arith = (strcmp(e, "exact") == 0) ? DEME_ARITH_EXACT : DEME_ARITH_FAST;
     if (const char* e = getenv("DEME_XCD_GROUP"))  // tuning knob (profiles/): see force_block_id
         c->xcdGroup = (uint32_t)std::max(0, atoi(e));
-    if (const char* e = getenv("DEME_TILE"))  // 0: keep the per-contact-block force kernel (A/B measurements)
-        c->tileEnable = atoi(e);
     if (const char* e = getenv("DEME_SPIN_SYNC"))
         c->spinSync = atoi(e);
-    if (const char* e = getenv("DEME_PASS1_BESIDE"))
-        c->pass1Beside = atoi(e);
     if (const char* e = getenv("DEME_KEY_SEG_MIN"))  // tests lower it to put small scenes through the segmented arena; 0 = one segment always
         c->keySegMin = (size_t)std::max(0ll, atoll(e));
     *out = c;
@@ -1596,8 +1525,6 @@ void deme_ctx_destroy(deme_ctx* c) {
     }
     if (c->pin)
         hipHostFree(c->pin);
-    if (c->evPass1)
-        hipEventDestroy(c->evPass1);
     for (DevBuf& b : c->spare)
         if (b.p)
             hipFree(b.p);
@@ -1611,7 +1538,7 @@ void deme_ctx_destroy(deme_ctx* c) {
         hipEventDestroy(c->evP1);
         hipStreamDestroy(c->detStream);
     }
-    DevBuf* all[] = {&c->tileCtr, &c->hCountIn, &c->ownersNext, &c->recContact, &c->inCnt, &c->inStart, &c->tInfoIn, &c->inContact, &c->sphFam, &c->tileBig, &c->bigList, &c->dO2E, &c->dS2E, &c->segCtr, &c->tInfo, &c->hList, &c->hCount, &c->tileMode, &c->tileOrg, &c->rIdx, &c->rStart, &c->remKey[0], &c->remKey[1], &c->lPos, &c->lOff, &c->lCount, &c->tileRem, &c->tileBase, &c->remVal, &c->rankC, &c->rec32, &c->revSlot, &c->nextAcc, &c->binStat, &c->volumes, &c->persistKeys, &c->owners, &c->spheres, &c->acc, &c->conA4, &c->conA2, &c->conB4, &c->conB2, &c->aSum, &c->prescList, &c->prescSlot, &c->prescRec, &c->smFlag, &c->smList, &c->cDefer, &c->blockMode, &c->ownerA, &c->ownerB[0], &c->ownerB[1], &c->bIdx[0], &c->bIdx[1], &c->aStart, &c->bStart, &c->heavy, &c->fixedFlag, &c->heavyList, &c->rangeCtr, &c->info, &c->tris, &c->triWorld, &c->triLo, &c->triHi, &c->triCounts, &c->triOffsets, &c->triKeys[0], &c->triKeys[1], &c->triVals[0], &c->triVals[1], &c->comp, &c->massProps, &c->anal, &c->matPair,
+    DevBuf* all[] = {&c->hCountIn, &c->ownersNext, &c->recContact, &c->inCnt, &c->inStart, &c->tInfoIn, &c->inContact, &c->sphFam, &c->tileBig, &c->bigList, &c->dO2E, &c->dS2E, &c->segCtr, &c->tInfo, &c->hList, &c->hCount, &c->tileMode, &c->tileOrg, &c->rIdx, &c->rStart, &c->remKey[0], &c->remKey[1], &c->lPos, &c->lOff, &c->lCount, &c->tileRem, &c->tileBase, &c->remVal, &c->rankC, &c->rec32, &c->revSlot, &c->nextAcc, &c->binStat, &c->volumes, &c->persistKeys, &c->owners, &c->spheres, &c->acc, &c->conA4, &c->conA2, &c->conB4, &c->conB2, &c->aSum, &c->prescList, &c->prescSlot, &c->prescRec, &c->smFlag, &c->smList, &c->cDefer, &c->blockMode, &c->ownerA, &c->ownerB[0], &c->ownerB[1], &c->bIdx[0], &c->bIdx[1], &c->aStart, &c->bStart, &c->heavy, &c->fixedFlag, &c->heavyList, &c->rangeCtr, &c->info, &c->tris, &c->triWorld, &c->triLo, &c->triHi, &c->triCounts, &c->triOffsets, &c->triKeys[0], &c->triKeys[1], &c->triVals[0], &c->triVals[1], &c->comp, &c->massProps, &c->anal, &c->matPair,
                      &c->E, &c->nu, &c->CoR, &c->mu, &c->Crr, &c->famMasks, &c->famExtra, &c->famFlags, &c->geo,
                      &c->binLo, &c->binN, &c->counts, &c->offsets, &c->incKeys[0], &c->incKeys[1], &c->incVals[0],
                      &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->mapping, &c->wc[0],
@@ -1679,11 +1606,11 @@ int deme_force_kernel_name(const deme_ctx* c, char* name, size_t cap, uint32_t* 
     const bool fastKernel = c->arith == DEME_ARITH_FAST && c->hp.forceModel != DEME_FORCE_CUSTOM;
     if (c->fusedPrevValid && c->fusedList && c->tileActive)  // the last step went through the one-kernel step (deme_tile_step.h)
         snprintf(name, cap, "k_tile_step<%d>", m);
-    else if (c->hp.forceModel == DEME_FORCE_CUSTOM && c->arith == DEME_ARITH_FAST && !c->record && c->customTileFn[0] && c->tileActive && c->tileEnable)
+    else if (c->hp.forceModel == DEME_FORCE_CUSTOM && c->arith == DEME_ARITH_FAST && !c->record && c->customTileFn[0] && c->tileActive)
         snprintf(name, cap, "deme_custom_tile<%s>", (c->nTri > 0 && c->nSM > 0) ? "true" : "false");
     else if (c->hp.forceModel == DEME_FORCE_CUSTOM)
         snprintf(name, cap, "deme_custom_forces_ss");
-    else if (fastKernel && c->tileActive && c->tileEnable)
+    else if (fastKernel && c->tileActive)
         snprintf(name, cap, "k_tile_forces<%d, %s>", m, (c->nTri > 0 && c->nSM > 0) ? "true" : "false");
     else if (fastKernel && !c->record)
         snprintf(name, cap, "k_forces_fast<%d>", m);
@@ -2666,20 +2593,6 @@ static int overlap_forces(deme_ctx* c) {
         return rc;
     if (int rc = ensure_halo_stream(c))
         return rc;
-    // The ghost-dependent pass of a split step touches a few per cent of the tiles: launched behind the interior pass it would run
-    // alone on a mostly empty GPU.  In the tile form it goes to the halo stream instead -- which holds the ghosts as soon as its
-    // unpack is done -- and its workgroups take the slots the interior pass frees; the integration waits for both.
-    const bool pass1Beside = !c->overlapDetect && !c->snapPending && c->tileActive && c->tileEnable && c->arith == DEME_ARITH_FAST &&
-                             !c->record && c->hp.forceModel != DEME_FORCE_CUSTOM && c->nContacts != 0 && c->pass1Beside;
-    if (pass1Beside) {
-        if (!c->evPass1)
-            HIPCK(hipEventCreateWithFlags(&c->evPass1, hipEventDisableTiming));
-        if (int rc = launch_forces(c, 1, c->haloStream))
-            return rc;
-        HIPCK(hipEventRecord(c->evPass1, c->haloStream));
-        HIPCK(hipStreamWaitEvent(c->stream, c->evPass1, 0));
-        return DEME_OK;
-    }
     HIPCK(hipStreamWaitEvent(c->stream, c->evHaloDone, 0));
     if (c->snapPending)  // an asynchronous detection starts from this moment: own clumps and ghosts both hold the state of the step just integrated
         if (int rc = async_snapshot(c))

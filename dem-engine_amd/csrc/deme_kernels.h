@@ -853,7 +853,7 @@ struct GatherArgs {
     // owner-tile form of the force pass (deme_tile.h): aSum holds, for EVERY owner, the sum over the contacts its tile evaluated
     // (A and B sides); bStart / bIdx list only the contacts whose B owner lives in another tile than A's, with records in conB
     uint32_t tile;
-    const float4* rec32;     // tile form: the crossing contacts' B-side records, 32 bytes each, dense; bIdx holds record numbers
+    const float4* rec32;     // tile form: the crossing contacts' B-side records, 24 bytes each, dense; bIdx holds record numbers
     // one evaluation per cross-cut contact (deme_halo_group_set_cross_contacts): the neighbour that evaluated an own clump's
     // contacts with ITS clumps sends a / alpha of their sum; revSlot[o] = the clump's place in that message, 0xFFFFFFFF = none
     const uint32_t* revSlot;
@@ -865,14 +865,9 @@ struct GatherArgs {
 // one B-side record for the per-owner gather: by contact index from the two per-contact arrays, or (tile form) by record number
 __device__ inline void gather_b_load(const GatherArgs& g, uint32_t idx, float4& c4, float2& c2) {
     if (g.tile) {
-#if DEME_REC24
         const float2* r24 = reinterpret_cast<const float2*>(g.rec32) + 3 * (size_t)idx;  // deme_tile.h: 24-byte records
         const float2 r0 = r24[0], r1 = r24[1];
         c4 = make_float4(r0.x, r0.y, r1.x, r1.y), c2 = r24[2];
-#else
-        const float4 r0 = g.rec32[2 * (size_t)idx], r1 = g.rec32[2 * (size_t)idx + 1];
-        c4 = r0, c2 = make_float2(r1.x, r1.y);
-#endif
     } else {
         conb_load(g.conB4, g.conB2, idx, c4, c2);
     }
@@ -892,15 +887,13 @@ __device__ inline void acc_from_world(const DevParams& p, const OwnerRec& r, flo
 // same in-order sum over the per-contact records (loads issued four at a time).
 __device__ inline void a_side_sum(const GatherArgs& g, uint32_t o, uint32_t s, uint32_t e, float& ax, float& ay, float& az,
                                   float& lx, float& ly, float& lz) {
-#if DEME_REC24
     if (g.tile) {  // the tile pass leaves six floats per owner (deme_tile.h)
         const float2* t24 = reinterpret_cast<const float2*>(g.aSum) + 3 * (size_t)o;
         const float2 u = t24[0], v = t24[1], w = t24[2];
         ax = u.x, ay = u.y, az = v.x, lx = v.y, ly = w.x, lz = w.y;
         return;
     }
-#endif
-    if (g.tile || a_run_in_one_block(s, e)) {
+    if (a_run_in_one_block(s, e)) {
         const float4 v = g.aSum[2 * (size_t)o], w = g.aSum[2 * (size_t)o + 1];
         ax = v.x, ay = v.y, az = v.z, lx = w.x, ly = w.y, lz = w.z;
         return;
@@ -1078,13 +1071,10 @@ __global__ __launch_bounds__(256) void k_reduce_heavy(const DevParams p, const G
         const uint32_t a0 = g.aStart[o], a1 = g.aStart[o + 1];
         if (g.tile || a_run_in_one_block(a0, a1)) {
             if (threadIdx.x == 0) {
-#if DEME_REC24
                 if (g.tile) {
                     const float2* t24 = reinterpret_cast<const float2*>(g.aSum) + 3 * (size_t)o;
                     s[0] = t24[0].x, s[1] = t24[0].y, s[2] = t24[1].x, s[3] = t24[1].y, s[4] = t24[2].x, s[5] = t24[2].y;
-                } else
-#endif
-                {
+                } else {
                     const float4 v = g.aSum[2 * (size_t)o], w = g.aSum[2 * (size_t)o + 1];
                     s[0] = v.x, s[1] = v.y, s[2] = v.z, s[3] = w.x, s[4] = w.y, s[5] = w.z;
                 }
@@ -1293,9 +1283,6 @@ struct PrescArgs {
 // The 64 consecutive owner records of a wavefront, read and written as 4 KB of contiguous memory (four fully coalesced 16-byte
 // accesses per lane) and transposed to one record per lane through LDS -- a lane that loads or stores its own 64-byte record
 // piece by piece makes every instruction touch 64 different cache lines (the vector L1 serves one per cycle).
-#ifndef DEME_INT_COOP
-#define DEME_INT_COOP 1
-#endif
 #define DEME_INT_STAGE (64 * 5)  // uint4 per wavefront: records at an 80-byte stride (bank-conflict-free ds_read_b128 per lane)
 __device__ inline void lds_wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // LDS operations of one wavefront complete in order: only the
@@ -1350,20 +1337,16 @@ __global__ __launch_bounds__(256) void k_integrate(const DevParams p, OwnerRec* 
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = o < p.nOwners;
     // one LDS area: the record transposes at both ends of the kernel, the gather tiles of the fused path in between
-    constexpr uint32_t kStage16 = DEME_INT_COOP ? 4u * DEME_INT_STAGE : 1u, kGather16 = FUSED ? (uint32_t)(sizeof(GatherLds) / 16) : 1u;
+    constexpr uint32_t kStage16 = 4u * DEME_INT_STAGE, kGather16 = FUSED ? (uint32_t)(sizeof(GatherLds) / 16) : 1u;
     __shared__ uint4 smem[kStage16 > kGather16 ? kStage16 : kGather16];
     GatherPre pre{};
     if (FUSED)
         pre = gather_prefetch(g, p.nOwners, o, valid);
-#if DEME_INT_COOP
     uint4* stage = smem + (threadIdx.x >> 6) * DEME_INT_STAGE;
     const uint32_t waveBase = o - (threadIdx.x & 63u);
     OwnerRec r = coop_load_owner(owners, p.nOwners, waveBase, stage);
     if (FUSED)
         __syncthreads();  // every wavefront has its records in registers before the gather tiles overwrite the area
-#else
-    OwnerRec r = load_owner(owners, valid ? o : 0u);
-#endif
     const uint32_t fflags = p.familyFlags[fam_of(r.family)];
     const bool ghost = ghost_of(r.family);  // its owner rank integrates it; refreshed by deme_halo_unpack
     const bool fixed = (fflags & 1u) != 0;
@@ -1394,12 +1377,7 @@ __global__ __launch_bounds__(256) void k_integrate(const DevParams p, OwnerRec* 
     }
     if (valid && !ghost && !later)
         integrate_owner(p, r, a, al, o, fflags, fixed, g, pa);
-#if DEME_INT_COOP
     coop_store_owner(owners, p.nOwners, waveBase, stage, r);  // a record nobody integrated goes back as it came
-#else
-    if (valid && !ghost && !later)
-        store_owner(owners, o, r);
-#endif
 }
 
 // the owners k_integrate left for later (revPhase 1): the same update, one thread per listed owner, sums gathered per thread in the

@@ -17,7 +17,7 @@
 //     ordering between wavefronts, a fixed summation order, reproducible run to run.  (LDS float atomics were measured at ~2 cycles
 //     PER LANE on gfx950 -- 12 of them per contact made the first version of this kernel 2.6 times slower than k_forces_fast -- and
 //     in-wavefront segmented DPP scans of the six sums cost 230 instructions per 64 contacts, a third of the kernel.)
-//     The sums leave the workgroup as ONE 32-byte record per owner; only a contact whose B owner lives in another tile writes a
+//     The sums leave the workgroup as ONE 24-byte record per owner; only a contact whose B owner lives in another tile writes a
 //     24-byte record, which the integrator gathers through the per-owner list of such contacts (deme_kernels.h:
 //     k_integrate<true> with GatherArgs::tile).
 // What the per-detection builder below leaves behind: tInfo (8 B per contact), the halo list of every tile, the per-owner lists
@@ -64,36 +64,7 @@ static_assert(DEME_TILE_HMAX <= DEME_TILE_HP2 && DEME_TILE_HMAX <= 256, "halo li
 
 namespace deme_dev {
 
-// Measurement builds (make variant EXTRA=-DDEME_TILE_KI=bits): "knock-in" duplicates of one section of k_tile_forces behind opaque
-// values -- the physics is untouched, the extra time of a variant is what that section costs (bit 0: the two sphere-offset
-// rotations + their fp64 conversions; 1: the pulls; 2: the staging conversion; 3: the whole per-contact evaluation) -- and
-// "knock-outs" of stores (bit 4: history; 5: crossing records; 6: tile sums: wrong results, timing only); bit 7: one more level of
-// dependent loads in front of the ids of the foreign owners; bit 8: one more barrier per round.
-#ifndef DEME_TILE_KI
-#define DEME_TILE_KI 0
-#endif
-// -DDEME_TILE_STAMPS=1: thread 0 of every tile leaves the 100 MHz wall clock at its phase boundaries (words 0 start, 1 tables in LDS,
-// 2 staged, 3.. the end of each round, 11 the end) and where it ran (word 12: HW_ID | XCC_ID << 32; 13: contacts; 14: foreign owners;
-// 15: shader cycles (s_memtime) over the tile's life -- with words 0 and 11 the clock the kernel runs at)
-#ifndef DEME_TILE_STAMPS
-#define DEME_TILE_STAMPS 0
-#endif
-#if DEME_TILE_STAMPS
-#define TILE_STAMP(k)                                                                  \
-    do {                                                                               \
-        if (a.stamps && threadIdx.x == 0)                                              \
-            a.stamps[(size_t)t * 16u + (k)] = (unsigned long long)wall_clock64();      \
-    } while (0)
-#else
-#define TILE_STAMP(k) \
-    do {              \
-    } while (0)
-#endif
 typedef float v2f __attribute__((ext_vector_type(2)));  // a register pair: += compiles to v_pk_add_f32
-__device__ inline void ki_opaque(float& v) { asm volatile("" : "+v"(v)); }
-__device__ inline void ki_opaque(uint32_t& v) { asm volatile("" : "+v"(v)); }
-__device__ inline void ki_sink(float v) { asm volatile("" ::"v"(v)); }
-__device__ inline void ki_sink(uint32_t v) { asm volatile("" ::"v"(v)); }
 
 // tInfo.x: slot of A (10) | slot of B (10) | class (2) | B lives in another tile: write a record (1) | 1 spare | material of A (4) |
 //          material of B (4);  tInfo.y: component of A (16) | component of B or analytical-object index (16)
@@ -116,9 +87,12 @@ struct TileArgs {
     const uint16_t* lPos;      // those contacts as positions in their tile's range of the list, ascending per owner; a tile's lists start
                                // at the index of the tile's first contact (there are never more of them than the tile has contacts)
     float* wc;
-    float4* tSum;              // two float4 per owner: the sum of the contributions of contacts evaluated by the owner's tile
-    float4* rec32;             // the B-side records of the contacts whose B owner lives in another tile: 32 bytes each, dense, in
-                               // list order (the k-th such contact writes record k: full cache lines instead of scattered pieces)
+    // tSum and rec32 hold 24-byte records (six floats as three 8-byte pieces) rather than two 16-byte pieces with two unused floats:
+    // -22 MB written by the force pass and -22 MB read by the integrator at 1e6 clumps (the integrator moves its bytes at the copy
+    // rate; the force pass answers to bytes with ~0.3)
+    float4* tSum;              // per owner: the sum of the contributions of contacts evaluated by the owner's tile
+    float4* rec32;             // the B-side records of the contacts whose B owner lives in another tile: dense, in list order (the
+                               // k-th such contact writes record k: full cache lines instead of scattered pieces)
     const uint32_t* rankC;     // per contact: the number of such contacts before it
     // scenes with a mesh (k_tile_forces<MODEL, true>): the sphere-triangle contacts were evaluated by the mesh variant of the general
     // kernel just before (launch_forces); the tile takes their per-contact records instead of evaluating them
@@ -146,9 +120,6 @@ struct TileArgs {
     uint32_t swz;
     uint32_t hCap, lCap;       // LDS capacities of this launch: foreign owners / local-B list entries of the largest tile (rounded up)
     uint32_t nComp, nAnal, nMass;  // table sizes (tile_table_bytes)
-    uint32_t* tileCtr;             // k_tile_forces_p (deme_tile_p.h): tiles handed out per partition, workgroups through; zero between launches
-    uint32_t ctrParts;             // ... partitions of the tiles (and of the workgroups), one counter each
-    unsigned long long* stamps;    // measurement builds (-DDEME_TILE_STAMPS=1): 16 words per tile, see k_tile_forces
 };
 
 // one staged owner, as the contact loop reads it back from LDS
@@ -288,16 +259,6 @@ __device__ inline void tile_contact(const DevParams& p, const TileTables& T, con
     const RotM &RA = A.R, &RB = B.R;
     const f3 relA = rot_apply(RA, mk3(cA.x, cA.y, cA.z));
     const float rA = cA.w;
-#if DEME_TILE_KI & 1
-    {
-        float qx = cA.x, qy = cA.y;
-        ki_opaque(qx), ki_opaque(qy);
-        const f3 r2 = rot_apply(RA, mk3(qx, qy, cA.z)), r3 = rot_apply(RB, mk3(qy, qx, cA.z));
-        const double e = (((A.px - B.px) + (double)r2.x) - (double)r3.x) + (((A.py - B.py) + (double)r2.y) - (double)r3.y) +
-                         (((A.pz - B.pz) + (double)r2.z) - (double)r3.z);
-        ki_sink((float)e);
-    }
-#endif
     float extraMargin = 0.f;
     if (!p.familyTrivial) {
         const float eA = T.fam[A.family & 0xFFu], eB = T.fam[B.family & 0xFFu];
@@ -508,31 +469,8 @@ __device__ inline uint32_t tile_block_id(uint32_t G) {
 #ifndef DEME_TILE_OCC
 #define DEME_TILE_OCC 1
 #endif
-#ifndef DEME_TILE_UNROLL
-#define DEME_TILE_UNROLL 0  // 1: the rounds unrolled DEME_TILE_DEPTH at a time, no rotation of the stream registers (measured: no gain, 3x the code)
-#endif
-#ifndef DEME_TILE_PKPULL
-#define DEME_TILE_PKPULL 1  // the pulls add register pairs (v_pk_add_f32); a missing entry reads the zero slot
-#endif
-#ifndef DEME_TILE_SPLITLOOP
-#define DEME_TILE_SPLITLOOP 0  // 1: a tile of at most DEME_TILE_DEPTH rounds (its streams were all asked for in the prologue) runs a copy of the round
-                               // loop without refills: no load is in flight there, so the rotation of the stream registers waits for nothing --
-                               // in the refilling loop the compiler's s_waitcnt vmcnt(0) in front of the rotation also drains the round's STORES
-#endif
-#ifndef DEME_TILE_PRIO_ROUNDS
-#define DEME_TILE_PRIO_ROUNDS 0  // wavefront priority of the rounds (the prologue runs at DEME_TILE_PRIO)
-#endif
-#ifndef DEME_TILE_PRIO_PULL
-#define DEME_TILE_PRIO_PULL 0  // > 0: wavefront priority between a round's two barriers (the pulls: the whole workgroup waits for them)
-#endif
 #ifndef DEME_TILE_PULLW
 #define DEME_TILE_PULLW 4  // entries an owner thread pulls per trip (a missing entry reads the zero slot)
-#endif
-#ifndef DEME_TILE_NOZERO
-#define DEME_TILE_NOZERO 1  // 1: no zero defaults for values that are only read where they were set (refilled stream stages, crossing records)
-#endif
-#ifndef DEME_TILE_PRIO
-#define DEME_TILE_PRIO 0  // > 0: wavefront priority of the prologue (ids -> records -> staging); the rounds run at 0
 #endif
 #ifndef DEME_TILE_DEPTH
 #define DEME_TILE_DEPTH 3  // rounds whose streams are in flight (tInfo + history: 24 bytes per thread and round)
@@ -559,17 +497,9 @@ __host__ __device__ inline uint32_t tile_lds_bytes(uint32_t hCap, uint32_t lCap,
            tableBytes + 16u;
 }
 
-template <bool B>
-struct TileFlag {
-    static constexpr bool value = B;
-};
-
 template <int MODEL, bool MESH, bool REC = false>
 __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(const DevParams p, const TileArgs a) {
     extern __shared__ uint4 tileLds[];
-#if DEME_TILE_PRIO
-    __builtin_amdgcn_s_setprio(DEME_TILE_PRIO);
-#endif
     uint4* const sOwn = tileLds;
     const uint32_t RSZ = a.rs16;  // uint4 per staged record: what the record holds, or one more (see TileArgs::rs16)
     float4* const recA4 = reinterpret_cast<float4*>(sOwn + (DEME_TILE_NB + a.hCap) * RSZ);
@@ -582,40 +512,20 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
     if (t >= a.nTiles)
         return;
     // Whether this tile is evaluated here at all -- the pass of a split step, a tile left to k_tile_forces_big -- is decided in FRONT of
-    // the tile's loads.  (DEME_TILE_LATE_SKIP=1 decides it behind the first loads: two scalar round trips off every tile's start --
-    // measured: 88.9 against 89.0 us, nothing, and the ghost-dependent pass of a slab step, which leaves 95 % of its tiles at once,
-    // would fetch every tile's records first.)
-#ifndef DEME_TILE_LATE_SKIP
-#define DEME_TILE_LATE_SKIP 0
-#endif
-#if DEME_TILE_LATE_SKIP
-    const uint32_t skipBig = a.tileBig[t];
-    const uint32_t skipMode = a.tileMode ? a.tileMode[t] : 0xFFFFFFFFu;
-#else
+    // the tile's loads: the ghost-dependent pass of a slab step leaves 95 % of its tiles at once, and would otherwise fetch every
+    // tile's records first.
     if (a.tileMode && !(a.tileMode[t] & (1u << a.pass)))
         return;
     if (a.tileBig[t])
         return;
-#endif
     const uint32_t tid = threadIdx.x;
     const uint32_t o0 = t * DEME_TILE_NB;
     const uint32_t nLoc = min((uint32_t)DEME_TILE_NB, a.nOwners - o0);
-    TILE_STAMP(0);
-#if DEME_TILE_STAMPS
-    const unsigned long long stampClk0 = (unsigned long long)clock64();  // (s_memtime: shader cycles; word 15 = cycles over the tile's life)
-#endif
     // ---- every load that needs nothing but the tile number goes out first: the ids of the foreign owners behind my staging slots
     // (the list is padded to DEME_TILE_HMAX per tile: reading past the tile's own count is harmless), my local owner's record,
     // my entries of the small tables.  A tile's lifetime is a chain of memory latencies; this makes it two deep
     // (ids -> foreign records), with the scalars -> streams chain beside it.
     const uint32_t* hl = a.hList + (size_t)t * DEME_TILE_HMAX;
-#if DEME_TILE_KI & 128  // knock-in: one more level in the chain of dependent loads (a vector load in front of the ids)
-    {
-        uint32_t zz = a.rankC[t];
-        asm volatile("v_and_b32 %0, 0, %0" : "+v"(zz));
-        hl += zz;
-    }
-#endif
     const uint32_t h0 = tid - nLoc, h1 = tid + DEME_TILE_T - nLoc;  // my foreign slots (meaningful when < nH)
     uint32_t id0 = (tid >= nLoc && h0 < DEME_TILE_HMAX) ? hl[h0] : 0u;
     uint32_t id1 = (h1 < DEME_TILE_HMAX) ? hl[h1] : 0u;
@@ -652,10 +562,6 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
     const uint16_t* const lOffT = a.lOff + (size_t)t * (DEME_TILE_NB + 1);
     const uint32_t nL = a.lCount[t];  // (a 32-bit word: a scalar load -- a 16-bit one would be a vector load, whose wait drains the loads issued before it)
     const int64_t u0x = a.org[3 * (size_t)t], u0y = a.org[3 * (size_t)t + 1], u0z = a.org[3 * (size_t)t + 2];
-#if DEME_TILE_LATE_SKIP
-    if (skipBig || !(skipMode & (1u << a.pass)))
-        return;
-#endif
     const float4* wc4 = reinterpret_cast<const float4*>(a.wc);
     uint2 inf[DEME_TILE_DEPTH];
     float4 hist[DEME_TILE_DEPTH];
@@ -707,20 +613,7 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
     if (!p.familyTrivial)
         const_cast<float*>(T.fam)[tid & 255u] = tabFam;
     __syncthreads();  // (the staging below reads the masses)
-    TILE_STAMP(1);
     {   // stage the tile's owners, its halo, the owners' run bounds and local-B lists
-#if DEME_TILE_KI & 4
-        if (tid < nLoc + nH) {
-            OwnerRec r2 = rec0;
-            ki_opaque(r2.qw), ki_opaque(r2.wx), ki_opaque(r2.family);
-            tile_stage<MODEL>(p, T.mass[r2.inertiaOff], r2, u0x, u0y, u0z, sOwn + (tid < nLoc ? tid : DEME_TILE_NB + h0) * RSZ, ((tid < nLoc ? tid : DEME_TILE_NB + h0) >> 3) & a.swz);
-        }
-        if (h1 < nH) {
-            OwnerRec r2 = rec1;
-            ki_opaque(r2.qw), ki_opaque(r2.wx), ki_opaque(r2.family);
-            tile_stage<MODEL>(p, T.mass[r2.inertiaOff], r2, u0x, u0y, u0z, sOwn + (DEME_TILE_NB + h1) * RSZ, ((DEME_TILE_NB + h1) >> 3) & a.swz);
-        }
-#endif
         if (tid < nLoc + nH)
             tile_stage<MODEL>(p, T.mass[rec0.inertiaOff], rec0, u0x, u0y, u0z, sOwn + (tid < nLoc ? tid : DEME_TILE_NB + h0) * RSZ, ((tid < nLoc ? tid : DEME_TILE_NB + h0) >> 3) & a.swz);
         if (h1 < nH)
@@ -735,10 +628,6 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                 sLPos[tid + k * DEME_TILE_T] = (uint16_t)lp[k];
     }
     __syncthreads();
-    TILE_STAMP(2);
-#if DEME_TILE_PRIO || DEME_TILE_PRIO_ROUNDS
-    __builtin_amdgcn_s_setprio(DEME_TILE_PRIO_ROUNDS);
-#endif
 
     // the pulling side of this thread: threads 0 .. NB - 1 take the A runs, NB .. 2 NB - 1 the local-B lists
     const uint32_t po = tid % DEME_TILE_NB;
@@ -751,12 +640,6 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
     const uint32_t nCt = c1 - c0;
     auto refill = [&](const int d, const uint32_t c) __attribute__((always_inline)) {  // stage d takes the round DEME_TILE_DEPTH rounds ahead of contact c
         const uint32_t cd = c + DEME_TILE_DEPTH * DEME_TILE_T;
-#if !DEME_TILE_NOZERO
-        inf[d] = make_uint2(0, 0), hist[d] = make_float4(0, 0, 0, 0), rbase[d] = 0u;
-#pragma unroll
-        for (int k = 0; k < NWU; k++)
-            uwv[d][k] = 0.f;
-#endif
         if (cd < c1) {
             inf[d] = stream_load(a.tInfo + cd);
             if (MODEL == 0)
@@ -769,14 +652,10 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
             rbase[d] = a.rankC[cd - (tid & 63u)];
         }
     };
-    auto round = [&](auto RF, const int d, const uint32_t rlo) __attribute__((always_inline)) {
+    auto round = [&](const int d, const uint32_t rlo) __attribute__((always_inline)) {
             const uint32_t c = c0 + rlo + tid;
             bool crossing = false;
-#if DEME_TILE_NOZERO
             float4 x4, x2;  // (read only where `crossing` was set)
-#else
-            float4 x4 = make_float4(0, 0, 0, 0), x2 = x4;
-#endif
             if (c < c1) {
                 const uint2 ci = inf[d];
                 float4 h = hist[d];
@@ -788,16 +667,6 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                     const float2 a2 = a.conA2[c], b2 = a.conB2[c];
                     force = mk3(a4.x, a4.y, a4.z), tA = mk3(a4.w, a2.x, a2.y), tB = mk3(b4.w, b2.x, b2.y);
                 } else {
-#if DEME_TILE_KI & 8
-                    {
-                        uint2 ci2 = ci;
-                        ki_opaque(ci2.x), ki_opaque(ci2.y);
-                        float4 h2 = h;
-                        f3 f2, u2, w2;
-                        tile_contact<MODEL>(p, T, ci2, A, B, h2, f2, u2, w2);
-                        ki_sink(f2.x + f2.y + f2.z + u2.x + u2.y + u2.z + w2.x + w2.y + w2.z + h2.x + h2.y + h2.z + h2.w);
-                    }
-#endif
                     if (MODEL == 2) {
                         float uw[NWU];
 #pragma unroll
@@ -828,10 +697,8 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                     } else {
                         tile_contact<MODEL>(p, T, ci, A, B, h, force, tA, tB);
                     }
-#if !(DEME_TILE_KI & 16)
                     if (MODEL == 0)
                         stream_store(reinterpret_cast<float4*>(a.wc) + c, h);
-#endif
                 }
                 recA4[tid] = make_float4(force.x, force.y, force.z, tA.x);
                 recA2[tid] = make_float2(tA.y, tA.z);
@@ -846,25 +713,13 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                 const uint64_t m = __ballot(crossing);
                 if (crossing) {
                     const uint32_t k = rbase[d] + (uint32_t)__popcll(m & ((1ull << (tid & 63u)) - 1ull));
-#if !(DEME_TILE_KI & 32)
-#if DEME_REC24
                     float2* const r24 = reinterpret_cast<float2*>(a.rec32) + 3 * (size_t)k;  // (-F.x -F.y) (-F.z tB.x) (tB.y tB.z)
                     stream_store(r24, make_float2(x4.x, x4.y));
                     stream_store(r24 + 1, make_float2(x4.z, x4.w));
                     stream_store(r24 + 2, make_float2(x2.x, x2.y));
-#else
-                    stream_store(a.rec32 + 2 * (size_t)k, x4);
-                    stream_store(a.rec32 + 2 * (size_t)k + 1, x2);
-#endif
-#else
-                    ki_sink(x4.x + x2.x + (float)k);
-#endif
                 }
             }
             
-#if DEME_TILE_UNROLL
-            refill(d, c);
-#else
 #pragma unroll
             for (int q = 0; q + 1 < DEME_TILE_DEPTH; q++) {
                 inf[q] = inf[q + 1], hist[q] = hist[q + 1], rbase[q] = rbase[q + 1];
@@ -872,18 +727,9 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                 for (int k = 0; k < NWU; k++)
                     uwv[q][k] = uwv[q + 1][k];
             }
-            if (decltype(RF)::value)
-                refill(DEME_TILE_DEPTH - 1, c);
-#endif
+            refill(DEME_TILE_DEPTH - 1, c);
 
             __syncthreads();
-#if DEME_TILE_KI & 256  // knock-in: one more barrier per round
-            asm volatile("s_nop 0" ::: "memory");
-            __syncthreads();
-#endif
-#if DEME_TILE_PRIO_PULL
-            __builtin_amdgcn_s_setprio(DEME_TILE_PRIO_PULL);
-#endif
             const uint32_t rhi = rlo + DEME_TILE_T;
             auto pulls = [&]() {
                 if (sideA) {  // my A run's part of this round: positions [plo, min(phi, rhi)); a missing entry reads the zero slot
@@ -891,7 +737,6 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                     while (plo < e) {
                         float4 v4[DEME_TILE_PULLW];
                         float2 v2[DEME_TILE_PULLW];
-#if DEME_TILE_PKPULL
 #pragma unroll
                         for (int k = 0; k < DEME_TILE_PULLW; k++) {
                             const uint32_t i = (plo + k < e) ? plo + k - rlo : (uint32_t)DEME_TILE_T;
@@ -903,17 +748,6 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                             s23 += v2f{v4[k].z, v4[k].w};
                             s45 += v2f{v2[k].x, v2[k].y};
                         }
-#else
-#pragma unroll
-                        for (int k = 0; k < DEME_TILE_PULLW; k++) {
-                            const uint32_t i = min(plo + k, e - 1u) - rlo;
-                            v4[k] = recA4[i], v2[k] = recA2[i];
-                        }
-#pragma unroll
-                        for (int k = 0; k < DEME_TILE_PULLW; k++)
-                            if (plo + k < e)
-                                s01.x += v4[k].x, s01.y += v4[k].y, s23.x += v4[k].z, s23.y += v4[k].w, s45.x += v2[k].x, s45.y += v2[k].y;
-#endif
                         plo = min(plo + (uint32_t)DEME_TILE_PULLW, e);
                     }
                 } else if (sideB) {  // my local-B list's entries that fall into this round: -F and tB of those contacts
@@ -926,7 +760,6 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                             break;
                         float4 v4[DEME_TILE_PULLW], vt[DEME_TILE_PULLW];
                         uint32_t used = 0;
-#if DEME_TILE_PKPULL
 #pragma unroll
                         for (int k = 0; k < DEME_TILE_PULLW; k++) {
                             const bool in = pos[k] < rhi;  // (ascending: the entries of this round come first)
@@ -941,64 +774,17 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
                             s23.y += vt[k].z;
                             s45 += v2f{vt[k].x, vt[k].y};
                         }
-#else
-#pragma unroll
-                        for (int k = 0; k < DEME_TILE_PULLW; k++) {
-                            const uint32_t i = (pos[k] < rhi ? pos[k] : pos[0]) - rlo;
-                            v4[k] = recA4[i], vt[k] = recT[i];
-                        }
-#pragma unroll
-                        for (int k = 0; k < DEME_TILE_PULLW; k++)
-                            if (pos[k] < rhi) {
-                                s01.x -= v4[k].x, s01.y -= v4[k].y, s23.x -= v4[k].z, s23.y += vt[k].z, s45.x += vt[k].x, s45.y += vt[k].y;
-                                used++;
-                            }
-#endif
                         plo += used;
                         if (used < (uint32_t)DEME_TILE_PULLW)
                             break;
                     }
                 }
             };
-#if DEME_TILE_KI & 2
-            {
-                const v2f k01 = s01, k23 = s23, k45 = s45;
-                uint32_t kp = plo;
-                pulls();
-                ki_sink(s01.x + s01.y + s23.x + s23.y + s45.x + s45.y);
-                ki_opaque(kp);
-                s01 = k01, s23 = k23, s45 = k45, plo = kp;
-            }
-#endif
             pulls();
-#if DEME_TILE_PRIO_PULL
-            __builtin_amdgcn_s_setprio(DEME_TILE_PRIO_ROUNDS);
-#endif
             __syncthreads();
-            TILE_STAMP(min(3u + rlo / DEME_TILE_T, 10u));
     };
-#if DEME_TILE_UNROLL
-    // The rounds, DEME_TILE_DEPTH at a time with the stage of the stream registers a round uses fixed at compile time: nothing is
-    // rotated between rounds
-    for (uint32_t rb = 0; rb < nCt; rb += DEME_TILE_DEPTH * DEME_TILE_T) {
-#pragma unroll
-        for (int d = 0; d < DEME_TILE_DEPTH; d++) {
-            const uint32_t rlo = rb + d * DEME_TILE_T;
-            if (rlo >= nCt)  // (uniform over the workgroup)
-                break;
-            round(TileFlag<true>{}, d, rlo);
-        }
-    }
-#else
-#if DEME_TILE_SPLITLOOP
-    if (nCt <= DEME_TILE_DEPTH * DEME_TILE_T) {
-        for (uint32_t rlo = 0; rlo < nCt; rlo += DEME_TILE_T)
-            round(TileFlag<false>{}, 0, rlo);
-    } else
-#endif
     for (uint32_t rlo = 0; rlo < nCt; rlo += DEME_TILE_T)  // stage 0 is the current round; the stages are rotated after it
-        round(TileFlag<true>{}, 0, rlo);
-#endif
+        round(0, rlo);
     // A-side sum + B-side sum, through LDS (the contribution arrays are free now)
     if (sideB) {
         recA4[po] = make_float4(s01.x, s01.y, s23.x, s23.y);
@@ -1008,39 +794,18 @@ __global__ __launch_bounds__(DEME_TILE_T, DEME_TILE_OCC) void k_tile_forces(cons
     if (sideA && po < nLoc) {
         const float4 b4 = recA4[po];
         const float2 b2 = recA2[po];
-#if !(DEME_TILE_KI & 64)
-#if DEME_REC24
         float2* const t24 = reinterpret_cast<float2*>(a.tSum) + 3 * (size_t)(o0 + po);  // (F.x F.y) (F.z t.x) (t.y t.z)
         t24[0] = make_float2(s01.x + b4.x, s01.y + b4.y);
         t24[1] = make_float2(s23.x + b4.z, s23.y + b4.w);
         t24[2] = make_float2(s45.x + b2.x, s45.y + b2.y);
-#else
-        a.tSum[2 * (size_t)(o0 + po)] = make_float4(s01.x + b4.x, s01.y + b4.y, s23.x + b4.z, 0.f);
-        a.tSum[2 * (size_t)(o0 + po) + 1] = make_float4(s23.y + b4.w, s45.x + b2.x, s45.y + b2.y, 0.f);
-#endif
-#else
-        ki_sink(s01.x + b4.x + s01.y + b4.y + s23.x + b4.z + s23.y + b4.w + s45.x + b2.x + s45.y + b2.y);
-#endif
     }
-#if DEME_TILE_STAMPS
-    TILE_STAMP(11);
-    if (a.stamps && tid == 0) {
-        uint32_t hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        a.stamps[(size_t)t * 16u + 12u] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-        a.stamps[(size_t)t * 16u + 13u] = nCt;
-        a.stamps[(size_t)t * 16u + 14u] = nH;
-        a.stamps[(size_t)t * 16u + 15u] = (unsigned long long)clock64() - stampClk0;
-    }
-#endif
 }
 
 // ---- the tiles that do not fit ---------------------------------------------------------------------------------------------------
 // A tile whose foreign owners exceed DEME_TILE_HMAX (a big sphere with hundreds of neighbours, a polydisperse pocket, a numbering
 // that is not spatial), whose contact range exceeds DEME_TILE_CMAX or whose local-B lists exceed DEME_TILE_LMAX is evaluated by this
 // kernel instead -- one workgroup per such tile, the rest of the list stays with k_tile_forces.  Same arithmetic (tile_contact), same
-// outputs (the per-owner sums of the A runs in tSum, 32-byte records for the integrator's gather), but nothing is staged: a contact
+// outputs (the per-owner sums of the A runs in tSum, 24-byte records for the integrator's gather), but nothing is staged: a contact
 // loads its two owner records from memory and converts them itself, the small tables are read where they lie, and EVERY contact
 // writes a B-side record (the builder numbered them: rankC holds a contact's own record number here), also those whose B owner
 // belongs to the tile.  Slower per contact -- it is the exception path -- and exact about the order of the sums like the tile pass.
@@ -1126,15 +891,10 @@ __global__ __launch_bounds__(DEME_TILE_T) void k_tile_forces_big(const DevParams
             recA4[tid] = make_float4(force.x, force.y, force.z, tA.x);
             recA2[tid] = make_float2(tA.y, tA.z);
             const uint32_t k = a.rankC[c];  // (this contact's own record)
-#if DEME_REC24
             float2* const r24 = reinterpret_cast<float2*>(a.rec32) + 3 * (size_t)k;
             stream_store(r24, make_float2(-force.x, -force.y));
             stream_store(r24 + 1, make_float2(-force.z, tB.x));
             stream_store(r24 + 2, make_float2(tB.y, tB.z));
-#else
-            stream_store(a.rec32 + 2 * (size_t)k, make_float4(-force.x, -force.y, -force.z, tB.x));
-            stream_store(a.rec32 + 2 * (size_t)k + 1, make_float4(tB.y, tB.z, 0.f, 0.f));
-#endif
         }
         __syncthreads();
         if (sideA) {
@@ -1159,17 +919,12 @@ __global__ __launch_bounds__(DEME_TILE_T) void k_tile_forces_big(const DevParams
         __syncthreads();
     }
     if (sideA) {
-#if DEME_REC24
         float2* const t24 = reinterpret_cast<float2*>(a.tSum) + 3 * (size_t)(o0 + tid);
         t24[0] = make_float2(s01.x, s01.y), t24[1] = make_float2(s23.x, s23.y), t24[2] = make_float2(s45.x, s45.y);
-#else
-        a.tSum[2 * (size_t)(o0 + tid)] = make_float4(s01.x, s01.y, s23.x, 0.f);
-        a.tSum[2 * (size_t)(o0 + tid) + 1] = make_float4(s23.y, s45.x, s45.y, 0.f);
-#endif
     }
 }
 
-#if !defined(DEME_JIT) && !defined(DEME_TILE_FORCE_ONLY)  // (the run-time compiled copy of this header and deme_tile_p.hip hold the force pass only)
+#ifndef DEME_JIT  // (the run-time compiled copy of this header holds the force pass only)
 // ---- per-detection builders ----------------------------------------------------------------------------------------------------
 // (1) k_contact_owners counts, per tile, the contacts whose B owner lives in another tile (tileRem; deme_kernels.h); an exclusive
 //     scan gives every tile the number of its first record (tileBase).

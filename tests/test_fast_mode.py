@@ -231,7 +231,7 @@ def test_a_tiled_list_serves_the_other_kernels_on_demand(pkg):
     assert np.isfinite(fa).all() and (np.abs(fa).sum(1) > 0).sum() > 300  # (most listed pairs are inside the margin, not touching)
     a.close(), t.close()
     # (b) the mode switch: both contexts switch at the same step of the same list; one of them had its B-sorted form built at the
-    # detection already (DEME_TILE cannot be switched per context, so the twin switches one step earlier and back: its lists exist)
+    # detection already (the tile form cannot be switched off per context, so the twin switches one step earlier and back: its lists exist)
     a, t = fresh(), fresh()
     t.set_arith_mode("exact"), t.set_arith_mode("fast")  # no step in between: state untouched, nothing built yet
     a.set_arith_mode("exact"), t.set_arith_mode("exact")
