@@ -209,6 +209,10 @@ def load_library():
         "deme_set_record_contacts": [_P, C.c_int],
         "deme_download_contact_records": [_P, _P, _P, _P, _P, C.c_size_t],
         "deme_download_sphere_geometry": [_P, _P, _P, _P, _P, C.c_size_t],
+        "deme_change_owner_sizes": [_P, _P, _P, C.c_size_t], "deme_num_components": [_P, C.POINTER(C.c_uint32)],
+        "deme_download_components": [_P, _P, _P, _P, _P, C.c_size_t], "deme_download_sphere_components": [_P, _P, C.c_size_t],
+        "deme_set_template_components": [_P, C.c_uint32], "deme_multi_change_owner_sizes": [_P, _P, _P, C.c_size_t],
+        "deme_multi_download_sphere_components": [_P, _P, C.c_size_t],
         "deme_compile_force_model": [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p],
         "deme_compile_force_model_ex": [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p),
                                         C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p],
@@ -616,6 +620,21 @@ class Multi:
         self._ck(self.lib.deme_multi_add_owner_acc(self.h, int(owner), n, None if a is None else _ptr(a), None if l is None else _ptr(l)),
                  "deme_multi_add_owner_acc")
 
+    def change_owner_sizes(self, gids, factors):
+        """Context.change_owner_sizes by GLOBAL owner id: own clumps and ghost copies on every slab, one table for all slabs;
+        DemeError naming the halo when the grown clumps no longer fit it (build the run again with a wider one)"""
+        ids = np.ascontiguousarray(gids, dtype=np.uint32).ravel()
+        f = np.ascontiguousarray(factors, dtype=np.float32).ravel()
+        if ids.size != f.size:
+            raise DemeError(f"change_owner_sizes: {ids.size} ids but {f.size} factors")
+        self._ck(self.lib.deme_multi_change_owner_sizes(self.h, _ptr(ids), _ptr(f), ids.size), "deme_multi_change_owner_sizes")
+
+    def sphere_components(self, n_spheres):
+        """every sphere's component index by global sphere id"""
+        out = np.zeros(int(n_spheres), np.uint16)
+        self._ck(self.lib.deme_multi_download_sphere_components(self.h, _ptr(out), out.size), "deme_multi_download_sphere_components")
+        return out
+
     def num_contacts(self):
         n = C.c_size_t(0)
         self.lib.deme_multi_num_contacts.argtypes = [_P, C.POINTER(C.c_size_t)]
@@ -1009,6 +1028,36 @@ class Context:
         self._ck(self.lib.deme_download_sphere_geometry(self.h, _ptr(X), _ptr(Y), _ptr(Z), _ptr(R), n),
                  "deme_download_sphere_geometry")
         return X, Y, Z, R
+
+    def change_owner_sizes(self, ids, factors):
+        """resize owners of the running simulation (DEMSolver::ChangeClumpSizes): every sphere of owner ids[i] gets its relative
+        position and radius multiplied by factors[i] in fp32; mass and moment of inertia stay.  The next step detects anew."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        f = np.ascontiguousarray(factors, dtype=np.float32).ravel()
+        if ids.size != f.size:
+            raise DemeError(f"change_owner_sizes: {ids.size} ids but {f.size} factors")
+        self._ck(self.lib.deme_change_owner_sizes(self.h, _ptr(ids), _ptr(f), ids.size), "deme_change_owner_sizes")
+
+    def num_components(self):
+        n = C.c_uint32()
+        self._ck(self.lib.deme_num_components(self.h, C.byref(n)), "deme_num_components")
+        return int(n.value)
+
+    def components(self):
+        """the component table in effect, (n, 4) float32 rows of relx, rely, relz, radius"""
+        n = self.num_components()
+        cols = [np.zeros(n, np.float32) for _ in range(4)]
+        self._ck(self.lib.deme_download_components(self.h, *[_ptr(a) for a in cols], n), "deme_download_components")
+        return np.stack(cols, axis=1)
+
+    def set_template_components(self, n):
+        self._ck(self.lib.deme_set_template_components(self.h, int(n)), "deme_set_template_components")
+
+    def sphere_components(self):
+        """every sphere's component index, by the caller's sphere id"""
+        out = np.zeros(self.n_spheres, np.uint16)
+        self._ck(self.lib.deme_download_sphere_components(self.h, _ptr(out), out.size), "deme_download_sphere_components")
+        return out
 
     def compile_force_model(self, src, wildcard_names=(), prerequisites="", owner_wildcards=(), geo_wildcards=()):
         def arr(names):

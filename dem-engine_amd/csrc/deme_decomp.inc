@@ -1621,3 +1621,108 @@ int deme_multi_slab_counts(deme_multi* m, uint32_t slab, uint32_t counts[6], dou
         range[0] = sl.geo.xLo, range[1] = sl.geo.xHi;
     return counts ? deme_halo_group_slab_counts(g, sl.ctx, counts) : DEME_OK;
 }
+
+// deme_change_owner_sizes on a decomposed run, by GLOBAL owner id: every slab resizes its own clumps and its ghost copies of them
+// (matched by ownerGid).  Migration carries component indices between slabs, so every slab must hold the same table: the keys of
+// all slabs are merged, their uses summed, the table planned once and applied everywhere.  Nothing changes before every check has
+// passed -- the ids, the 16-bit index, and the halo the plan was cut with, which must still hold two reaches of the largest clump.
+int deme_multi_change_owner_sizes(deme_multi* m, const uint32_t* globalIds, const float* factors, size_t n) {
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    std::vector<uint32_t> fb;
+    char msg[256];
+    if (int rc = resize_check(msg, sizeof msg, globalIds, factors, n, m->plan->nOwnersGlobal, fb))
+        return mfail(m, rc, "deme_multi_change_owner_sizes: %s", msg);
+    if (!n)
+        return DEME_OK;
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    std::vector<uint32_t> byGid(m->plan->nOwnersGlobal, 0);
+    for (size_t i = 0; i < n; i++)
+        byGid[globalIds[i]] = fb[i];
+    struct Part {
+        deme_ctx* c;
+        int device;
+    };
+    std::vector<Part> parts;
+    std::map<uint64_t, uint32_t> merged;  // key -> spheres that carry it, over every slab (own clumps and ghost copies)
+    std::vector<uint32_t> usesAll;
+    const deme_ctx* first = nullptr;
+    for (auto* g : m->groups)
+        for (auto& s : g->slabs) {
+            deme_ctx* c = s.ctx;
+            if (hipSetDevice(g->device) != hipSuccess)
+                return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+            if (!first) {
+                first = c;
+                usesAll.assign(c->nComp, 0);
+            } else if (c->nComp != first->nComp || c->nTemplateComps != first->nTemplateComps ||
+                       memcmp(c->hComp.data(), first->hComp.data(), (size_t)c->nComp * sizeof(float4)) != 0) {
+                return mfail(m, DEME_ERR_INVALID, "deme_multi_change_owner_sizes: the slabs' component tables differ");
+            }
+            std::vector<uint32_t> gid(c->nOwnerClumps), ids, bits;
+            if (c->nOwnerClumps && hipMemcpy(gid.data(), s.geo.ownerGid, (size_t)c->nOwnerClumps * 4, hipMemcpyDeviceToHost) != hipSuccess)
+                return mfail(m, DEME_ERR_HIP, "the slab's books could not be read");
+            for (uint32_t i = 0; i < c->nOwnerClumps; i++)  // own clumps [0, nOwn) and ghost copies [nOwn, nOwnerClumps)
+                if (gid[i] < byGid.size() && byGid[gid[i]])
+                    ids.push_back(i), bits.push_back(byGid[gid[i]]);
+            std::vector<uint64_t> keys;
+            std::vector<uint32_t> runs, uses;
+            if (int rc = resize_collect(c, ids.data(), bits.data(), ids.size(), keys, runs, uses))
+                return mfail(m, rc, "%s", c->err.c_str());
+            for (size_t u = 0; u < keys.size(); u++)
+                merged[keys[u]] += runs[u];
+            for (size_t k = 0; k < uses.size(); k++)
+                usesAll[k] += uses[k];
+            parts.push_back({c, g->device});
+        }
+    if (merged.empty() || !first)
+        return DEME_OK;
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> runs;
+    for (auto& kv : merged)  // (std::map: sorted, as the apply pass's binary search wants them)
+        keys.push_back(kv.first), runs.push_back(kv.second);
+    ResizePlan pl;
+    resize_plan(first->hComp, first->nTemplateComps, keys, runs, usesAll, pl);
+    if (pl.table.size() > 65535)
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_change_owner_sizes: the resized scene needs %zu clump components; at most 65535 are "
+                     "supported", pl.table.size());
+    if (2.0 * pl.reach > m->plan->halo)
+        return mfail(m, DEME_ERR_HALO, "deme_multi_change_owner_sizes: the largest clump would reach %g m from its centre, but the slabs were "
+                     "cut with a halo of %g m, which must hold two such reaches; build the run again with a halo of at least %g m",
+                     pl.reach, m->plan->halo, 2.0 * pl.reach);
+    for (auto& pt : parts) {
+        if (hipSetDevice(pt.device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", pt.device);
+        if (int rc = resize_apply(pt.c, keys, pl))
+            return mfail(m, rc, "%s", pt.c->err.c_str());
+    }
+    m->rowsValid = false;
+    return DEME_OK;
+}
+
+// every sphere's component index by GLOBAL sphere id (a ghost copy holds what its own slab holds)
+int deme_multi_download_sphere_components(deme_multi* m, uint16_t* comp, size_t cap) {
+    if (!m || !m->plan || !comp)
+        return DEME_ERR_INVALID;
+    if (cap < m->plan->nSpheresGlobal)
+        return mfail(m, DEME_ERR_INVALID, "buffer too small: need %u", m->plan->nSpheresGlobal);
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    for (auto* g : m->groups)
+        for (auto& s : g->slabs) {
+            deme_ctx* c = s.ctx;
+            if (hipSetDevice(g->device) != hipSuccess)
+                return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+            std::vector<uint32_t> gid(c->nSpheres);
+            std::vector<uint16_t> loc(c->nSpheres);
+            if (c->nSpheres && hipMemcpy(gid.data(), s.geo.sphereGid, (size_t)c->nSpheres * 4, hipMemcpyDeviceToHost) != hipSuccess)
+                return mfail(m, DEME_ERR_HIP, "the slab's books could not be read");
+            if (int rc = deme_download_sphere_components(c, loc.data(), loc.size()))
+                return mfail(m, rc, "%s", c->err.c_str());
+            for (uint32_t i = 0; i < c->nSpheres; i++)
+                if (gid[i] < m->plan->nSpheresGlobal)
+                    comp[gid[i]] = loc[i];
+        }
+    return DEME_OK;
+}

@@ -46,6 +46,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_tile_step.h"
 #include "deme_migrate.h"
 #include "deme_mesh_kernels.h"
+#include "deme_resize.h"
 
 using namespace deme_dev;
 
@@ -81,6 +82,11 @@ struct deme_ctx {
     // model
     DevBuf owners, spheres, acc, comp, massProps, anal, matPair, E, nu, CoR, mu, Crr, famMasks, famExtra, famFlags;
     std::vector<uint8_t> hObjType;  // host copy for contact-type decoding on download
+    // the component table as the device holds it (deme_change_owner_sizes derives entries from it); the first nTemplateComps
+    // entries are the uploaded scene's and always stay, the others are derived by resizes and dropped when no sphere uses them
+    std::vector<float4> hComp;
+    uint32_t nTemplateComps = 0;
+    DevBuf rsMark, rsKeys[2], rsRuns, rsUKeys, rsIdx, rsOldR, rsUses, rsRemap;  // resize scratch (deme_resize.h), allocated by the first resize
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
     DevBuf geo, binLo, binN, counts, offsets, incKeys[2], incVals[2], keysRaw, keysMid, keysSorted[2], mapping, wc[2], ctr, segCtr,
@@ -1543,7 +1549,8 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->binLo, &c->binN, &c->counts, &c->offsets, &c->incKeys[0], &c->incKeys[1], &c->incVals[0],
                      &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->mapping, &c->wc[0],
                      &c->wc[1], &c->ctr, &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3],
-                     &c->stage, &c->sharedIds, &c->sharedBuf, &c->keysMid, &c->ownersSnap};
+                     &c->stage, &c->sharedIds, &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1],
+                     &c->rsRuns, &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -1821,6 +1828,8 @@ int deme_upload_scene(deme_ctx* c, const DemeScene* s) {
         hm[i] = make_float4(s->MassProperties[i], s->moiX[i], s->moiY[i], s->moiZ[i]);
     if (int rc = upload(c, c->comp, hc.data(), hc.size()))
         return rc;
+    c->hComp = hc;
+    c->nTemplateComps = s->nComp;
     if (int rc = upload(c, c->massProps, hm.data(), hm.size()))
         return rc;
     std::vector<AnalObj> ha(s->nAnal);
@@ -4216,4 +4225,240 @@ int deme_halo_unpack(deme_ctx* c, const uint32_t* d_ids, uint32_t n, const void*
 }  // extern "C"
 
 // (templates inside: after the extern "C" block; its entry points take C linkage from their declarations in deme_hip.h)
+// ---- run-time resizing of clumps (deme_resize.h) ------------------------------------------------------------------------------
+namespace {
+struct CompBits {  // a component's bit pattern: derived entries are shared by every sphere whose geometry is the same
+    uint32_t w[4];
+    bool operator<(const CompBits& o) const { return std::lexicographical_compare(w, w + 4, o.w, o.w + 4); }
+};
+CompBits comp_bits(const float4& v) {
+    CompBits b;
+    memcpy(&b.w[0], &v.x, 4), memcpy(&b.w[1], &v.y, 4), memcpy(&b.w[2], &v.z, 4), memcpy(&b.w[3], &v.w, 4);
+    return b;
+}
+}  // namespace
+
+// the checks every request passes before anything changes (the reference writes in place and races on a repeated id); fb: the
+// factors' bits (a positive finite float has non-zero bits: 0 marks an owner that is not resized)
+static int resize_check(char* msg, size_t cap, const uint32_t* ids, const float* factors, size_t n, uint32_t nOwners, std::vector<uint32_t>& fb) {
+    if (n && (!ids || !factors))
+        return snprintf(msg, cap, "null id or factor array"), DEME_ERR_INVALID;
+    std::vector<uint8_t> seen(nOwners, 0);
+    fb.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t o = ids[i];
+        const float f = factors[i];
+        if (o >= nOwners)
+            return snprintf(msg, cap, "owner id %u is out of range (%u owners)", o, nOwners), DEME_ERR_INVALID;
+        if (seen[o])
+            return snprintf(msg, cap, "owner id %u is given twice", o), DEME_ERR_INVALID;
+        if (!std::isfinite(f) || !(f > 0.f))
+            return snprintf(msg, cap, "the factor of owner %u is %g; factors must be finite and > 0", o, (double)f), DEME_ERR_INVALID;
+        seen[o] = 1;
+        memcpy(&fb[i], &f, 4);
+    }
+    return DEME_OK;
+}
+
+// phase 1 (device): mark the owners (ids in this context's caller numbering), emit the keys of their spheres, count every
+// component's uses; the distinct keys, how many spheres carry each, and the use counts come back to the host
+static int resize_collect(deme_ctx* c, const uint32_t* ids, const uint32_t* fb, size_t n, std::vector<uint64_t>& keys,
+                          std::vector<uint32_t>& runs, std::vector<uint32_t>& uses) {
+    const uint32_t nS = c->nSpheres, nC = c->nComp;
+    keys.clear(), runs.clear(), uses.assign(nC, 0);
+    if (ensure(c, c->rsMark, (size_t)c->nOwners * 4 + 4) || ensure(c, c->rsKeys[0], (size_t)nS * 8 + 8) ||
+        ensure(c, c->rsKeys[1], (size_t)nS * 8 + 8) || ensure(c, c->rsRuns, (size_t)nS * 4 + 16) || ensure(c, c->rsUses, (size_t)nC * 4 + 4) ||
+        ensure(c, c->stage, n * 8 + 8))
+        return c->lastStatus;
+    uint32_t* dCnt = c->rsRuns.as<uint32_t>() + nS;  // [0]: keys emitted, [1]: distinct keys
+    HIPCK(hipMemsetAsync(c->rsMark.p, 0, (size_t)c->nOwners * 4, c->stream));
+    HIPCK(hipMemsetAsync(dCnt, 0, 8, c->stream));
+    HIPCK(hipMemsetAsync(c->rsUses.p, 0, (size_t)nC * 4, c->stream));
+    if (n) {
+        uint32_t* dIds = c->stage.as<uint32_t>();
+        uint32_t* dBits = dIds + n;
+        HIPCK(hipMemcpyAsync(dIds, ids, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpyAsync(dBits, fb, n * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_resize_mark, dim3(grid_for(n)), dim3(256), 0, c->stream, (uint32_t)n, dIds, dBits, c->rsMark.as<uint32_t>());
+    }
+    if (nS) {
+        hipLaunchKernelGGL(k_resize_keys, dim3(grid_for(nS)), dim3(256), 0, c->stream, nS, c->spheres.as<SphereRec>(), c->dp.o2e,
+                           c->rsMark.as<uint32_t>(), c->rsKeys[0].as<uint64_t>(), dCnt);
+        hipLaunchKernelGGL(k_resize_uses, dim3(grid_for(nS)), dim3(256), 0, c->stream, nS, c->spheres.as<SphereRec>(), c->rsUses.as<uint32_t>());
+    }
+    uint32_t nK = 0;
+    HIPCK(hipMemcpyAsync(&nK, dCnt, 4, hipMemcpyDeviceToHost, c->stream));
+    if (nC)
+        HIPCK(hipMemcpyAsync(uses.data(), c->rsUses.p, (size_t)nC * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (!nK)
+        return DEME_OK;
+    uint64_t* kIn = c->rsKeys[0].as<uint64_t>();
+    uint64_t* kSorted = c->rsKeys[1].as<uint64_t>();
+    uint32_t* runLen = c->rsRuns.as<uint32_t>();
+    // (a key holds 48 bits: the 16-bit component index above the 32 factor bits)
+    size_t need = 0, need2 = 0;
+    HIPCK(rocprim::radix_sort_keys(nullptr, need, kIn, kSorted, (size_t)nK, 0, 48, c->stream));
+    HIPCK(rocprim::run_length_encode(nullptr, need2, kSorted, (size_t)nK, kIn, runLen, dCnt + 1, c->stream));
+    if (int rc = ensure(c, c->sortTmp, std::max(need, need2)))
+        return rc;
+    need = c->sortTmp.bytes;
+    HIPCK(rocprim::radix_sort_keys(c->sortTmp.p, need, kIn, kSorted, (size_t)nK, 0, 48, c->stream));
+    need2 = c->sortTmp.bytes;
+    HIPCK(rocprim::run_length_encode(c->sortTmp.p, need2, kSorted, (size_t)nK, kIn, runLen, dCnt + 1, c->stream));
+    uint32_t nU = 0;
+    HIPCK(hipMemcpyAsync(&nU, dCnt + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    keys.resize(nU), runs.resize(nU);
+    HIPCK(hipMemcpyAsync(keys.data(), kIn, (size_t)nU * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipMemcpyAsync(runs.data(), runLen, (size_t)nU * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+
+// phase 2 (host): the new table -- the uploaded entries, the derived entries some sphere still uses, then the new geometry, each
+// distinct bit pattern once -- and where every old entry and every key goes.  A decomposed run plans once, from the union of its
+// slabs' keys and the sum of their uses, so that every slab holds the same table (migration carries component indices).
+struct ResizePlan {
+    std::vector<float4> table;
+    std::vector<uint32_t> remap, keyIdx;
+    std::vector<float> keyOldR;
+    double reach = 0;  // largest |relPos| + radius of an entry in use: the extent of the largest clump after the change
+};
+static void resize_plan(const std::vector<float4>& hComp, uint32_t nTemplate, const std::vector<uint64_t>& keys, const std::vector<uint32_t>& runs,
+                        std::vector<uint32_t> uses, ResizePlan& pl) {
+    const uint32_t nC = (uint32_t)hComp.size(), nU = (uint32_t)keys.size();
+    for (uint32_t u = 0; u < nU; u++)
+        uses[(uint32_t)(keys[u] >> 32)] -= runs[u];
+    std::map<CompBits, uint32_t> where;
+    pl.table.clear();
+    auto place = [&](const float4& v) {
+        auto it = where.emplace(comp_bits(v), (uint32_t)pl.table.size());
+        if (it.second)
+            pl.table.push_back(v);
+        return it.first->second;
+    };
+    auto reach = [&](const float4& v) {
+        pl.reach = std::max(pl.reach, std::sqrt((double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z) + (double)v.w);
+    };
+    const uint32_t nT = std::min(nTemplate, nC);
+    pl.remap.assign(nC, 0), pl.keyIdx.assign(nU, 0), pl.keyOldR.assign(nU, 0.f), pl.reach = 0;
+    for (uint32_t i = 0; i < nT; i++) {  // (kept whatever their bits: UpdateClumps appends clumps that refer to them by index)
+        where.emplace(comp_bits(hComp[i]), i);
+        pl.table.push_back(hComp[i]);
+        pl.remap[i] = i;
+        if (uses[i])
+            reach(hComp[i]);
+    }
+    for (uint32_t i = nT; i < nC; i++)
+        if (uses[i]) {
+            pl.remap[i] = place(hComp[i]);
+            reach(hComp[i]);
+        }
+    for (uint32_t u = 0; u < nU; u++) {
+        const float4 b = hComp[(uint32_t)(keys[u] >> 32)];
+        pl.keyOldR[u] = b.w;
+        float f;
+        const uint32_t bits = (uint32_t)keys[u];
+        memcpy(&f, &bits, 4);
+        const float4 v = make_float4(b.x * f, b.y * f, b.z * f, b.w * f);  // one fp32 multiply each (modifyComponents)
+        pl.keyIdx[u] = place(v);
+        reach(v);
+    }
+}
+
+// phase 3 (device): the scratch of the apply pass first, the table last -- a failed allocation leaves the context as it was
+static int resize_apply(deme_ctx* c, const std::vector<uint64_t>& keys, const ResizePlan& pl) {
+    const uint32_t nS = c->nSpheres, nU = (uint32_t)keys.size();
+    if (upload(c, c->rsUKeys, keys.data(), keys.size()) || upload(c, c->rsIdx, pl.keyIdx.data(), pl.keyIdx.size()) ||
+        upload(c, c->rsOldR, pl.keyOldR.data(), pl.keyOldR.size()) || upload(c, c->rsRemap, pl.remap.data(), pl.remap.size()))
+        return c->lastStatus;
+    if (int rc = upload(c, c->comp, pl.table.data(), pl.table.size()))
+        return rc;
+    c->nComp = (uint32_t)pl.table.size();
+    c->hComp = pl.table;
+    refresh_dev_params(c);  // (the table may have moved)
+    if (nS) {
+        GeoRec* geo = (c->haveList && !c->geoStale && c->geo.bytes >= (size_t)nS * sizeof(GeoRec)) ? c->geo.as<GeoRec>() : nullptr;
+        hipLaunchKernelGGL(k_resize_apply, dim3(grid_for(nS)), dim3(256), 0, c->stream, nS, c->spheres.as<SphereRec>(), c->dp.o2e,
+                           c->rsMark.as<uint32_t>(), c->rsUKeys.as<uint64_t>(), nU, c->rsIdx.as<uint32_t>(), c->rsOldR.as<float>(),
+                           c->rsRemap.as<uint32_t>(), c->comp.as<float4>(), geo);
+    }
+    HIPCK(hipStreamSynchronize(c->stream));
+    // a critical change (the reference's announceCritical): the next step detects with the new sizes and fresh margins, the
+    // history follows through the normal map; an asynchronous detection does not start from a stale list (async_detection_can_start)
+    c->listStale = true;
+    c->fusedPrevValid = false;
+    return DEME_OK;
+}
+
+int deme_change_owner_sizes(deme_ctx* c, const uint32_t* ownerIds, const float* factors, size_t n) {
+    if (int rc = check_ready(c))
+        return rc;
+    std::vector<uint32_t> fb;
+    char msg[256];
+    if (int rc = resize_check(msg, sizeof msg, ownerIds, factors, n, c->nOwners, fb))
+        return fail(c, rc, "deme_change_owner_sizes: %s", msg);
+    if (!n || !c->nSpheres)
+        return DEME_OK;
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> runs, uses;
+    if (int rc = resize_collect(c, ownerIds, fb.data(), n, keys, runs, uses))
+        return rc;
+    if (keys.empty())  // only owners without spheres (analytical objects, meshes): nothing to do, as in the reference
+        return DEME_OK;
+    ResizePlan pl;
+    resize_plan(c->hComp, c->nTemplateComps, keys, runs, uses, pl);
+    if (pl.table.size() > 65535)
+        return fail(c, DEME_ERR_INVALID, "deme_change_owner_sizes: the resized scene needs %zu clump components; at most 65535 are supported "
+                    "(fewer distinct factors keep the table small)", pl.table.size());
+    return resize_apply(c, keys, pl);
+}
+
+int deme_set_template_components(deme_ctx* c, uint32_t n) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (n > c->nComp)
+        return fail(c, DEME_ERR_INVALID, "deme_set_template_components: %u entries but the table holds %u", n, c->nComp);
+    c->nTemplateComps = n;
+    return DEME_OK;
+}
+
+int deme_num_components(const deme_ctx* c, uint32_t* n) {
+    if (!c || !n)
+        return DEME_ERR_INVALID;
+    *n = c->nComp;
+    return DEME_OK;
+}
+
+int deme_download_components(deme_ctx* c, float* relX, float* relY, float* relZ, float* radius, size_t cap) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (cap < c->nComp)
+        return fail(c, DEME_ERR_INVALID, "buffer too small: need %u", c->nComp);
+    for (uint32_t i = 0; i < c->nComp; i++) {
+        const float4 v = c->hComp[i];
+        if (relX) relX[i] = v.x;
+        if (relY) relY[i] = v.y;
+        if (relZ) relZ[i] = v.z;
+        if (radius) radius[i] = v.w;
+    }
+    return DEME_OK;
+}
+
+int deme_download_sphere_components(deme_ctx* c, uint16_t* comp, size_t cap) {
+    if (int rc = check_ready(c))
+        return rc;
+    const size_t n = c->nSpheres;
+    if (cap < n || (n && !comp))
+        return fail(c, DEME_ERR_INVALID, "buffer too small: need %zu", n);
+    std::vector<SphereRec> h(n);
+    if (n)
+        HIPCK(hipMemcpyAsync(h.data(), c->spheres.p, n * sizeof(SphereRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n; k++)
+        comp[order_sphere_out(c, (uint32_t)k)] = h[k].comp;
+    return DEME_OK;
+}
+
 #include "deme_decomp.inc"

@@ -1115,6 +1115,45 @@ class DEMSolver {
             UpdateClumps();  // (nothing appended: the re-upload of the same batches with the owners' current state)
     }
     void SetSlabReplanInterval(unsigned int steps) { m_replan_every = steps; }
+    /// ChangeClumpSizes (API.h:1047): every sphere of owner IDs[i] gets its relative position and radius multiplied by factors[i]
+    /// (fp32, compounding over calls); mass and moment of inertia stay, as in the reference.  Owners without spheres are left
+    /// alone.  The next step detects contacts with the new sizes.  Unlike the reference, an id out of range or given twice, a
+    /// factor that is not finite or <= 0 and arrays of different lengths are refused with nothing changed; the resized geometry
+    /// is kept through UpdateClumps and ResortClumps.
+    void ChangeClumpSizes(const std::vector<bodyID_t>& IDs, const std::vector<float>& factors) {
+        if (!m_initialized)
+            throw std::runtime_error(
+                "ChangeClumpSizes operates on device-side arrays directly, so it requires the system to be initialized first.");
+        if (IDs.size() != factors.size())
+            throw std::runtime_error("ChangeClumpSizes: " + std::to_string(IDs.size()) + " IDs but " + std::to_string(factors.size()) +
+                                     " factors");
+        std::vector<uint32_t> ids(IDs.begin(), IDs.end());
+        if (m_multi) {
+            int rc = deme_multi_change_owner_sizes(m_multi, ids.data(), factors.data(), ids.size());
+            if (rc == DEME_ERR_HALO) {
+                // the grown clumps outreach the ghost layer the slabs were cut with: cut them again (the current geometry carried
+                // over by UpdateClumps) with a halo of four reaches of the largest grown clump, as an automatic halo is sized
+                m_slab_halo = std::max(m_slab_halo, (float)(4.0 * grown_reach(ids, factors)));
+                UpdateClumps();
+                rc = deme_multi_change_owner_sizes(m_multi, ids.data(), factors.data(), ids.size());
+            }
+            mcheck(rc);
+        } else {
+            check(deme_change_owner_sizes(m_ctx, ids.data(), factors.data(), ids.size()));
+        }
+        // the shell's copy of the geometry (WriteSphereFile, scene re-uploads) is the engine's table from now on (every slab of a
+        // decomposed run holds the same one)
+        deme_ctx* c = diag_ctx();
+        uint32_t n = 0;
+        check(deme_num_components(c, &n));
+        m_keep.Radii.resize(n), m_keep.rx.resize(n), m_keep.ry.resize(n), m_keep.rz.resize(n);
+        check(deme_download_components(c, m_keep.rx.data(), m_keep.ry.data(), m_keep.rz.data(), m_keep.Radii.data(), n));
+        if (m_multi)
+            mcheck(deme_multi_download_sphere_components(m_multi, m_keep.sphComp.data(), m_keep.sphComp.size()));
+        else
+            check(deme_download_sphere_components(m_ctx, m_keep.sphComp.data(), m_keep.sphComp.size()));
+        m_resized = true;
+    }
     /// Restore spatial order in a running simulation (no reference equivalent: its owner ids never change).  The clumps of every
     /// batch are renumbered along a Z-order curve of their current positions; state, contact list, contact history and
     /// persistent marks follow.  Mixing destroys the locality the load order had and the engine's gathers slow down with it
@@ -1721,6 +1760,66 @@ class DEMSolver {
     size_t m_reupload_n = 0;
     std::function<size_t(size_t, size_t)> m_reupload_dst;
     float m_slab_halo = 0.f;
+    bool m_resized = false;  // ChangeClumpSizes was called: m_keep holds geometry the templates do not
+    // largest |relPos| + radius of a clump sphere once owners ids[i] are grown by factors[i] (the engine's fp32 products)
+    double grown_reach(const std::vector<uint32_t>& ids, const std::vector<float>& factors) const {
+        std::unordered_map<uint32_t, float> f;
+        for (size_t i = 0; i < ids.size(); i++)
+            f[ids[i]] = factors[i];
+        double reach = 0;
+        for (size_t i = 0; i < m_keep.sphOwner.size(); i++) {
+            const uint16_t cp = m_keep.sphComp[i];
+            auto it = f.find(m_keep.sphOwner[i]);
+            const float k = it == f.end() ? 1.f : it->second;
+            const double x = m_keep.rx[cp] * k, y = m_keep.ry[cp] * k, z = m_keep.rz[cp] * k;
+            reach = std::max(reach, std::sqrt(x * x + y * y + z * z) + (double)(m_keep.Radii[cp] * k));
+        }
+        return reach;
+    }
+    // (scene re-upload after ChangeClumpSizes) every re-uploaded clump keeps the geometry its spheres had: entries of the new table
+    // for the spheres whose geometry the templates no longer give, shared by equal bit patterns
+    void carry_resized_geometry(const std::vector<uint32_t>& sphOwner, std::vector<uint16_t>& sphComp, std::vector<float>& Radii,
+                                std::vector<float>& rx, std::vector<float>& ry, std::vector<float>& rz, size_t nC, size_t nO) {
+        if (!m_resized || !m_reupload_dst)
+            return;
+        auto starts = [](const std::vector<uint32_t>& owner, size_t n) {
+            std::vector<size_t> st(n + 1, owner.size());
+            for (size_t i = owner.size(); i-- > 0;)
+                if (owner[i] < n)
+                    st[owner[i]] = i;
+            for (size_t o = n; o-- > 0;)  // (owners without spheres start where the next one does)
+                if (st[o] > st[o + 1])
+                    st[o] = st[o + 1];
+            return st;
+        };
+        const std::vector<uint32_t>& oldOwner = m_keep.sphOwner;
+        const std::vector<size_t> so = starts(oldOwner, m_reupload_n), sn = starts(sphOwner, nO);
+        auto bits = [](float a, float b, float c, float d) {
+            std::array<uint32_t, 4> k;
+            memcpy(&k[0], &a, 4), memcpy(&k[1], &b, 4), memcpy(&k[2], &c, 4), memcpy(&k[3], &d, 4);
+            return k;
+        };
+        std::map<std::array<uint32_t, 4>, uint16_t> where;
+        for (size_t i = 0; i < Radii.size(); i++)
+            where.emplace(bits(rx[i], ry[i], rz[i], Radii[i]), (uint16_t)std::min<size_t>(i, 65535));
+        for (size_t o = 0; o < m_reupload_n; o++) {
+            const size_t d = m_reupload_dst(o, nC);
+            if (d >= nO || so[o + 1] - so[o] != sn[d + 1] - sn[d])
+                continue;
+            for (size_t k = 0; k < so[o + 1] - so[o]; k++) {
+                const uint16_t oc = m_keep.sphComp[so[o] + k];
+                const auto key = bits(m_keep.rx[oc], m_keep.ry[oc], m_keep.rz[oc], m_keep.Radii[oc]);
+                auto it = where.find(key);
+                if (it == where.end()) {
+                    if (Radii.size() >= 65535)
+                        throw std::runtime_error("more than 65535 clump components");
+                    it = where.emplace(key, (uint16_t)Radii.size()).first;
+                    rx.push_back(m_keep.rx[oc]), ry.push_back(m_keep.ry[oc]), rz.push_back(m_keep.rz[oc]), Radii.push_back(m_keep.Radii[oc]);
+                }
+                sphComp[sn[d] + k] = it->second;
+            }
+        }
+    }
 
     void open_devices(const std::vector<int>& ids) {
         int visible = 0;
@@ -2671,6 +2770,8 @@ class DEMSolver {
         p.errOutBinSphNum = m_max_sph_in_bin;
         p.errOutVel = m_err_vel;
 
+        const uint32_t nTemplateComps = (uint32_t)Radii.size();  // (the derived entries carried over are not the scene's own)
+        carry_resized_geometry(sphOwner, sphComp, Radii, rx, ry, rz, nC, nO);
         if (m_reupload_state) {
             const DemeOwnerState& st = *m_reupload_state;
             for (size_t o = 0; o < m_reupload_n; o++) {
@@ -2736,6 +2837,8 @@ class DEMSolver {
             check(deme_set_params(m_ctx, &p));
             check(deme_upload_scene(m_ctx, &s));
         }
+        if (nTemplateComps != Radii.size())
+            each_ctx([&](deme_ctx* c) { return deme_set_template_components(c, nTemplateComps); });
         volumes.resize(mass.size(), 0.f);  // analytical / mesh owners: unused, like the reference (dT.cpp:607-618)
         if (std::any_of(volumes.begin(), volumes.end(), [](float v) { return v != 0.f; }))
             each_ctx([&](deme_ctx* c) { return deme_upload_volumes(c, volumes.data(), volumes.size()); });
@@ -2953,6 +3056,14 @@ class DEMTracker {
         for (size_t i = 0; i < m_n; i++)
             out[i] = Pos(i);
         return out;
+    }
+    /// ChangeClumpSizes with ids counted from this tracker's first owner (AuxClasses.cpp:674-679)
+    void ChangeClumpSizes(const std::vector<bodyID_t>& IDs, const std::vector<float>& factors) {
+        std::vector<bodyID_t> ids(IDs);
+        const size_t first = m_sys->tracker_first_owner(m_kind, m_index);
+        for (auto& x : ids)
+            x += (bodyID_t)first;
+        m_sys->ChangeClumpSizes(ids, factors);
     }
     void SetPos(float3 pos, size_t offset = 0) { m_sys->set_owner(GetOwnerID(offset), &pos, nullptr, nullptr, nullptr); }
     void SetVel(float3 vel, size_t offset = 0) { m_sys->set_owner(GetOwnerID(offset), nullptr, &vel, nullptr, nullptr); }

@@ -64,6 +64,7 @@ extern "C" {
 #define DEME_ERR_VELOCITY 5     /* reference: errOutVel, kT.cpp:136-149 */
 #define DEME_ERR_COMPILE 6
 #define DEME_ERR_PEER 7 /* a collective call gave up because ANOTHER rank of the halo group reported an error (its own message says which) */
+#define DEME_ERR_HALO 8 /* deme_multi_change_owner_sizes: the grown clumps would no longer fit the halo the slabs were cut with */
 
 /* ---- parameter block: replaces deme::DEMSimParams (DEM/Defines.h:194-265) - */
 typedef struct DemeParams {
@@ -300,6 +301,23 @@ int deme_set_record_contacts(deme_ctx* ctx, int enable);
 int deme_download_contact_records(deme_ctx* ctx, float* force, float* torqueOnly, float* cpA, float* cpB, size_t cap);
 /* per-sphere world position (LBF-shifted frame, as kT sees it) and inflated radius */
 int deme_download_sphere_geometry(deme_ctx* ctx, double* X, double* Y, double* Z, float* R, size_t cap);
+
+/* Resize clumps of a running simulation (DEMSolver::ChangeClumpSizes, API.h:1047): every sphere of owner ownerIds[i] (the caller's
+ * numbering) gets relPos *= factors[i] and radius *= factors[i], one fp32 multiply of the current value each; repeated calls
+ * compound.  Mass and moment of inertia are not changed (nor are they in the reference); owners without spheres are left alone.
+ * The next step detects contacts with the new sizes; the history of pairs that stay in contact is kept.  Refused, with nothing
+ * changed: an id out of range or given twice, a factor that is not finite or <= 0, a table of more than 65535 components.
+ * Resized spheres get derived entries of the component table (shared by equal geometry); the first entries, the uploaded scene's,
+ * always stay, derived entries no sphere uses any more are dropped. */
+int deme_change_owner_sizes(deme_ctx* ctx, const uint32_t* ownerIds, const float* factors, size_t n);
+int deme_num_components(const deme_ctx* ctx, uint32_t* n);
+/* the component table in effect (deme_num_components entries; any pointer may be NULL) and every sphere's index into it, by the
+ * caller's sphere id: what a scene re-upload needs to carry resized geometry over */
+int deme_download_components(deme_ctx* ctx, float* relX, float* relY, float* relZ, float* radius, size_t cap);
+int deme_download_sphere_components(deme_ctx* ctx, uint16_t* comp, size_t cap);
+/* how many leading entries of the table are the scene's own (kept by every resize; the rest are derived and dropped when unused).
+ * deme_upload_scene counts the whole uploaded table; a re-upload that carries derived entries over names the true count here. */
+int deme_set_template_components(deme_ctx* ctx, uint32_t n);
 
 /* Force-model hook (DEMForceModel::DefineCustomModel, AuxClasses.h:422-485;
  * equipForceModel APIPrivate.cpp:1381-1574): splice a user statement block into
@@ -597,6 +615,11 @@ int deme_multi_reset(deme_multi* m);
  * context (A, then class, then B).  Per-contact wildcards and recorded forces / contact points follow in the same order; where a slab
  * held a pair the other way round, its B -> A vector wildcards (the flipMask given at build) and its recorded force change sign and
  * its two contact points swap.  The list is rebuilt after every step / state upload. */
+/* deme_change_owner_sizes by GLOBAL owner id: every slab resizes its own clumps and its ghost copies; one table, planned from all
+ * slabs' keys, goes to every slab.  DEME_ERR_HALO, with nothing changed, when the largest clump would reach more than half the
+ * halo the plan was cut with (build the run again with a wider halo). */
+int deme_multi_change_owner_sizes(deme_multi* m, const uint32_t* globalIds, const float* factors, size_t n);
+int deme_multi_download_sphere_components(deme_multi* m, uint16_t* comp, size_t cap); /* by global sphere id */
 int deme_multi_num_contacts(deme_multi* m, size_t* n);
 int deme_multi_download_contacts(deme_multi* m, uint32_t* idA, uint32_t* idB, uint8_t* type, size_t cap);
 int deme_multi_download_contact_wildcard(deme_multi* m, uint32_t w, float* out, size_t cap);
