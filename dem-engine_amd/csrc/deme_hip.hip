@@ -61,6 +61,43 @@ struct DevBuf {
     }
 };
 
+// One built contact list: what a detection's part 2 (detect_part2, build_legacy_lists) writes and the stepping kernels read, with
+// the host scalars that describe it.  A context holds two (deme_ctx::list): an asynchronous detection builds one while the steps
+// in flight read the other, and the pair is swapped by flipping an index.  Everything else a list refers to is shared by both
+// and stays on the context -- see the note at deme_ctx::list.
+struct ContactList {
+    // per contact (size_list_per_contact)
+    DevBuf mapping, ownerA, ownerB[2], bIdx[2], info, tInfo, rIdx, lPos, remVal, rankC, remKey[2], cDefer, blockMode, smFlag, smList;
+    // per owner / per tile (size_list_per_owner)
+    DevBuf aStart, bStart, heavy, fixedFlag, heavyList, rangeCtr, hList, hCount, tileMode, tileOrg, rStart, lOff, lCount, tileRem, tileBase,
+        tileBig, bigList;
+    uint64_t nListed = 0;      // contacts the owner arrays (ownerA, ownerB[0], info ...) were built for
+    int listKeys = 0;          // ... and the key buffer (deme_ctx::keysSorted) they were built from
+    bool legacyLists = false;  // the B-sorted list of the round-2 kernels exists (built on demand when the list has tile structures)
+    bool tileActive = false;   // the list has tile structures (built-in model, fast mode, every halo fits)
+    bool fusedList = false;    // the list has the incoming structures of the one-kernel step (decided per detection)
+    bool fusedChecked = false;  // ... and the device has been asked whether every closed tile fits
+    // the heavy-owner counts of a tiled list are fetched without stopping the stream: the copy lands in pinned memory
+    // (deme_ctx::hrPinned), the first reader (launch_reduce_heavy, one force launch later) waits for its event
+    bool hrPending = false, heavyOverflow = false;
+    uint32_t nHeavy = 0, nHeavyFree = 0, nSA = 0, nSM = 0;
+    uint32_t nBigTiles = 0, tileMaxHalo = 0, tileMaxList = 0, tileMaxHaloIn = 0;
+
+    // nothing is built: whatever changes the owners, their slots or the keys under a list calls this, and the detection that
+    // always follows describes the list again
+    void invalidate() {
+        nListed = 0, listKeys = 0;
+        legacyLists = tileActive = fusedList = fusedChecked = hrPending = heavyOverflow = false;
+        nHeavy = nHeavyFree = nSA = nSM = 0;
+        nBigTiles = tileMaxHalo = tileMaxList = tileMaxHaloIn = 0;
+    }
+    std::array<DevBuf*, 35> buffers() {
+        return {&mapping, &ownerA, &ownerB[0], &ownerB[1], &bIdx[0], &bIdx[1], &info, &tInfo, &rIdx, &lPos, &remVal, &rankC, &remKey[0],
+                &remKey[1], &cDefer, &blockMode, &smFlag, &smList, &aStart, &bStart, &heavy, &fixedFlag, &heavyList, &rangeCtr, &hList,
+                &hCount, &tileMode, &tileOrg, &rStart, &lOff, &lCount, &tileRem, &tileBase, &tileBig, &bigList};
+    }
+};
+
 struct TimerSlot {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double total_ms = 0;
@@ -89,33 +126,32 @@ struct deme_ctx {
     DevBuf rsMark, rsKeys[2], rsRuns, rsUKeys, rsIdx, rsOldR, rsUses, rsRemap;  // resize scratch (deme_resize.h), allocated by the first resize
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
-    DevBuf geo, binLo, binN, counts, offsets, incKeys[2], incVals[2], keysRaw, keysMid, keysSorted[2], mapping, wc[2], ctr, segCtr,
+    DevBuf geo, binLo, binN, counts, offsets, incKeys[2], incVals[2], keysRaw, keysMid, keysSorted[2], wc[2], ctr, segCtr,
         scanTmp, sortTmp, rec[4], stage;
-    // per-contact contributions and the per-owner gather lists (built once per detection)
-    DevBuf conA4, conA2, conB4, conB2, aSum, ownerA, ownerB[2], bIdx[2], aStart, bStart, heavy, fixedFlag, heavyList, rangeCtr;
-    uint32_t nHeavy = 0, nHeavyFree = 0, nSA = 0, nSM = 0;
-    DevBuf info;
-    // owner-tile form of the force pass (deme_tile.h), rebuilt per detection
-    DevBuf tileBig, bigList, tInfo, hList, hCount, tileMode, tileOrg, rIdx, rStart, remKey[2], remVal, lPos, lOff, lCount, tileRem, tileBase, rankC, rec32;
-    // the heavy-owner counts of a tiled list are fetched without stopping the stream: the copy lands in pinned memory, the first
-    // reader (launch_reduce_heavy, one force launch later) waits for its event
+    // The contact list the steps read (list[cur]) and the one an asynchronous detection builds beside them (list[cur ^ 1]).
+    // Shared by both, on purpose: the key and history double buffers with their selectors (keysSorted, wc, keysCur, wcCur ...),
+    // the per-contact products of the force pass (conA*, conB*, aSum, rec32, rec[]), the pinned target of the heavy-owner
+    // read-back (hrPinned, hrEvent) and the closed-tile structures of the one-kernel step (recContact, inCnt ... below).
+    ContactList list[2];
+    int cur = 0;
+    // per-contact contributions of the force pass
+    DevBuf conA4, conA2, conB4, conB2, aSum, rec32;
+    // One pinned block and one event serve the pending read-back (ContactList::hrPending) of both lists: a list's read-back is
+    // resolved by the first force launch on it, or superseded when the list is built again, before the other list's is issued
+    // -- an asynchronous cycle enqueues D >= 1 steps on the current list before part 2 builds the other.
     RangeCounters* hrPinned = nullptr;
     hipEvent_t hrEvent = nullptr;
-    bool hrPending = false, heavyOverflow = false;
     bool ctrFresh = false;  // DetectCounters were zeroed by the margins kernel's launch and nothing has counted in them since
-    uint64_t nListed = 0;      // contacts of the list the owner arrays (ownerA, ownerB[0], info ...) were built for
-    int listKeys = 0;
-    bool legacyLists = false;  // the B-sorted list of the round-2 kernels exists for the current contact list (built on demand when the list has tile structures)
-    bool tileActive = false;  // the current list has tile structures (built-in model, fast mode, every halo fits)
     bool conTile = false;     // the contributions in memory were written by the tile kernel
     // the whole step in one kernel (deme_tile_step.h): closed tiles -- a contact that straddles two tiles is evaluated by both --
     // integrate their own owners; owners and history are double-buffered
 #define DEME_FUSED_AUTO_MAX_OWNERS 100000u  // deme_set_fused_step(ctx, 2): the one-kernel step where it was measured faster (header)
     int fusedEnable = 0;          // deme_set_fused_step / DEME_FUSED=1: the one-kernel step (measured slower on the packed bed: DESIGN 3.7)
-    bool fusedList = false;       // the current list has the incoming structures (decided per detection)
-    bool fusedChecked = false;    // ... and the device has been asked whether every closed tile fits
     bool fusedPrevValid = false;  // the last step was a fused one: the buffers of its start are intact (a / alpha can be replayed from them)
     uint64_t nFusedSteps = 0;
+    // (these exist once, not per list: only k_tile_incoming and k_tile_step read them, and the one-kernel step is never chosen for
+    // a list built while asyncLead != 0.  k_tile_build writes recContact unconditionally, so the pointer is always valid -- also
+    // when part 2 runs on the detection stream, where nothing in flight reads it.)
     DevBuf ownersNext, recContact, inCnt, inStart, tInfoIn, inContact, hCountIn;
     // A run-time compiled model takes the tile pass only when a tile holds enough contacts to pay for its staging (measured on
     // configs[4], 1e6 single spheres with 1.6 contacts each = 200 per tile: tile pass 0.058 ms against 0.044 ms for the general
@@ -123,7 +159,6 @@ struct deme_ctx {
     uint32_t tileMinContactsCustom = 320;
     uint64_t lastSegMax = 0;             // longest segment of the last detection (sizes the early launch of k_compact_keys)
     size_t keySegMin = (size_t)1 << 20;  // arenas from this many slots on are cut into DEME_KEY_SEGS segments (DEME_KEY_SEG_MIN; 0: never)
-    uint32_t tileMaxHalo = 0, tileMaxList = 0, nBigTiles = 0, tileMaxHaloIn = 0;
     // persistent contacts: the sorted set of marked keys (host copy + device copy appended to every detection's raw keys)
     DevBuf persistKeys, binStat;
     // acceleration the script adds for the next step only (deme_add_owner_acc): device records + host mirror
@@ -153,7 +188,7 @@ struct deme_ctx {
     // family motion prescriptions: run-time compiled kernel + the owners it applies to
     hipModule_t prescMod = nullptr;
     hipFunction_t prescFn = nullptr;
-    DevBuf prescList, prescSlot, prescRec, smFlag, smList, cDefer, blockMode;
+    DevBuf prescList, prescSlot, prescRec;
     DevBuf userWc[4][8];  // [kind: owners, spheres, triangles, analytical][index]
     uint32_t nOwnerWc = 0, nGeoWc = 0;
     bool hasGhosts = false;  // a family carries DEME_FAMILY_GHOST: force passes can be split for the halo overlap
@@ -168,8 +203,6 @@ struct deme_ctx {
     bool crossStale = false;  // a scene was uploaded while the group evaluates cross-cut contacts once: rev_setup_slab runs again first
     char* pin = nullptr;       // 16 KB of pinned host memory: where the detection's read-backs land
     int spinSync = 1;          // DEME_SPIN_SYNC=0: blocking waits at the detection's read-backs
-    bool listOwnersSnap = false;  // (asynchronous detection) part 2 runs beside the steps too: it reads the snapshot, writes the spare set
-    DevBuf spare[40];              // the second set of the list structures (list_set): the steps in flight read one, part 2 builds the other
     bool snapPending = false;  // (slab group) take the owner snapshot of an asynchronous detection in this step, once the ghosts are in place
     DevBuf ownersSnap;
     hipStream_t detStream = nullptr;
@@ -260,13 +293,13 @@ int fail(deme_ctx* c, int code, const char* fmt, ...) {
 
 // The sizing read-backs of a detection: the host has nothing else to do, the GPU idles until it is back with the next launches,
 // and a blocking wait wakes up tens of microseconds late -- so the host polls the stream (for at most a few milliseconds; a
-// detection beside the steps, whose wait is long by design, blocks instead of burning a core).
+// part 1 beside the steps, whose wait is long by design, blocks instead of burning a core).
 template <typename T>
 static inline T* pin_at(deme_ctx* c, size_t off) {
     return reinterpret_cast<T*>(c->pin + off);
 }
-static hipError_t sync_readback(deme_ctx* c, hipStream_t st) {
-    if (c->spinSync && st == c->stream) {
+static hipError_t sync_readback(deme_ctx* c, hipStream_t st, bool spin) {
+    if (c->spinSync && spin) {
         const auto t0 = std::chrono::steady_clock::now();
         for (int it = 0;; it++) {
             const hipError_t q = hipStreamQuery(st);
@@ -307,6 +340,19 @@ int upload(deme_ctx* c, DevBuf& b, const T* src, size_t n) {
         HIPCK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     else if (n)
         HIPCK(hipMemsetAsync(b.p, 0, n * sizeof(T), c->stream));
+    return DEME_OK;
+}
+
+// The two-call idiom of the rocprim device algorithms: size query, room in `tmp` (scanTmp or sortTmp), the call itself.
+// call(void* storage, size_t& bytes) -> hipError_t
+template <class Call>
+int with_temp(deme_ctx* c, DevBuf& tmp, Call&& call) {
+    size_t bytes = 0;
+    HIPCK(call(nullptr, bytes));
+    if (int rc = ensure(c, tmp, bytes))
+        return rc;
+    bytes = tmp.bytes;
+    HIPCK(call(tmp.p, bytes));
     return DEME_OK;
 }
 
@@ -431,6 +477,47 @@ void build_mat_pairs(const DemeScene* s, std::vector<MatPair>& out) {
         }
 }
 
+// ---- the sizes of a contact list's buffers: ONE statement each for the per-contact and the per-owner / per-tile ones, used for
+// the current list (grow_contact_arena, owner_scratch_for_counts) and for the one an asynchronous detection builds (async_size_next)
+int size_list_per_contact(deme_ctx* c, ContactList& L, size_t cap, bool hasGhosts, uint32_t nTri) {
+    int rc = 0;
+    rc |= ensure(c, L.mapping, cap * 4, true);  // (read by the history migration after the detection that wrote it: kept)
+    rc |= ensure(c, L.ownerA, cap * 4);
+    for (int k = 0; k < 2; k++) {
+        rc |= ensure(c, L.ownerB[k], cap * 4);
+        rc |= ensure(c, L.bIdx[k], cap * 4);
+    }
+    rc |= ensure(c, L.info, cap * 16);
+    rc |= ensure(c, L.tInfo, cap * 8);
+    rc |= ensure(c, L.rIdx, cap * 4);
+    rc |= ensure(c, L.lPos, cap * 2);
+    rc |= ensure(c, L.remVal, (cap + 1) * 4);
+    rc |= ensure(c, L.rankC, (cap + 1) * 4);
+    rc |= ensure(c, L.remKey[0], (cap + 1) * 4);
+    rc |= ensure(c, L.remKey[1], (cap + 1) * 4);
+    if (hasGhosts) {
+        rc |= ensure(c, L.cDefer, cap);
+        rc |= ensure(c, L.blockMode, (cap / DEME_FORCE_BLOCK + 2) * 4);
+    }
+    if (nTri) {
+        rc |= ensure(c, L.smFlag, cap);
+        rc |= ensure(c, L.smList, cap * 4);
+    }
+    return rc;
+}
+int size_list_per_owner(deme_ctx* c, ContactList& L, size_t nO) {
+    if (ensure(c, L.aStart, (nO + 1) * 4) || ensure(c, L.bStart, (nO + 1) * 4) || ensure(c, L.heavy, nO + 1) || ensure(c, L.fixedFlag, nO + 1) ||
+        ensure(c, L.heavyList, 4096 * 4) || ensure(c, L.rangeCtr, sizeof(RangeCounters)))
+        return c->lastStatus;
+    const size_t nTiles = (nO + DEME_TILE_NB - 1) / DEME_TILE_NB + 1;
+    if (ensure(c, L.hList, nTiles * DEME_TILE_HMAX * 4) || ensure(c, L.hCount, nTiles * 4) || ensure(c, L.tileMode, nTiles * 4) ||
+        ensure(c, L.tileOrg, nTiles * 24) || ensure(c, L.rStart, (nO + 1) * 4) || ensure(c, L.lOff, nTiles * (DEME_TILE_NB + 1) * 2) ||
+        ensure(c, L.lCount, nTiles * 4) || ensure(c, L.tileRem, (nTiles + 1) * 4) || ensure(c, L.tileBase, (nTiles + 1) * 4) ||
+        ensure(c, L.tileBig, nTiles * 4) || ensure(c, L.bigList, nTiles * 4))
+        return c->lastStatus;
+    return DEME_OK;
+}
+
 int grow_contact_arena(deme_ctx* c, size_t cap) {
     const uint32_t nW = std::max<uint32_t>(c->hp.nContactWildcards, 1);
     int rc = 0;
@@ -438,7 +525,6 @@ int grow_contact_arena(deme_ctx* c, size_t cap) {
     // sorted lists and wildcards carry state between detections: keep their contents
     rc |= ensure(c, c->keysSorted[0], cap * 8, true);
     rc |= ensure(c, c->keysSorted[1], cap * 8, true);
-    rc |= ensure(c, c->mapping, cap * 4, true);
     rc |= ensure(c, c->wc[0], cap * 4 * nW, true);
     rc |= ensure(c, c->wc[1], cap * 4 * nW, true);
     if (c->record)
@@ -448,31 +534,11 @@ int grow_contact_arena(deme_ctx* c, size_t cap) {
     rc |= ensure(c, c->conA2, cap * 8);
     rc |= ensure(c, c->conB4, cap * 16);
     rc |= ensure(c, c->conB2, cap * 8);
-    rc |= ensure(c, c->ownerA, cap * 4);
-    for (int k = 0; k < 2; k++) {
-        rc |= ensure(c, c->ownerB[k], cap * 4);
-        rc |= ensure(c, c->bIdx[k], cap * 4);
-    }
-    rc |= ensure(c, c->info, cap * 16);
-    rc |= ensure(c, c->tInfo, cap * 8);
-    rc |= ensure(c, c->rIdx, cap * 4);
-    rc |= ensure(c, c->lPos, cap * 2);
-    rc |= ensure(c, c->remVal, (cap + 1) * 4);
-    rc |= ensure(c, c->rankC, (cap + 1) * 4);
+    rc |= size_list_per_contact(c, c->list[c->cur], cap, c->hasGhosts, c->nTri);
     rc |= ensure(c, c->recContact, (cap + 1) * 4);
     rc |= ensure(c, c->tInfoIn, cap * 8);
     rc |= ensure(c, c->inContact, cap * 4);
     rc |= ensure(c, c->rec32, cap * 32);
-    rc |= ensure(c, c->remKey[0], (cap + 1) * 4);
-    rc |= ensure(c, c->remKey[1], (cap + 1) * 4);
-    if (c->hasGhosts) {
-        rc |= ensure(c, c->cDefer, cap);
-        rc |= ensure(c, c->blockMode, (cap / DEME_FORCE_BLOCK + 2) * 4);
-    }
-    if (c->nTri) {
-        rc |= ensure(c, c->smFlag, cap);
-        rc |= ensure(c, c->smList, cap * 4);
-    }
     if (rc)
         return rc;
     c->cntCap = cap;
@@ -563,7 +629,7 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             // tens of microseconds of host time before the wait even starts)
             HIPCK(hipMemcpyAsync(pin_at<uint32_t>(c, 0), c->offsets.as<uint32_t>() + nS, 4, hipMemcpyDeviceToHost, st));
             HIPCK(hipMemcpyAsync(pin_at<DetectCounters>(c, 64), c->ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
-            HIPCK(sync_readback(c, st));
+            HIPCK(sync_readback(c, st, !async));
             P = *pin_at<uint32_t>(c, 0), hc = *pin_at<DetectCounters>(c, 64);
             if (!statusSeen) {
                 statusSeen = true;
@@ -580,12 +646,10 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
                 unsigned long long* tot = &c->ctr.as<DetectCounters>()->nContactsRaw;  // borrowed: saved and restored around the reduction (k_sphere_prep has already counted its sphere-analytical contacts here)
                 unsigned long long keep = 0, total = 0;
                 HIPCK(hipMemcpyAsync(&keep, tot, 8, hipMemcpyDeviceToHost, st));
-                size_t need = 0;
-                HIPCK(rocprim::reduce(nullptr, need, in64, tot, 0ull, (size_t)nS, rocprim::plus<unsigned long long>(), st));
-                if (int rc = ensure(c, c->sortTmp, need))
+                if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                        return rocprim::reduce(tmp, bytes, in64, tot, 0ull, (size_t)nS, rocprim::plus<unsigned long long>(), st);
+                    }))
                     return rc;
-                need = c->sortTmp.bytes;
-                HIPCK(rocprim::reduce(c->sortTmp.p, need, in64, tot, 0ull, (size_t)nS, rocprim::plus<unsigned long long>(), st));
                 HIPCK(hipMemcpyAsync(&total, tot, 8, hipMemcpyDeviceToHost, st));
                 HIPCK(hipStreamSynchronize(st));
                 HIPCK(hipMemcpyAsync(tot, &keep, 8, hipMemcpyHostToDevice, st));
@@ -610,20 +674,15 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             unsigned bits = 1;
             while (bits < 32 && (1ull << bits) < nBins)
                 bits++;
-            size_t need = 0;
             // bin ids of up to 22 bits: two passes of 11 bits (16 keys per thread) take as long as three of 8 and save a pass's launches
             const bool twoPass = bits > 16 && bits <= 22;
-            auto sortInc = [&](void* tmp, size_t& bytes) {
-                return twoPass ? rocprim::radix_sort_pairs<DemeRadixCfg<11, 16>>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
-                                                                                 c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P, 0, bits, st)
-                               : rocprim::radix_sort_pairs<DemeRadixCfg<8>>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
-                                                                            c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P, 0, bits, st);
-            };
-            HIPCK(sortInc(nullptr, need));
-            if (int rc = ensure(c, c->sortTmp, need))
+            if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                    return twoPass ? rocprim::radix_sort_pairs<DemeRadixCfg<11, 16>>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
+                                                                                     c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P, 0, bits, st)
+                                   : rocprim::radix_sort_pairs<DemeRadixCfg<8>>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
+                                                                                c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P, 0, bits, st);
+                }))
                 return rc;
-            need = c->sortTmp.bytes;
-            HIPCK(sortInc(c->sortTmp.p, need));
             sortedIdx = 1;
             const uint32_t nWin = (uint32_t)grid_for(P, SW_T);
             if (int rc = ensure(c, c->binStat, (size_t)nWin * sizeof(uint2)))
@@ -666,16 +725,11 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
                 unsigned bits = 1;
                 while (bits < 32 && (1ull << bits) < nBins)
                     bits++;
-                size_t need = 0;
-                HIPCK(rocprim::radix_sort_pairs(nullptr, need, c->triKeys[0].as<uint32_t>(), c->triKeys[1].as<uint32_t>(),
-                                                c->triVals[0].as<uint32_t>(), c->triVals[1].as<uint32_t>(), (size_t)TP, 0, bits,
-                                                st));
-                if (int rc = ensure(c, c->sortTmp, need))
+                if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                        return rocprim::radix_sort_pairs(tmp, bytes, c->triKeys[0].as<uint32_t>(), c->triKeys[1].as<uint32_t>(),
+                                                         c->triVals[0].as<uint32_t>(), c->triVals[1].as<uint32_t>(), (size_t)TP, 0, bits, st);
+                    }))
                     return rc;
-                need = c->sortTmp.bytes;
-                HIPCK(rocprim::radix_sort_pairs(c->sortTmp.p, need, c->triKeys[0].as<uint32_t>(), c->triKeys[1].as<uint32_t>(),
-                                                c->triVals[0].as<uint32_t>(), c->triVals[1].as<uint32_t>(), (size_t)TP, 0, bits,
-                                                st));
                 hipLaunchKernelGGL(k_tri_sweep, dim3(grid_for(TP)), dim3(256), 0, st, c->dp, TP,
                                    c->triKeys[1].as<uint32_t>(), c->triVals[1].as<uint32_t>(), c->triWorld.as<TriWorld>(), P,
                                    c->incKeys[1].as<uint32_t>(), c->incVals[1].as<uint32_t>(), c->geo.as<GeoRec>(),
@@ -695,7 +749,7 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
         const unsigned long long* hseg = pin_at<unsigned long long>(c, 1024);
         if (segmented)
             HIPCK(hipMemcpyAsync(pin_at<unsigned long long>(c, 1024), c->segCtr.p, DEME_KEY_SEGS * DEME_KEY_SEG_STRIDE * 8, hipMemcpyDeviceToHost, st));
-        HIPCK(sync_readback(c, st));
+        HIPCK(sync_readback(c, st, !async));
         hc = *pin_at<DetectCounters>(c, 64);
         if (!statusSeen) {
             statusSeen = true;
@@ -763,24 +817,19 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             if (int rc = ensure(c, c->keysMid, (size_t)c->cntCap * 8))  // (its own scratch: an asynchronous detection runs beside force passes)
                 return rc;
             uint64_t* mid = c->keysMid.as<uint64_t>();
-            size_t needHi = 0;
-            HIPCK(rocprim::radix_sort_keys<DemeRadixCfg<8>>(nullptr, needHi, rawKeys, mid, (size_t)nC, 31, 33 + bitsA, st));
-            if (int rc = ensure(c, c->sortTmp, needHi))
+            if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                    return rocprim::radix_sort_keys<DemeRadixCfg<8>>(tmp, bytes, rawKeys, mid, (size_t)nC, 31, 33 + bitsA, st);
+                }))
                 return rc;
-            needHi = c->sortTmp.bytes;
-            HIPCK(rocprim::radix_sort_keys<DemeRadixCfg<8>>(c->sortTmp.p, needHi, rawKeys, mid, (size_t)nC, 31, 33 + bitsA, st));
             hipLaunchKernelGGL(k_segment_rank_sort, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, mid,
                                c->keysSorted[next].as<uint64_t>());
             if (nPersist) {  // a marked contact the sweep found as well appears once (markDuplicateContacts)
                 unsigned long long* cnt = &c->ctr.as<DetectCounters>()->nContactsRaw;
-                size_t need2 = 0;
-                HIPCK(rocprim::unique(nullptr, need2, c->keysSorted[next].as<uint64_t>(), c->keysRaw.as<uint64_t>(), cnt, (size_t)nC,
-                                      rocprim::equal_to<uint64_t>(), st));
-                if (int rc = ensure(c, c->scanTmp, need2))
+                if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+                        return rocprim::unique(tmp, bytes, c->keysSorted[next].as<uint64_t>(), c->keysRaw.as<uint64_t>(), cnt, (size_t)nC,
+                                               rocprim::equal_to<uint64_t>(), st);
+                    }))
                     return rc;
-                need2 = c->scanTmp.bytes;
-                HIPCK(rocprim::unique(c->scanTmp.p, need2, c->keysSorted[next].as<uint64_t>(), c->keysRaw.as<uint64_t>(), cnt,
-                                      (size_t)nC, rocprim::equal_to<uint64_t>(), st));
                 unsigned long long nU = 0;
                 HIPCK(hipMemcpyAsync(&nU, cnt, 8, hipMemcpyDeviceToHost, st));
                 HIPCK(hipStreamSynchronize(st));
@@ -794,235 +843,210 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
     return fail(c, DEME_ERR_OVERFLOW, "contact arena kept overflowing");
 }
 
-// The owner records the list builders read (tile origins, ghost and family flags): the live ones -- or, while an asynchronous
-// detection builds its list beside steps that are integrating them, the snapshot part 1 was made from
-static inline const OwnerRec* list_owners(deme_ctx* c) {
-    return c->listOwnersSnap ? c->ownersSnap.as<OwnerRec>() : c->owners.as<OwnerRec>();
-}
-
 // The B-sorted contact list of the round-2 kernels (k_forces_fast / k_calc_forces + the integrator's gather): owner-B sort, run
-// starts, heavy / fixed flags, the deferral flags of the halo overlap.  Enqueued on the main stream; the caller reads rangeCtr.
-int build_legacy_lists(deme_ctx* c) {
-    const uint64_t nC = c->nListed;
+// starts, heavy / fixed flags, the deferral flags of the halo overlap.  Enqueued on `st`; the caller reads rangeCtr.
+int build_legacy_lists(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st) {
+    const uint64_t nC = L.nListed;
     if (nC) {
         unsigned obits = 1;
         while (obits < 32 && (1ull << obits) < (uint64_t)c->nOwners)
             obits++;
-        size_t need = 0;
-        HIPCK(rocprim::radix_sort_pairs(nullptr, need, c->ownerB[0].as<uint32_t>(), c->ownerB[1].as<uint32_t>(),
-                                        c->bIdx[0].as<uint32_t>(), c->bIdx[1].as<uint32_t>(), (size_t)nC, 0, obits, c->stream));
-        if (int rc = ensure(c, c->sortTmp, need))
+        if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                return rocprim::radix_sort_pairs(tmp, bytes, L.ownerB[0].as<uint32_t>(), L.ownerB[1].as<uint32_t>(), L.bIdx[0].as<uint32_t>(),
+                                                 L.bIdx[1].as<uint32_t>(), (size_t)nC, 0, obits, st);
+            }))
             return rc;
-        need = c->sortTmp.bytes;
-        HIPCK(rocprim::radix_sort_pairs(c->sortTmp.p, need, c->ownerB[0].as<uint32_t>(), c->ownerB[1].as<uint32_t>(),
-                                        c->bIdx[0].as<uint32_t>(), c->bIdx[1].as<uint32_t>(), (size_t)nC, 0, obits, c->stream));
     }
     if (c->hasGhosts) {  // (the arena may have been sized before the scene's family flags were known)
-        if (ensure(c, c->cDefer, c->cntCap) || ensure(c, c->blockMode, (c->cntCap / DEME_FORCE_BLOCK + 2) * 4))
-            return c->lastStatus;
-        HIPCK(hipMemsetAsync(c->blockMode.p, 0, c->blockMode.bytes, c->stream));
+        if (int rc = size_list_per_contact(c, L, c->cntCap, true, c->nTri))
+            return rc;
+        HIPCK(hipMemsetAsync(L.blockMode.p, 0, L.blockMode.bytes, st));
     }
     if (nC)
-        hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nC)), dim3(256), 0, c->stream, (uint32_t)nC, c->ownerB[1].as<uint32_t>(),
-                           c->nOwners, c->bStart.as<uint32_t>());
+        hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, L.ownerB[1].as<uint32_t>(),
+                           c->nOwners, L.bStart.as<uint32_t>());
     else
-        HIPCK(hipMemsetAsync(c->bStart.p, 0, ((size_t)c->nOwners + 1) * 4, c->stream));
+        HIPCK(hipMemsetAsync(L.bStart.p, 0, ((size_t)c->nOwners + 1) * 4, st));
     // (the counters may hold the tile builders' count of the same owners)
-    HIPCK(hipMemsetAsync(&c->rangeCtr.as<RangeCounters>()->nHeavy, 0, 2 * sizeof(unsigned int), c->stream));
-    hipLaunchKernelGGL(k_owner_ranges, dim3(grid_for((size_t)c->nOwners + 1)), dim3(256), 0, c->stream, c->dp, (uint32_t)nC,
-                       c->ownerA.as<uint32_t>(), c->ownerB[1].as<uint32_t>(), list_owners(c), c->aStart.as<uint32_t>(),
-                       c->bStart.as<uint32_t>(), c->heavy.as<uint8_t>(), c->fixedFlag.as<uint8_t>(), c->heavyList.as<uint32_t>(),
-                       (uint32_t)(c->heavyList.bytes / 4), c->rangeCtr.as<RangeCounters>(), c->info.as<uint4>(),
-                       c->hasGhosts ? c->cDefer.as<uint8_t>() : (uint8_t*)nullptr, c->blockMode.as<uint32_t>());
-    c->legacyLists = true;
+    HIPCK(hipMemsetAsync(&L.rangeCtr.as<RangeCounters>()->nHeavy, 0, 2 * sizeof(unsigned int), st));
+    hipLaunchKernelGGL(k_owner_ranges, dim3(grid_for((size_t)c->nOwners + 1)), dim3(256), 0, st, c->dp, (uint32_t)nC,
+                       L.ownerA.as<uint32_t>(), L.ownerB[1].as<uint32_t>(), ow, L.aStart.as<uint32_t>(),
+                       L.bStart.as<uint32_t>(), L.heavy.as<uint8_t>(), L.fixedFlag.as<uint8_t>(), L.heavyList.as<uint32_t>(),
+                       (uint32_t)(L.heavyList.bytes / 4), L.rangeCtr.as<RangeCounters>(), L.info.as<uint4>(),
+                       c->hasGhosts ? L.cDefer.as<uint8_t>() : (uint8_t*)nullptr, L.blockMode.as<uint32_t>());
+    L.legacyLists = true;
+    return DEME_OK;
+}
+// ... and its heavy-owner counts on the host (a wait for `st`)
+int read_legacy_counts(deme_ctx* c, ContactList& L, hipStream_t st, RangeCounters& hr) {
+    HIPCK(hipMemcpyAsync(&hr, L.rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (hr.nHeavy > L.heavyList.bytes / 4)
+        return fail(c, DEME_ERR_OVERFLOW, "%u owners exceed the heavy-owner list", hr.nHeavy);
+    L.nHeavy = hr.nHeavy, L.nHeavyFree = hr.nHeavyFree;
     return DEME_OK;
 }
 
-void resolve_heavy_counts(deme_ctx* c);
+void resolve_heavy_counts(deme_ctx* c, ContactList& L);
 // a list built with tile structures that the round-2 kernels evaluate after all (contact recording switched on, the arithmetic
 // mode changed ...): its B-sorted form is built now
 int ensure_legacy_lists(deme_ctx* c) {
-    if (c->legacyLists || !c->haveList)
+    ContactList& L = c->list[c->cur];
+    if (L.legacyLists || !c->haveList)
         return DEME_OK;
-    resolve_heavy_counts(c);
-    if (int rc = build_legacy_lists(c))
+    resolve_heavy_counts(c, L);
+    if (int rc = build_legacy_lists(c, L, c->owners.as<OwnerRec>(), c->stream))
         return rc;
     RangeCounters hr{};
-    HIPCK(hipMemcpyAsync(&hr, c->rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    if (hr.nHeavy > c->heavyList.bytes / 4)
-        return fail(c, DEME_ERR_OVERFLOW, "%u owners exceed the heavy-owner list", hr.nHeavy);
-    c->nHeavy = hr.nHeavy, c->nHeavyFree = hr.nHeavyFree;
-    return DEME_OK;
+    return read_legacy_counts(c, L, c->stream, hr);
 }
 
-int detect_part2(deme_ctx* c, uint64_t nC) {
+// Part 2 of a detection: the history map and the structures of `L`, built on `st` from the owner records `ow` (the live ones --
+// or, beside steps that are integrating them, the snapshot part 1 was made from) and the nC keys part 1 left in the next key
+// buffer.  Everything fallible comes first and touches `L` only; the context turns to the new list in the last lines.
+int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st, uint64_t nC) {
     const int next = c->keysCur ^ 1;
-    {
-        if (nC) {
-            const uint64_t nPrev = c->haveList ? c->nContacts : 0;
-            hipLaunchKernelGGL(k_history, dim3(grid_for(nC)), dim3(256), 0, c->stream, (uint32_t)nC,
-                               c->keysSorted[next].as<uint64_t>(), (uint32_t)nPrev,
-                               c->keysSorted[c->keysCur].as<uint64_t>(), c->mapping.as<uint32_t>());
-        }
-        // per-owner gather lists for the atomics-free accumulation
-        HIPCK(hipMemsetAsync(c->rangeCtr.p, 0, sizeof(RangeCounters), c->stream));
-        const bool tileEligible = nC && c->arith == DEME_ARITH_FAST &&
-                                  (c->hp.forceModel != DEME_FORCE_CUSTOM ||
-                                   (c->customTileFn[0] && nC >= (uint64_t)c->tileMinContactsCustom * ((c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB))) &&
-                                  c->hShared.empty() && c->nMat <= 16 && c->nAnal <= 65535 && c->nComp <= 65535 &&
-                                  tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial) <= DEME_TILE_TABLE_MAX &&
-                                  c->nComp + c->nMat * c->nMat * 2u + c->nAnal * 4u <= DEME_TILE_T && c->nMassProps <= DEME_TILE_T;
-        const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
-        if (tileEligible)
-            HIPCK(hipMemsetAsync(c->tileRem.p, 0, ((size_t)nTiles + 1) * 4, c->stream));
-        if (nC) {
-            hipLaunchKernelGGL(k_contact_owners, dim3(grid_for(nC)), dim3(256), 0, c->stream, c->dp, (uint32_t)nC,
-                               c->keysSorted[next].as<uint64_t>(), c->spheres.as<SphereRec>(), c->ownerA.as<uint32_t>(),
-                               c->ownerB[0].as<uint32_t>(), c->bIdx[0].as<uint32_t>(), c->info.as<uint4>(),
-                               c->nTri ? c->smFlag.as<uint8_t>() : (uint8_t*)nullptr,
-                               tileEligible ? c->tileRem.as<uint32_t>() : (uint32_t*)nullptr, (uint32_t)DEME_TILE_NB);
-            if (c->nTri) {  // work list of the mesh-variant force kernel; its length lands in RangeCounters::nSM
-                unsigned int* cnt = &c->rangeCtr.as<RangeCounters>()->nSM;
-                size_t need2 = 0;
-                HIPCK(rocprim::select(nullptr, need2, rocprim::counting_iterator<uint32_t>(0), c->smFlag.as<uint8_t>(),
-                                      c->smList.as<uint32_t>(), cnt, (size_t)nC, c->stream));
-                if (int rc = ensure(c, c->scanTmp, need2))
-                    return rc;
-                need2 = c->scanTmp.bytes;
-                HIPCK(rocprim::select(c->scanTmp.p, need2, rocprim::counting_iterator<uint32_t>(0), c->smFlag.as<uint8_t>(),
-                                      c->smList.as<uint32_t>(), cnt, (size_t)nC, c->stream));
-            }
-            hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nC)), dim3(256), 0, c->stream, (uint32_t)nC, c->ownerA.as<uint32_t>(),
-                               c->nOwners, c->aStart.as<uint32_t>());
-        } else {
-            HIPCK(hipMemsetAsync(c->aStart.p, 0, ((size_t)c->nOwners + 1) * 4, c->stream));
-        }
-        c->legacyLists = false;
-        c->nListed = nC, c->listKeys = next;
-        bool tiled = false;
-        RangeCounters hr{};
-        if (tileEligible) {  // owner tiles (deme_tile.h): the builders of the list structures k_tile_forces and the integrator read
-            size_t need = 0;
-            HIPCK(rocprim::exclusive_scan(nullptr, need, c->tileRem.as<uint32_t>(), c->tileBase.as<uint32_t>(), 0u, (size_t)nTiles + 1,
-                                          rocprim::plus<uint32_t>(), c->stream));
-            if (int rc = ensure(c, c->scanTmp, need))
-                return rc;
-            need = c->scanTmp.bytes;
-            HIPCK(rocprim::exclusive_scan(c->scanTmp.p, need, c->tileRem.as<uint32_t>(), c->tileBase.as<uint32_t>(), 0u, (size_t)nTiles + 1,
-                                          rocprim::plus<uint32_t>(), c->stream));
-            hipLaunchKernelGGL(k_tile_build, dim3(nTiles), dim3(256), 0, c->stream, c->dp, c->nOwners, c->info.as<uint4>(),
-                               c->ownerB[0].as<uint32_t>(), c->aStart.as<uint32_t>(), list_owners(c), c->tileBase.as<uint32_t>(), c->tInfo.as<uint2>(),
-                               c->hList.as<uint32_t>(), c->hCount.as<uint32_t>(),
-                               c->hasGhosts ? c->tileMode.as<uint32_t>() : (uint32_t*)nullptr, c->lOff.as<uint16_t>(),
-                               c->lPos.as<uint16_t>(), c->lCount.as<uint32_t>(), c->rankC.as<uint32_t>(), c->remKey[0].as<uint32_t>(),
-                               c->remVal.as<uint32_t>(), c->tileOrg.as<int64_t>(), c->rangeCtr.as<RangeCounters>(), nTiles,
-                               c->tileBig.as<uint32_t>(), c->bigList.as<uint32_t>(), c->recContact.as<uint32_t>());
-            hipLaunchKernelGGL(k_tile_stats, dim3((nTiles + 1023u) / 1024u), dim3(256), 0, c->stream, nTiles, c->hCount.as<uint32_t>(),
-                               c->lCount.as<uint32_t>(), c->rangeCtr.as<RangeCounters>());
-            uint32_t nR = 0;  // crossing contacts = records = entries of the sort below: the one size the host has to know
-            HIPCK(hipMemcpyAsync(pin_at<uint32_t>(c, 8), c->tileBase.as<uint32_t>() + nTiles, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCK(hipMemcpyAsync(pin_at<RangeCounters>(c, 128), c->rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
-            HIPCK(sync_readback(c, c->stream));
-            nR = *pin_at<uint32_t>(c, 8), hr = *pin_at<RangeCounters>(c, 128);
-            nR += hr.nExtra;  // the records of the tiles that do not fit (k_tile_forces_big): every contact of such a tile has one
-            c->nBigTiles = hr.nBig;
-            {
-                unsigned obits = 1;
-                while (obits < 32 && (1ull << obits) < (uint64_t)c->nOwners)
-                    obits++;
-                if (nR) {
-                    size_t needS = 0;
-                    HIPCK(rocprim::radix_sort_pairs<DemeRadixCfg<10>>(nullptr, needS, c->remKey[0].as<uint32_t>(), c->remKey[1].as<uint32_t>(),
-                                                    c->remVal.as<uint32_t>(), c->rIdx.as<uint32_t>(), (size_t)nR, 0, obits, c->stream));
-                    if (int rc = ensure(c, c->sortTmp, needS))
-                        return rc;
-                    needS = c->sortTmp.bytes;
-                    HIPCK(rocprim::radix_sort_pairs<DemeRadixCfg<10>>(c->sortTmp.p, needS, c->remKey[0].as<uint32_t>(), c->remKey[1].as<uint32_t>(),
-                                                    c->remVal.as<uint32_t>(), c->rIdx.as<uint32_t>(), (size_t)nR, 0, obits, c->stream));
-                    hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nR)), dim3(256), 0, c->stream, nR, c->remKey[1].as<uint32_t>(),
-                                       c->nOwners, c->rStart.as<uint32_t>());
-                } else {
-                    HIPCK(hipMemsetAsync(c->rStart.p, 0, ((size_t)c->nOwners + 1) * 4, c->stream));
-                }
-                hipLaunchKernelGGL(k_owner_ranges_tile, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp, list_owners(c),
-                                   c->aStart.as<uint32_t>(), c->lOff.as<uint16_t>(), c->rStart.as<uint32_t>(), c->heavy.as<uint8_t>(),
-                                   c->fixedFlag.as<uint8_t>(), c->heavyList.as<uint32_t>(), (uint32_t)(c->heavyList.bytes / 4),
-                                   c->rangeCtr.as<RangeCounters>());
-                tiled = true;
-                // closed tiles (deme_tile_step.h): the contacts that hold a tile's owners as B from other tiles, in the tile's frame
-                static const int fusedEnv = getenv("DEME_FUSED") ? atoi(getenv("DEME_FUSED")) : -1;  // (1 / 0 override the context's switch)
-                c->fusedList = false;
-                const int fusedMode = fusedEnv < 0 ? c->fusedEnable : fusedEnv;  // 0 off, 1 on, 2 by the size of the bed
-                if ((fusedMode == 2 ? c->nOwners <= DEME_FUSED_AUTO_MAX_OWNERS : fusedMode != 0) && hr.nBig == 0 && c->hp.forceModel != DEME_FORCE_CUSTOM && !c->record && c->nTri == 0 &&
-                    !c->hasGhosts && !c->prescFn && !c->rulesFn && c->hShared.empty() && c->asyncLead == 0 && !c->listOwnersSnap &&
-                    !c->ad.autoBinSize && !c->ad.autoUpdateFreq) {
-                    hipLaunchKernelGGL(k_in_count, dim3(grid_for((size_t)c->nOwners + 1)), dim3(256), 0, c->stream, c->dp, list_owners(c),
-                                       c->rStart.as<uint32_t>(), c->inCnt.as<uint32_t>());
-                    size_t needI = 0;
-                    HIPCK(rocprim::exclusive_scan(nullptr, needI, c->inCnt.as<uint32_t>(), c->inStart.as<uint32_t>(), 0u, (size_t)c->nOwners + 1,
-                                                  rocprim::plus<uint32_t>(), c->stream));
-                    if (int rc = ensure(c, c->scanTmp, needI))
-                        return rc;
-                    needI = c->scanTmp.bytes;
-                    HIPCK(rocprim::exclusive_scan(c->scanTmp.p, needI, c->inCnt.as<uint32_t>(), c->inStart.as<uint32_t>(), 0u, (size_t)c->nOwners + 1,
-                                                  rocprim::plus<uint32_t>(), c->stream));
-                    hipLaunchKernelGGL(k_tile_incoming, dim3(nTiles), dim3(256), 0, c->stream, c->dp, c->nOwners, c->info.as<uint4>(),
-                                       c->rStart.as<uint32_t>(), c->rIdx.as<uint32_t>(), c->recContact.as<uint32_t>(), c->inStart.as<uint32_t>(),
-                                       c->hList.as<uint32_t>(), c->hCount.as<uint32_t>(), c->hCountIn.as<uint32_t>(), c->tInfoIn.as<uint2>(),
-                                       c->inContact.as<uint32_t>(), c->rangeCtr.as<RangeCounters>());
-                    c->fusedList = true;  // (whether every closed tile fits comes back with the counters below: fused_ready)
-                }
-                c->fusedChecked = false;
-            }
-        }
-        c->hrPending = c->heavyOverflow = false;
-        if (tiled) {  // (hr holds the tile extremes already; nSA / nSM are not used by the tile path)
-            if (!c->hrPinned) {
-                HIPCK(hipHostMalloc((void**)&c->hrPinned, sizeof(RangeCounters), hipHostMallocDefault));
-                HIPCK(hipEventCreateWithFlags(&c->hrEvent, hipEventDisableTiming));
-            }
-            HIPCK(hipMemcpyAsync(c->hrPinned, c->rangeCtr.p, sizeof(RangeCounters), hipMemcpyDeviceToHost, c->stream));
-            HIPCK(hipEventRecord(c->hrEvent, c->stream));
-            c->hrPending = true;
-            c->nHeavy = c->nHeavyFree = 0;
-        } else {
-            if (int rc = build_legacy_lists(c))
-                return rc;
-            HIPCK(hipMemcpyAsync(&hr, c->rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, c->stream));
-            HIPCK(hipStreamSynchronize(c->stream));
-            if (hr.nHeavy > c->heavyList.bytes / 4)
-                return fail(c, DEME_ERR_OVERFLOW, "%u owners exceed the heavy-owner list", hr.nHeavy);
-            c->nHeavy = hr.nHeavy;
-            c->nHeavyFree = hr.nHeavyFree;
-        }
-        c->tileActive = tiled;
-        c->fusedPrevValid = false;  // (a replay of the last fused step would read the list it was taken with)
-        c->tileMaxHalo = hr.tileMaxHalo, c->tileMaxList = hr.tileMaxList;
-        if (tiled && c->orderEligible) {  // has the bed drifted away from the order it was given?  (order_renew at the next detection)
-            const uint32_t fit = std::max(1u, nTiles - std::min(nTiles, hr.nBig));
-            const uint32_t mean16 = (uint32_t)(16ull * hr.tileHaloSum / fit);
-            if (!c->orderBaseHalo) {
-                c->orderBaseHalo = std::max(mean16, 16u);
-                c->orderDetAt = c->nDetections;
-            } else if (c->nDetections - c->orderDetAt >= 20 && nTiles > 4 &&
-                       (hr.nBig > std::max(4u, nTiles / 64u) || mean16 > c->orderBaseHalo + c->orderBaseHalo / 2)) {
-                c->orderRenewDue = true;
-            }
-        }
-        c->nSA = hr.nSA;
-        c->nSM = hr.nSM;
-        c->conValid = false;
-        c->nPrev = c->haveList ? c->nContacts : 0;
-        c->nContacts = nC;
-        c->keysCur = next;
-        c->listSerial++;
-        c->haveList = true;
-        c->seeded = false;
-        c->mapFresh = true;
-        c->nDetections++;
-        return DEME_OK;
+    L.invalidate();  // (a pending read-back of this list's last build is superseded)
+    if (nC) {
+        const uint64_t nPrev = c->haveList ? c->nContacts : 0;
+        hipLaunchKernelGGL(k_history, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, c->keysSorted[next].as<uint64_t>(),
+                           (uint32_t)nPrev, c->keysSorted[c->keysCur].as<uint64_t>(), L.mapping.as<uint32_t>());
     }
+    // per-owner gather lists for the atomics-free accumulation
+    HIPCK(hipMemsetAsync(L.rangeCtr.p, 0, sizeof(RangeCounters), st));
+    const bool tileEligible = nC && c->arith == DEME_ARITH_FAST &&
+                              (c->hp.forceModel != DEME_FORCE_CUSTOM ||
+                               (c->customTileFn[0] && nC >= (uint64_t)c->tileMinContactsCustom * ((c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB))) &&
+                              c->hShared.empty() && c->nMat <= 16 && c->nAnal <= 65535 && c->nComp <= 65535 &&
+                              tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial) <= DEME_TILE_TABLE_MAX &&
+                              c->nComp + c->nMat * c->nMat * 2u + c->nAnal * 4u <= DEME_TILE_T && c->nMassProps <= DEME_TILE_T;
+    const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
+    if (tileEligible)
+        HIPCK(hipMemsetAsync(L.tileRem.p, 0, ((size_t)nTiles + 1) * 4, st));
+    if (nC) {
+        hipLaunchKernelGGL(k_contact_owners, dim3(grid_for(nC)), dim3(256), 0, st, c->dp, (uint32_t)nC,
+                           c->keysSorted[next].as<uint64_t>(), c->spheres.as<SphereRec>(), L.ownerA.as<uint32_t>(),
+                           L.ownerB[0].as<uint32_t>(), L.bIdx[0].as<uint32_t>(), L.info.as<uint4>(),
+                           c->nTri ? L.smFlag.as<uint8_t>() : (uint8_t*)nullptr,
+                           tileEligible ? L.tileRem.as<uint32_t>() : (uint32_t*)nullptr, (uint32_t)DEME_TILE_NB);
+        if (c->nTri) {  // work list of the mesh-variant force kernel; its length lands in RangeCounters::nSM
+            unsigned int* cnt = &L.rangeCtr.as<RangeCounters>()->nSM;
+            if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+                    return rocprim::select(tmp, bytes, rocprim::counting_iterator<uint32_t>(0), L.smFlag.as<uint8_t>(), L.smList.as<uint32_t>(), cnt,
+                                           (size_t)nC, st);
+                }))
+                return rc;
+        }
+        hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, L.ownerA.as<uint32_t>(), c->nOwners,
+                           L.aStart.as<uint32_t>());
+    } else {
+        HIPCK(hipMemsetAsync(L.aStart.p, 0, ((size_t)c->nOwners + 1) * 4, st));
+    }
+    L.nListed = nC, L.listKeys = next;
+    bool tiled = false;
+    RangeCounters hr{};
+    if (tileEligible) {  // owner tiles (deme_tile.h): the builders of the list structures k_tile_forces and the integrator read
+        if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+                return rocprim::exclusive_scan(tmp, bytes, L.tileRem.as<uint32_t>(), L.tileBase.as<uint32_t>(), 0u, (size_t)nTiles + 1,
+                                               rocprim::plus<uint32_t>(), st);
+            }))
+            return rc;
+        hipLaunchKernelGGL(k_tile_build, dim3(nTiles), dim3(256), 0, st, c->dp, c->nOwners, L.info.as<uint4>(),
+                           L.ownerB[0].as<uint32_t>(), L.aStart.as<uint32_t>(), ow, L.tileBase.as<uint32_t>(), L.tInfo.as<uint2>(),
+                           L.hList.as<uint32_t>(), L.hCount.as<uint32_t>(),
+                           c->hasGhosts ? L.tileMode.as<uint32_t>() : (uint32_t*)nullptr, L.lOff.as<uint16_t>(),
+                           L.lPos.as<uint16_t>(), L.lCount.as<uint32_t>(), L.rankC.as<uint32_t>(), L.remKey[0].as<uint32_t>(),
+                           L.remVal.as<uint32_t>(), L.tileOrg.as<int64_t>(), L.rangeCtr.as<RangeCounters>(), nTiles,
+                           L.tileBig.as<uint32_t>(), L.bigList.as<uint32_t>(), c->recContact.as<uint32_t>());
+        hipLaunchKernelGGL(k_tile_stats, dim3((nTiles + 1023u) / 1024u), dim3(256), 0, st, nTiles, L.hCount.as<uint32_t>(),
+                           L.lCount.as<uint32_t>(), L.rangeCtr.as<RangeCounters>());
+        uint32_t nR = 0;  // crossing contacts = records = entries of the sort below: the one size the host has to know
+        HIPCK(hipMemcpyAsync(pin_at<uint32_t>(c, 8), L.tileBase.as<uint32_t>() + nTiles, 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(pin_at<RangeCounters>(c, 128), L.rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, st));
+        HIPCK(sync_readback(c, st, true));  // (part 2 is short, also beside the steps)
+        nR = *pin_at<uint32_t>(c, 8), hr = *pin_at<RangeCounters>(c, 128);
+        nR += hr.nExtra;  // the records of the tiles that do not fit (k_tile_forces_big): every contact of such a tile has one
+        L.nBigTiles = hr.nBig;
+        unsigned obits = 1;
+        while (obits < 32 && (1ull << obits) < (uint64_t)c->nOwners)
+            obits++;
+        if (nR) {
+            if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                    return rocprim::radix_sort_pairs<DemeRadixCfg<10>>(tmp, bytes, L.remKey[0].as<uint32_t>(), L.remKey[1].as<uint32_t>(),
+                                                                       L.remVal.as<uint32_t>(), L.rIdx.as<uint32_t>(), (size_t)nR, 0, obits, st);
+                }))
+                return rc;
+            hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nR)), dim3(256), 0, st, nR, L.remKey[1].as<uint32_t>(), c->nOwners,
+                               L.rStart.as<uint32_t>());
+        } else {
+            HIPCK(hipMemsetAsync(L.rStart.p, 0, ((size_t)c->nOwners + 1) * 4, st));
+        }
+        hipLaunchKernelGGL(k_owner_ranges_tile, dim3(grid_for(c->nOwners)), dim3(256), 0, st, c->dp, ow, L.aStart.as<uint32_t>(),
+                           L.lOff.as<uint16_t>(), L.rStart.as<uint32_t>(), L.heavy.as<uint8_t>(), L.fixedFlag.as<uint8_t>(),
+                           L.heavyList.as<uint32_t>(), (uint32_t)(L.heavyList.bytes / 4), L.rangeCtr.as<RangeCounters>());
+        tiled = true;
+        // closed tiles (deme_tile_step.h): the contacts that hold a tile's owners as B from other tiles, in the tile's frame
+        // (never for a context with asynchronous detection on: the closed-tile structures exist once -- see deme_ctx)
+        static const int fusedEnv = getenv("DEME_FUSED") ? atoi(getenv("DEME_FUSED")) : -1;  // (1 / 0 override the context's switch)
+        const int fusedMode = fusedEnv < 0 ? c->fusedEnable : fusedEnv;  // 0 off, 1 on, 2 by the size of the bed
+        if ((fusedMode == 2 ? c->nOwners <= DEME_FUSED_AUTO_MAX_OWNERS : fusedMode != 0) && hr.nBig == 0 && c->hp.forceModel != DEME_FORCE_CUSTOM && !c->record && c->nTri == 0 &&
+            !c->hasGhosts && !c->prescFn && !c->rulesFn && c->hShared.empty() && c->asyncLead == 0 &&
+            !c->ad.autoBinSize && !c->ad.autoUpdateFreq) {
+            hipLaunchKernelGGL(k_in_count, dim3(grid_for((size_t)c->nOwners + 1)), dim3(256), 0, st, c->dp, ow,
+                               L.rStart.as<uint32_t>(), c->inCnt.as<uint32_t>());
+            if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+                    return rocprim::exclusive_scan(tmp, bytes, c->inCnt.as<uint32_t>(), c->inStart.as<uint32_t>(), 0u, (size_t)c->nOwners + 1,
+                                                   rocprim::plus<uint32_t>(), st);
+                }))
+                return rc;
+            hipLaunchKernelGGL(k_tile_incoming, dim3(nTiles), dim3(256), 0, st, c->dp, c->nOwners, L.info.as<uint4>(),
+                               L.rStart.as<uint32_t>(), L.rIdx.as<uint32_t>(), c->recContact.as<uint32_t>(), c->inStart.as<uint32_t>(),
+                               L.hList.as<uint32_t>(), L.hCount.as<uint32_t>(), c->hCountIn.as<uint32_t>(), c->tInfoIn.as<uint2>(),
+                               c->inContact.as<uint32_t>(), L.rangeCtr.as<RangeCounters>());
+            L.fusedList = true;  // (whether every closed tile fits comes back with the counters below: fused_ready)
+        }
+    }
+    if (tiled) {  // (hr holds the tile extremes already; nSA / nSM are not used by the tile path)
+        if (!c->hrPinned) {
+            HIPCK(hipHostMalloc((void**)&c->hrPinned, sizeof(RangeCounters), hipHostMallocDefault));
+            HIPCK(hipEventCreateWithFlags(&c->hrEvent, hipEventDisableTiming));
+        }
+        HIPCK(hipMemcpyAsync(c->hrPinned, L.rangeCtr.p, sizeof(RangeCounters), hipMemcpyDeviceToHost, st));
+        HIPCK(hipEventRecord(c->hrEvent, st));
+        L.hrPending = true;
+    } else {
+        if (int rc = build_legacy_lists(c, L, ow, st))
+            return rc;
+        if (int rc = read_legacy_counts(c, L, st, hr))
+            return rc;
+    }
+    L.tileActive = tiled;
+    L.tileMaxHalo = hr.tileMaxHalo, L.tileMaxList = hr.tileMaxList;
+    L.nSA = hr.nSA;
+    L.nSM = hr.nSM;
+    // ---- the list is built: the context turns to it
+    c->fusedPrevValid = false;  // (a replay of the last fused step would read the list it was taken with)
+    if (tiled && c->orderEligible) {  // has the bed drifted away from the order it was given?  (order_renew at the next detection)
+        const uint32_t fit = std::max(1u, nTiles - std::min(nTiles, hr.nBig));
+        const uint32_t mean16 = (uint32_t)(16ull * hr.tileHaloSum / fit);
+        if (!c->orderBaseHalo) {
+            c->orderBaseHalo = std::max(mean16, 16u);
+            c->orderDetAt = c->nDetections;
+        } else if (c->nDetections - c->orderDetAt >= 20 && nTiles > 4 &&
+                   (hr.nBig > std::max(4u, nTiles / 64u) || mean16 > c->orderBaseHalo + c->orderBaseHalo / 2)) {
+            c->orderRenewDue = true;
+        }
+    }
+    c->conValid = false;
+    c->nPrev = c->haveList ? c->nContacts : 0;
+    c->nContacts = nC;
+    c->keysCur = next;
+    c->listSerial++;
+    c->haveList = true;
+    c->seeded = false;
+    c->mapFresh = true;
+    c->nDetections++;
+    return DEME_OK;
 }
 
 
@@ -1036,10 +1060,11 @@ int do_detect(deme_ctx* c) {
     uint64_t nC = 0;
     if (int rc = detect_part1(c, c->stream, c->owners.as<OwnerRec>(), false, &nC))
         return rc;
-    return detect_part2(c, nC);
+    return detect_part2(c, c->list[c->cur], c->owners.as<OwnerRec>(), c->stream, nC);
 }
 
 int do_migrate(deme_ctx* c) {
+    ContactList& L = c->list[c->cur];
     const uint32_t nW = c->hp.nContactWildcards;
     if (!c->mapFresh)
         return DEME_OK;
@@ -1051,7 +1076,7 @@ int do_migrate(deme_ctx* c) {
     const int next = c->wcCur ^ 1;
     if (c->nContacts)
         hipLaunchKernelGGL(k_migrate, dim3(grid_for(c->nContacts)), dim3(256), 0, c->stream, (uint32_t)c->nContacts, nW,
-                           c->mapping.as<uint32_t>(), (uint32_t)c->nWcStored, c->wc[c->wcCur].as<float>(),
+                           L.mapping.as<uint32_t>(), (uint32_t)c->nWcStored, c->wc[c->wcCur].as<float>(),
                            c->wc[next].as<float>());
     c->wcCur = next;
     c->nWcStored = c->nContacts;
@@ -1059,9 +1084,10 @@ int do_migrate(deme_ctx* c) {
 }
 
 GatherArgs gather_args(deme_ctx* c) {
+    ContactList& L = c->list[c->cur];
     GatherArgs g{};
-    g.aStart = c->aStart.as<uint32_t>(), g.bStart = c->bStart.as<uint32_t>(), g.bIdx = c->bIdx[1].as<uint32_t>();
-    g.heavy = c->heavy.as<uint8_t>();
+    g.aStart = L.aStart.as<uint32_t>(), g.bStart = L.bStart.as<uint32_t>(), g.bIdx = L.bIdx[1].as<uint32_t>();
+    g.heavy = L.heavy.as<uint8_t>();
     g.conA4 = c->conA4.as<float4>(), g.conA2 = c->conA2.as<float2>();
     g.conB4 = c->conB4.as<float4>(), g.conB2 = c->conB2.as<float2>();
     g.aSum = c->aSum.as<float4>();
@@ -1070,7 +1096,7 @@ GatherArgs gather_args(deme_ctx* c) {
         g.revSlot = c->revSlot.as<uint32_t>(), g.revAcc = (const float4*)c->revAcc;
     g.world = c->arith == DEME_ARITH_FAST ? 1u : 0u;
     if (c->conTile) {  // the tile kernel's sums and its records of tile-crossing contacts
-        g.bStart = c->rStart.as<uint32_t>(), g.bIdx = c->rIdx.as<uint32_t>();
+        g.bStart = L.rStart.as<uint32_t>(), g.bIdx = L.rIdx.as<uint32_t>();
         g.rec32 = c->rec32.as<float4>();
         g.tile = 1u;
     }
@@ -1078,37 +1104,38 @@ GatherArgs gather_args(deme_ctx* c) {
 }
 
 // heavy owners: skipFixed=true in the stepping loop (a fixed owner's a/alpha are only needed by queries)
-void resolve_heavy_counts(deme_ctx* c) {
-    if (!c->hrPending)
+void resolve_heavy_counts(deme_ctx* c, ContactList& L) {
+    if (!L.hrPending)
         return;
-    c->hrPending = false;
+    L.hrPending = false;
     if (const hipError_t e = hipEventSynchronize(c->hrEvent); e != hipSuccess) {
         fail(c, DEME_ERR_HIP, "waiting for the heavy-owner counts: %s", hipGetErrorString(e));
-        c->heavyOverflow = true;  // (the stepping loop returns the error: launch_integrate)
+        L.heavyOverflow = true;  // (the stepping loop returns the error: launch_integrate)
         return;
     }
-    const size_t cap = c->heavyList.bytes / 4;
-    c->nHeavy = c->hrPinned->nHeavy, c->nHeavyFree = c->hrPinned->nHeavyFree;
-    if (c->fusedList) {  // the halos were extended by the incoming contacts' owners (k_tile_incoming): the kernels' LDS follows
-        c->tileMaxHaloIn = c->hrPinned->tileMaxHaloIn;
+    const size_t cap = L.heavyList.bytes / 4;
+    L.nHeavy = c->hrPinned->nHeavy, L.nHeavyFree = c->hrPinned->nHeavyFree;
+    if (L.fusedList) {  // the halos were extended by the incoming contacts' owners (k_tile_incoming): the kernels' LDS follows
+        L.tileMaxHaloIn = c->hrPinned->tileMaxHaloIn;
         if (c->hrPinned->nBigIn)  // a closed tile does not fit: this list keeps force pass + integrator
-            c->fusedList = false;
-        c->fusedChecked = true;
+            L.fusedList = false;
+        L.fusedChecked = true;
     }
-    if (c->nHeavy > cap) {
-        fail(c, DEME_ERR_OVERFLOW, "%u owners exceed the heavy-owner list", c->nHeavy);
-        c->nHeavy = (uint32_t)cap;
-        c->heavyOverflow = true;  // (the stepping loop returns the error)
+    if (L.nHeavy > cap) {
+        fail(c, DEME_ERR_OVERFLOW, "%u owners exceed the heavy-owner list", L.nHeavy);
+        L.nHeavy = (uint32_t)cap;
+        L.heavyOverflow = true;  // (the stepping loop returns the error)
     }
 }
 
 void launch_reduce_heavy(deme_ctx* c, bool skipFixed) {
-    resolve_heavy_counts(c);
-    if (c->nHeavy == 0 || (skipFixed && c->nHeavyFree == 0))
+    ContactList& L = c->list[c->cur];
+    resolve_heavy_counts(c, L);
+    if (L.nHeavy == 0 || (skipFixed && L.nHeavyFree == 0))
         return;
-    hipLaunchKernelGGL(k_reduce_heavy, dim3(std::min<uint32_t>(c->nHeavy, 1024)), dim3(256), 0, c->stream, c->dp, gather_args(c),
-                       c->owners.as<OwnerRec>(), c->heavyList.as<uint32_t>(), &c->rangeCtr.as<RangeCounters>()->nHeavy,
-                       skipFixed ? c->fixedFlag.as<uint8_t>() : (const uint8_t*)nullptr, c->acc.as<AccRec>());
+    hipLaunchKernelGGL(k_reduce_heavy, dim3(std::min<uint32_t>(L.nHeavy, 1024)), dim3(256), 0, c->stream, c->dp, gather_args(c),
+                       c->owners.as<OwnerRec>(), L.heavyList.as<uint32_t>(), &L.rangeCtr.as<RangeCounters>()->nHeavy,
+                       skipFixed ? L.fixedFlag.as<uint8_t>() : (const uint8_t*)nullptr, c->acc.as<AccRec>());
 }
 
 // the stride of the staged owner records of a tile launch (TileArgs::rs16): padded by 16 bytes when that costs no workgroup per CU
@@ -1122,6 +1149,7 @@ static uint32_t tile_record_stride(uint32_t hCap, uint32_t lCap, uint32_t tabByt
 }
 // pass: -1 everything in one launch; 0 / 1 the two halves of a split step (contacts that read no ghost owner / the rest)
 int launch_forces(deme_ctx* c, int pass = -1) {
+    ContactList& L = c->list[c->cur];
     c->fusedPrevValid = false;
     if (c->nContacts == 0) {
         c->conValid = true;
@@ -1134,23 +1162,23 @@ int launch_forces(deme_ctx* c, int pass = -1) {
     a.owners = c->owners.as<OwnerRec>();
     a.spheres = c->spheres.as<SphereRec>();
     a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
-    a.info = c->info.as<uint4>();
+    a.info = L.info.as<uint4>();
     a.wc = c->wc[c->wcCur].as<float>();
     a.conA4 = c->conA4.as<float4>(), a.conA2 = c->conA2.as<float2>();
     a.conB4 = c->conB4.as<float4>(), a.conB2 = c->conB2.as<float2>();
     a.aSum = c->aSum.as<float4>();
-    a.aStart = c->aStart.as<uint32_t>();
-    a.smList = c->smList.as<uint32_t>();
-    a.nSM = c->nSM;
+    a.aStart = L.aStart.as<uint32_t>();
+    a.smList = L.smList.as<uint32_t>();
+    a.nSM = L.nSM;
     for (int k = 0; k < 8; k++) {
         a.ownerWc[k] = c->userWc[0][k].as<float>();
         a.geoWcSph[k] = c->userWc[1][k].as<float>();
         a.geoWcTri[k] = c->userWc[2][k].as<float>();
         a.geoWcAnal[k] = c->userWc[3][k].as<float>();
     }
-    if (pass >= 0 && c->hasGhosts && c->cDefer.p) {
-        a.cDefer = c->cDefer.as<uint8_t>();
-        a.blockMode = c->blockMode.as<uint32_t>();
+    if (pass >= 0 && c->hasGhosts && L.cDefer.p) {
+        a.cDefer = L.cDefer.as<uint8_t>();
+        a.blockMode = L.blockMode.as<uint32_t>();
         a.pass = (uint32_t)pass;
     }
     a.nContacts = (uint32_t)c->nContacts;
@@ -1164,22 +1192,22 @@ int launch_forces(deme_ctx* c, int pass = -1) {
     // through the general kernel
     const bool fastKernel = fastMode && c->hp.forceModel != DEME_FORCE_CUSTOM;
     const bool customTile = fastMode && !c->record && c->hp.forceModel == DEME_FORCE_CUSTOM && c->customTileFn[0];
-    if ((fastKernel || customTile) && c->tileActive) {  // owner tiles: deme_tile.h
-        if (c->fusedList && !c->fusedChecked)
-            resolve_heavy_counts(c);
+    if ((fastKernel || customTile) && L.tileActive) {  // owner tiles: deme_tile.h
+        if (L.fusedList && !L.fusedChecked)
+            resolve_heavy_counts(c, L);
         TileArgs ta{};
         ta.owners = a.owners;
-        ta.tInfo = c->tInfo.as<uint2>();
+        ta.tInfo = L.tInfo.as<uint2>();
         ta.aStart = a.aStart;
-        ta.hList = c->hList.as<uint32_t>(), ta.hCount = c->hCount.as<uint32_t>(), ta.org = c->tileOrg.as<int64_t>();
-        ta.lOff = c->lOff.as<uint16_t>(), ta.lPos = c->lPos.as<uint16_t>(), ta.lCount = c->lCount.as<uint32_t>();
+        ta.hList = L.hList.as<uint32_t>(), ta.hCount = L.hCount.as<uint32_t>(), ta.org = L.tileOrg.as<int64_t>();
+        ta.lOff = L.lOff.as<uint16_t>(), ta.lPos = L.lPos.as<uint16_t>(), ta.lCount = L.lCount.as<uint32_t>();
         ta.wc = a.wc;
         ta.tSum = a.aSum;
-        ta.rec32 = c->rec32.as<float4>(), ta.rankC = c->rankC.as<uint32_t>();
+        ta.rec32 = c->rec32.as<float4>(), ta.rankC = L.rankC.as<uint32_t>();
         ta.nOwners = c->nOwners;
         ta.nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
         ta.xcdGroup = c->xcdGroup;
-        ta.tileBig = c->tileBig.as<uint32_t>(), ta.bigList = c->bigList.as<uint32_t>(), ta.info = a.info;
+        ta.tileBig = L.tileBig.as<uint32_t>(), ta.bigList = L.bigList.as<uint32_t>(), ta.info = a.info;
         ta.keys = a.keys, ta.timeElapsed = a.timeElapsed;
         if (c->record) {
             for (int k = 0; k < 4; k++)
@@ -1190,27 +1218,27 @@ int launch_forces(deme_ctx* c, int pass = -1) {
         for (int k = 0; k < 8; k++)
             ta.ownerWc[k] = a.ownerWc[k], ta.geoWcSph[k] = a.geoWcSph[k], ta.geoWcAnal[k] = a.geoWcAnal[k];
         if (pass >= 0 && c->hasGhosts) {
-            ta.tileMode = c->tileMode.as<uint32_t>();
+            ta.tileMode = L.tileMode.as<uint32_t>();
             ta.pass = (uint32_t)pass;
         }
         unsigned nBlk = ta.nTiles;
         if (ta.xcdGroup)
             nBlk = (nBlk + 8u * ta.xcdGroup - 1u) / (8u * ta.xcdGroup) * (8u * ta.xcdGroup);
         // LDS sized from this list's largest tile (rounded up so that a launch configuration serves many detections)
-        ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (c->tileMaxHalo + 15u) & ~15u);
-        ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (c->tileMaxList + 15u) & ~15u);
+        ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (L.tileMaxHalo + 15u) & ~15u);
+        ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (L.tileMaxList + 15u) & ~15u);
         ta.nComp = c->nComp, ta.nAnal = c->nAnal, ta.nMass = c->nMassProps;
         const uint32_t tabBytes = tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial);
         ta.rs16 = tile_record_stride(ta.hCap, ta.lCap, tabBytes, customTile ? 2 : 0);
         ta.swz = (!customTile && ta.rs16 == tile_rec16(0)) ? 1u : 0u;
         const uint32_t ldsBytes = tile_lds_bytes(ta.hCap, ta.lCap, tabBytes, ta.rs16);
         ScopedTimer tm(c, "calc_forces");
-        const bool mesh = c->nTri > 0 && c->nSM > 0;
+        const bool mesh = c->nTri > 0 && L.nSM > 0;
         if (mesh) {
             ta.conA4 = a.conA4, ta.conA2 = a.conA2, ta.conB4 = a.conB4, ta.conB2 = a.conB2;
             if (pass != 1) {  // sphere-triangle contacts: the mesh variant of the general kernel, before the tiles that read its records
                               // (they read no ghost owner -- meshes are replicated, not ghosted --: all of them go with pass 0)
-                const dim3 gm(grid_for(std::max<uint32_t>(c->nSM, 1u), DEME_FORCE_BLOCK)), bm(DEME_FORCE_BLOCK);
+                const dim3 gm(grid_for(std::max<uint32_t>(L.nSM, 1u), DEME_FORCE_BLOCK)), bm(DEME_FORCE_BLOCK);
                 if (customTile) {
                     void* args0[] = {&c->dp, &a};
                     HIPCK(hipModuleLaunchKernel(c->customFn[1], gm.x, 1, 1, DEME_FORCE_BLOCK, 1, 1, 0, c->stream, args0, nullptr));
@@ -1220,7 +1248,7 @@ int launch_forces(deme_ctx* c, int pass = -1) {
                     hipLaunchKernelGGL((k_calc_forces<1, 1>), gm, bm, 0, c->stream, c->dp, a);
             }
         }
-        const unsigned nBig = c->nBigTiles;  // tiles that do not fit LDS: one workgroup each, the same outputs (deme_tile.h)
+        const unsigned nBig = L.nBigTiles;  // tiles that do not fit LDS: one workgroup each, the same outputs (deme_tile.h)
         if (customTile) {  // the same kernels compiled at run time around the user's statements (deme_jit.h)
             void* argsT[] = {&c->dp, &ta};
             HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 1 : 0], nBlk, 1, 1, DEME_TILE_T, 1, 1, ldsBytes, c->stream, argsT, nullptr));
@@ -1265,8 +1293,8 @@ int launch_forces(deme_ctx* c, int pass = -1) {
             nBlk = (nBlk + 8u * a.xcdGroup - 1u) / (8u * a.xcdGroup) * (8u * a.xcdGroup);
         const dim3 g(nBlk), b(DEME_FORCE_BLOCK);
         // sphere-mesh contacts read no ghost owner (meshes are replicated, not ghosted): all of them go with pass 0
-        const bool hasSM = c->nTri > 0 && c->nSM > 0 && pass != 1;
-        const dim3 gm(grid_for(std::max<uint32_t>(c->nSM, 1u), DEME_FORCE_BLOCK));
+        const bool hasSM = c->nTri > 0 && L.nSM > 0 && pass != 1;
+        const dim3 gm(grid_for(std::max<uint32_t>(L.nSM, 1u), DEME_FORCE_BLOCK));
         if (c->hp.forceModel == DEME_FORCE_HERTZIAN) {
             if (hasSM)  // mesh variant first: the hot variant folds its A-side records into the in-block sums
                 hipLaunchKernelGGL((k_calc_forces<0, 1>), gm, b, 0, c->stream, c->dp, a);
@@ -1297,29 +1325,31 @@ int launch_forces(deme_ctx* c, int pass = -1) {
 // The whole step in one launch (deme_tile_step.h).  dry: replay the force evaluation of the step just taken on the buffers of its
 // start and leave a / alpha (state downloads).
 bool fused_ready(deme_ctx* c) {
-    if (!c->fusedList || !c->tileActive || c->arith != DEME_ARITH_FAST || c->record || c->hp.forceModel == DEME_FORCE_CUSTOM ||
+    ContactList& L = c->list[c->cur];
+    if (!L.fusedList || !L.tileActive || c->arith != DEME_ARITH_FAST || c->record || c->hp.forceModel == DEME_FORCE_CUSTOM ||
         c->prescFn || c->rulesFn || c->nContacts == 0)
         return false;
-    if (!c->fusedChecked)
-        resolve_heavy_counts(c);
-    return c->fusedList && c->nHeavyFree == 0;
+    if (!L.fusedChecked)
+        resolve_heavy_counts(c, L);
+    return L.fusedList && L.nHeavyFree == 0;
 }
 int launch_fused_step(deme_ctx* c, bool dry) {
+    ContactList& L = c->list[c->cur];
     StepArgs sa{};
     TileArgs& ta = sa.t;
     const int cur = dry ? (c->wcCur ^ 1) : c->wcCur;  // (dry: the step is over, the names are swapped already)
     ta.owners = dry ? c->ownersNext.as<OwnerRec>() : c->owners.as<OwnerRec>();
-    ta.tInfo = c->tInfo.as<uint2>();
-    ta.aStart = c->aStart.as<uint32_t>();
-    ta.hList = c->hList.as<uint32_t>(), ta.hCount = c->hCountIn.as<uint32_t>(), ta.org = c->tileOrg.as<int64_t>();
-    ta.lOff = c->lOff.as<uint16_t>(), ta.lPos = c->lPos.as<uint16_t>(), ta.lCount = c->lCount.as<uint32_t>();
+    ta.tInfo = L.tInfo.as<uint2>();
+    ta.aStart = L.aStart.as<uint32_t>();
+    ta.hList = L.hList.as<uint32_t>(), ta.hCount = c->hCountIn.as<uint32_t>(), ta.org = L.tileOrg.as<int64_t>();
+    ta.lOff = L.lOff.as<uint16_t>(), ta.lPos = L.lPos.as<uint16_t>(), ta.lCount = L.lCount.as<uint32_t>();
     ta.wc = c->wc[cur].as<float>();
     ta.nOwners = c->nOwners;
     ta.nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
     ta.xcdGroup = c->xcdGroup;
-    ta.tileBig = c->tileBig.as<uint32_t>(), ta.bigList = c->bigList.as<uint32_t>(), ta.info = c->info.as<uint4>();
-    ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (c->tileMaxHaloIn + 15u) & ~15u);
-    ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (c->tileMaxList + 15u) & ~15u);
+    ta.tileBig = L.tileBig.as<uint32_t>(), ta.bigList = L.bigList.as<uint32_t>(), ta.info = L.info.as<uint4>();
+    ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (L.tileMaxHaloIn + 15u) & ~15u);
+    ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (L.tileMaxList + 15u) & ~15u);
     ta.nComp = c->nComp, ta.nAnal = c->nAnal, ta.nMass = c->nMassProps;
     sa.ownersNext = dry ? c->owners.as<OwnerRec>() : c->ownersNext.as<OwnerRec>();
     sa.wcNext = c->wc[cur ^ 1].as<float>();
@@ -1399,6 +1429,7 @@ int rebuild_presc_list(deme_ctx* c) {
 // `laterIds` (slab group, one evaluation per cross-cut contact): the owners that wait for a reverse share are left out of this launch
 // (GatherArgs::revPhase) and integrated by launch_integrate_later once the share has arrived
 int launch_integrate(deme_ctx* c, bool fused, bool heavyDone = false, bool splitLater = false) {
+    ContactList& L = c->list[c->cur];
     ScopedTimer tm(c, "integrate");
     PrescArgs pa{nullptr, nullptr};
     if (c->prescFn) {
@@ -1420,7 +1451,7 @@ int launch_integrate(deme_ctx* c, bool fused, bool heavyDone = false, bool split
     if (fused) {
         if (!heavyDone)
             launch_reduce_heavy(c, true);
-        if (c->heavyOverflow)
+        if (L.heavyOverflow)
             return c->lastStatus;
         GatherArgs ga = gather_args(c);
         ga.revPhase = splitLater ? 1u : 0u;
@@ -1531,9 +1562,10 @@ void deme_ctx_destroy(deme_ctx* c) {
     }
     if (c->pin)
         hipHostFree(c->pin);
-    for (DevBuf& b : c->spare)
-        if (b.p)
-            hipFree(b.p);
+    for (ContactList& l : c->list)
+        for (DevBuf* b : l.buffers())
+            if (b->p)
+                hipFree(b->p);
     if (c->hrPinned) {
         hipHostFree(c->hrPinned);
         hipEventDestroy(c->hrEvent);
@@ -1544,13 +1576,17 @@ void deme_ctx_destroy(deme_ctx* c) {
         hipEventDestroy(c->evP1);
         hipStreamDestroy(c->detStream);
     }
-    DevBuf* all[] = {&c->hCountIn, &c->ownersNext, &c->recContact, &c->inCnt, &c->inStart, &c->tInfoIn, &c->inContact, &c->sphFam, &c->tileBig, &c->bigList, &c->dO2E, &c->dS2E, &c->segCtr, &c->tInfo, &c->hList, &c->hCount, &c->tileMode, &c->tileOrg, &c->rIdx, &c->rStart, &c->remKey[0], &c->remKey[1], &c->lPos, &c->lOff, &c->lCount, &c->tileRem, &c->tileBase, &c->remVal, &c->rankC, &c->rec32, &c->revSlot, &c->nextAcc, &c->binStat, &c->volumes, &c->persistKeys, &c->owners, &c->spheres, &c->acc, &c->conA4, &c->conA2, &c->conB4, &c->conB2, &c->aSum, &c->prescList, &c->prescSlot, &c->prescRec, &c->smFlag, &c->smList, &c->cDefer, &c->blockMode, &c->ownerA, &c->ownerB[0], &c->ownerB[1], &c->bIdx[0], &c->bIdx[1], &c->aStart, &c->bStart, &c->heavy, &c->fixedFlag, &c->heavyList, &c->rangeCtr, &c->info, &c->tris, &c->triWorld, &c->triLo, &c->triHi, &c->triCounts, &c->triOffsets, &c->triKeys[0], &c->triKeys[1], &c->triVals[0], &c->triVals[1], &c->comp, &c->massProps, &c->anal, &c->matPair,
-                     &c->E, &c->nu, &c->CoR, &c->mu, &c->Crr, &c->famMasks, &c->famExtra, &c->famFlags, &c->geo,
-                     &c->binLo, &c->binN, &c->counts, &c->offsets, &c->incKeys[0], &c->incKeys[1], &c->incVals[0],
-                     &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->mapping, &c->wc[0],
-                     &c->wc[1], &c->ctr, &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3],
-                     &c->stage, &c->sharedIds, &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1],
-                     &c->rsRuns, &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap};
+    DevBuf* all[] = {&c->hCountIn, &c->ownersNext, &c->recContact, &c->inCnt, &c->inStart, &c->tInfoIn, &c->inContact,
+                     &c->sphFam, &c->dO2E, &c->dS2E, &c->segCtr, &c->rec32, &c->revSlot, &c->nextAcc, &c->binStat, &c->volumes,
+                     &c->persistKeys, &c->owners, &c->spheres, &c->acc, &c->conA4, &c->conA2, &c->conB4, &c->conB2, &c->aSum,
+                     &c->prescList, &c->prescSlot, &c->prescRec, &c->tris, &c->triWorld, &c->triLo, &c->triHi, &c->triCounts,
+                     &c->triOffsets, &c->triKeys[0], &c->triKeys[1], &c->triVals[0], &c->triVals[1], &c->comp, &c->massProps,
+                     &c->anal, &c->matPair, &c->E, &c->nu, &c->CoR, &c->mu, &c->Crr, &c->famMasks, &c->famExtra, &c->famFlags,
+                     &c->geo, &c->binLo, &c->binN, &c->counts, &c->offsets, &c->incKeys[0], &c->incKeys[1], &c->incVals[0],
+                     &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->wc[0], &c->wc[1], &c->ctr,
+                     &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
+                     &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
+                     &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -1609,33 +1645,35 @@ int deme_get_arith_mode(const deme_ctx* c) { return c ? c->arith : -1; }
 int deme_force_kernel_name(const deme_ctx* c, char* name, size_t cap, uint32_t* tileMaxHalo, uint32_t* tileMaxList) {
     if (!c || !name || !cap)
         return DEME_ERR_INVALID;
+    const ContactList& L = c->list[c->cur];
     const int m = c->hp.forceModel == DEME_FORCE_HERTZIAN ? 0 : 1;
     const bool fastKernel = c->arith == DEME_ARITH_FAST && c->hp.forceModel != DEME_FORCE_CUSTOM;
-    if (c->fusedPrevValid && c->fusedList && c->tileActive)  // the last step went through the one-kernel step (deme_tile_step.h)
+    if (c->fusedPrevValid && L.fusedList && L.tileActive)  // the last step went through the one-kernel step (deme_tile_step.h)
         snprintf(name, cap, "k_tile_step<%d>", m);
-    else if (c->hp.forceModel == DEME_FORCE_CUSTOM && c->arith == DEME_ARITH_FAST && !c->record && c->customTileFn[0] && c->tileActive)
-        snprintf(name, cap, "deme_custom_tile<%s>", (c->nTri > 0 && c->nSM > 0) ? "true" : "false");
+    else if (c->hp.forceModel == DEME_FORCE_CUSTOM && c->arith == DEME_ARITH_FAST && !c->record && c->customTileFn[0] && L.tileActive)
+        snprintf(name, cap, "deme_custom_tile<%s>", (c->nTri > 0 && L.nSM > 0) ? "true" : "false");
     else if (c->hp.forceModel == DEME_FORCE_CUSTOM)
         snprintf(name, cap, "deme_custom_forces_ss");
-    else if (fastKernel && c->tileActive)
-        snprintf(name, cap, "k_tile_forces<%d, %s>", m, (c->nTri > 0 && c->nSM > 0) ? "true" : "false");
+    else if (fastKernel && L.tileActive)
+        snprintf(name, cap, "k_tile_forces<%d, %s>", m, (c->nTri > 0 && L.nSM > 0) ? "true" : "false");
     else if (fastKernel && !c->record)
         snprintf(name, cap, "k_forces_fast<%d>", m);
     else
         snprintf(name, cap, "k_calc_forces<%d, 0>", m);
     if (tileMaxHalo)
-        *tileMaxHalo = c->tileMaxHalo;
+        *tileMaxHalo = L.tileMaxHalo;
     if (tileMaxList)
-        *tileMaxList = c->tileMaxList;
+        *tileMaxList = L.tileMaxList;
     return DEME_OK;
 }
 
 int deme_tile_stats(const deme_ctx* c, uint32_t out[4]) {
     if (!c || !out)
         return DEME_ERR_INVALID;
-    out[0] = c->tileActive ? (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB : 0u;
-    out[1] = c->tileActive ? c->nBigTiles : 0u;
-    out[2] = c->tileMaxHalo, out[3] = c->tileMaxList;
+    const ContactList& L = c->list[c->cur];
+    out[0] = L.tileActive ? (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB : 0u;
+    out[1] = L.tileActive ? L.nBigTiles : 0u;
+    out[2] = L.tileMaxHalo, out[3] = L.tileMaxList;
     return DEME_OK;
 }
 int deme_set_tile_policy(deme_ctx* c, uint32_t minContactsPerTileCustom) {
@@ -1727,24 +1765,21 @@ static int owner_scratch_for_counts(deme_ctx* c, size_t nO) {
         return rc;
     if (ensure(c, c->ownersNext, std::max<size_t>(nO, 1) * sizeof(OwnerRec)) || ensure(c, c->inCnt, (nO + 2) * 4) || ensure(c, c->inStart, (nO + 2) * 4))
         return c->lastStatus;
-    c->fusedList = c->fusedPrevValid = false;
     HIPCK(hipMemsetAsync(c->acc.p, 0, c->acc.bytes, c->stream));
-    if (ensure(c, c->aStart, (nO + 1) * 4) || ensure(c, c->aSum, (nO + 1) * 32) || ensure(c, c->bStart, (nO + 1) * 4) || ensure(c, c->heavy, nO + 1) ||
-        ensure(c, c->fixedFlag, nO + 1) || ensure(c, c->heavyList, 4096 * 4) || ensure(c, c->rangeCtr, sizeof(RangeCounters)))
-        return c->lastStatus;
+    ContactList& L = c->list[c->cur];
     const size_t nTiles = (nO + DEME_TILE_NB - 1) / DEME_TILE_NB + 1;
-    if (ensure(c, c->hList, nTiles * DEME_TILE_HMAX * 4) || ensure(c, c->hCount, nTiles * 4) || ensure(c, c->hCountIn, nTiles * 4) ||
-        ensure(c, c->tileMode, nTiles * 4) || ensure(c, c->tileOrg, nTiles * 24) || ensure(c, c->rStart, (nO + 1) * 4) ||
-        ensure(c, c->lOff, nTiles * (DEME_TILE_NB + 1) * 2) || ensure(c, c->lCount, nTiles * 4) || ensure(c, c->tileRem, (nTiles + 1) * 4) ||
-        ensure(c, c->tileBase, (nTiles + 1) * 4) || ensure(c, c->tileBig, nTiles * 4) || ensure(c, c->bigList, nTiles * 4))
+    if (ensure(c, c->aSum, (nO + 1) * 32) || ensure(c, c->hCountIn, nTiles * 4))
         return c->lastStatus;
-    HIPCK(hipMemsetAsync(c->hCount.p, 0, c->hCount.bytes, c->stream));
-    c->tileActive = c->conTile = false;
-    HIPCK(hipMemsetAsync(c->aStart.p, 0, c->aStart.bytes, c->stream));
-    HIPCK(hipMemsetAsync(c->bStart.p, 0, c->bStart.bytes, c->stream));
-    HIPCK(hipMemsetAsync(c->heavy.p, 0, c->heavy.bytes, c->stream));
-    HIPCK(hipMemsetAsync(c->fixedFlag.p, 0, c->fixedFlag.bytes, c->stream));
-    HIPCK(hipMemsetAsync(c->rangeCtr.p, 0, sizeof(RangeCounters), c->stream));
+    if (int rc = size_list_per_owner(c, L, nO))
+        return rc;
+    L.invalidate();  // (what it holds was built for the old owners)
+    c->fusedPrevValid = c->conTile = false;
+    HIPCK(hipMemsetAsync(L.hCount.p, 0, L.hCount.bytes, c->stream));
+    HIPCK(hipMemsetAsync(L.aStart.p, 0, L.aStart.bytes, c->stream));
+    HIPCK(hipMemsetAsync(L.bStart.p, 0, L.bStart.bytes, c->stream));
+    HIPCK(hipMemsetAsync(L.heavy.p, 0, L.heavy.bytes, c->stream));
+    HIPCK(hipMemsetAsync(L.fixedFlag.p, 0, L.fixedFlag.bytes, c->stream));
+    HIPCK(hipMemsetAsync(L.rangeCtr.p, 0, sizeof(RangeCounters), c->stream));
     return DEME_OK;
 }
 static int sphere_scratch_for_counts(deme_ctx* c, size_t nS) {
@@ -1807,8 +1842,6 @@ int deme_upload_scene(deme_ctx* c, const DemeScene* s) {
         return rc;
     if (int rc = owner_scratch_for_counts(c, nO))
         return rc;
-    c->nHeavy = c->nHeavyFree = 0;
-    c->hrPending = false;
     c->conValid = false;
     // spheres
     std::vector<SphereRec> hs(nS);
@@ -2329,28 +2362,12 @@ static int async_part1(deme_ctx* c, uint64_t* nC) {
     HIPCK(hipEventRecord(c->evP1, c->detStream));
     return DEME_OK;
 }
-// Everything detect_part2 / build_legacy_lists write and the stepping kernels read.  While the D steps of an asynchronous cycle are
-// in flight (they were enqueued with the current buffers' addresses) the names are swapped to a second set, which part 2 fills on
-// the detection stream; when the main stream has waited for it, the names already point at the new list.
-static std::vector<DevBuf*> list_set(deme_ctx* c) {
-    return {&c->mapping, &c->rangeCtr, &c->tileRem, &c->ownerA, &c->ownerB[0], &c->ownerB[1], &c->bIdx[0], &c->bIdx[1], &c->info,
-            &c->smFlag, &c->smList, &c->aStart, &c->bStart, &c->tileBase, &c->tInfo, &c->hList, &c->hCount, &c->tileMode, &c->lOff,
-            &c->lPos, &c->lCount, &c->rankC, &c->remKey[0], &c->remKey[1], &c->remVal, &c->tileOrg, &c->rIdx, &c->rStart, &c->heavy,
-            &c->fixedFlag, &c->heavyList, &c->cDefer, &c->blockMode, &c->tileBig, &c->bigList};
-}
-// the second set at the sizes of the one in use (sized by the arenas / the scene); nothing in flight reads the spare set
-static int async_size_spare(deme_ctx* c) {
-    const std::vector<DevBuf*> set = list_set(c);
-    static_assert(sizeof(c->spare) / sizeof(c->spare[0]) >= 33, "spare set too small");
-    for (size_t k = 0; k < set.size(); k++)
-        if (c->spare[k].bytes < set[k]->bytes) {
-            if (c->spare[k].p)
-                HIPCK(hipFree(c->spare[k].p));
-            c->spare[k].p = nullptr, c->spare[k].bytes = 0;
-            HIPCK(hipMalloc(&c->spare[k].p, set[k]->bytes));
-            c->spare[k].bytes = set[k]->bytes;
-        }
-    return DEME_OK;
+// the list an asynchronous detection builds, at the sizes of the arenas and the scene; nothing in flight reads it
+static int async_size_next(deme_ctx* c) {
+    ContactList& N = c->list[c->cur ^ 1];
+    if (int rc = size_list_per_contact(c, N, c->cntCap, c->hasGhosts, c->nTri))
+        return rc;
+    return size_list_per_owner(c, N, c->nOwners);
 }
 // streams, events and buffers of the asynchronous detection, made when it is switched on (a first cycle that allocates a
 // gigabyte of list structures inside a short timed run costs more than the detection it hides)
@@ -2366,39 +2383,27 @@ static int async_prepare(deme_ctx* c) {
         return rc;
     if (int rc = ensure(c, c->keysMid, (size_t)c->cntCap * 8))
         return rc;
-    return async_size_spare(c);
+    return async_size_next(c);
 }
+// Part 2 beside the steps: every step that reads the current list has been enqueued, the other list is built on the detection
+// stream from the snapshot, and the index flips once that has succeeded.  A failure leaves the current list -- buffers and
+// description alike -- as the steps know it.
 static int async_part2(deme_ctx* c, uint64_t nC) {
-    // (every step that reads the current list has been enqueued: from here on the names belong to the list being built)
-    const std::vector<DevBuf*> set = list_set(c);
-    hipStream_t mainStream = c->stream;
-    if (int rc = async_size_spare(c))
+    ContactList& N = c->list[c->cur ^ 1];
+    if (int rc = async_size_next(c))
         return rc;
-    for (size_t k = 0; k < set.size(); k++)
-        std::swap(*set[k], c->spare[k]);
-    c->stream = c->detStream;
-    c->listOwnersSnap = true;
-    int rc = DEME_OK;
     {
-        ScopedTimer tm(c, "detect_async_part2", true);
-        // (no early return between the swap above and the restore below: a failed call must not leave the context launching on
-        // the detection stream)
-        hipError_t e = hipMemsetAsync(c->heavy.p, 0, c->heavy.bytes, c->stream);
-        if (e == hipSuccess)
-            e = hipMemsetAsync(c->fixedFlag.p, 0, c->fixedFlag.bytes, c->stream);
-        rc = e == hipSuccess ? detect_part2(c, nC) : fail(c, DEME_ERR_HIP, "asynchronous detection, part 2: %s", hipGetErrorString(e));
+        ScopedTimer tm(c, "detect_async_part2", true, c->detStream);
+        HIPCK(hipMemsetAsync(N.heavy.p, 0, N.heavy.bytes, c->detStream));
+        HIPCK(hipMemsetAsync(N.fixedFlag.p, 0, N.fixedFlag.bytes, c->detStream));
+        if (int rc = detect_part2(c, N, c->ownersSnap.as<OwnerRec>(), c->detStream, nC))
+            return rc;
     }
-    c->listOwnersSnap = false;
-    c->stream = mainStream;
-    if (rc) {  // the half-built set goes back to the spare slots: the names keep the list the steps are using
-        for (size_t k = 0; k < set.size(); k++)
-            std::swap(*set[k], c->spare[k]);
-        return rc;
-    }
+    c->cur ^= 1;
     HIPCK(hipEventRecord(c->evP1, c->detStream));
     HIPCK(hipStreamWaitEvent(c->stream, c->evP1, 0));
-    if (int rc2 = do_migrate(c))  // the history follows its contacts into the new order: with the wildcards the last step left
-        return rc2;
+    if (int rc = do_migrate(c))  // the history follows its contacts into the new order: with the wildcards the last step left
+        return rc;
     c->stepsSinceCD = 0;
     c->listStale = false;
     c->nAsyncDetections++;
@@ -2478,6 +2483,7 @@ static int launch_family_rules(deme_ctx* c, const AccRec* accp) {
 // separately reduced a / alpha (heavy and replicated owners), then the integration.  A slab group adds the replicated owners'
 // sums up across slabs between the two (deme_halo_group_step).
 static int step_tail_pre(deme_ctx* c) {
+    ContactList& L = c->list[c->cur];
     bool fused = true;
     if (c->rulesFn) {  // routineChecks(): applyFamilyChanges between forces and integration (dT.cpp:2437-2443)
         const AccRec* accp = nullptr;
@@ -2492,7 +2498,7 @@ static int step_tail_pre(deme_ctx* c) {
     c->tailFused = fused;
     if (fused)
         launch_reduce_heavy(c, true);
-    if (c->heavyOverflow)
+    if (L.heavyOverflow)
         return c->lastStatus;
     return DEME_OK;
 }
@@ -3417,7 +3423,7 @@ int deme_download_contacts(deme_ctx* c, uint32_t* idA, uint32_t* idB, uint8_t* t
             mapping[i] = 0xFFFFFFFFu;
     } else if (mapping && n) {
         std::vector<uint32_t> m(n);
-        HIPCK(hipMemcpyAsync(m.data(), c->mapping.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipMemcpyAsync(m.data(), c->list[c->cur].mapping.p, n * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCK(hipStreamSynchronize(c->stream));
         if (!c->permuted) {
             memcpy(mapping, m.data(), n * 4);
@@ -3571,6 +3577,7 @@ int deme_seed_contacts(deme_ctx* c, const uint32_t* idA, const uint32_t* idB, co
     c->seeded = true;
     c->mapFresh = false;
     c->conValid = false;
+    c->list[c->cur].invalidate();
     return DEME_OK;
 }
 
@@ -4092,24 +4099,12 @@ int deme_inspect_region(deme_ctx* c, uint32_t q, int region, float* out) {
         return rc;
     float* in = c->stage.as<float>();
     float* res = in + n;  // one spare slot behind the values
-    size_t need = 0;
-    if (isMax) {
-        HIPCK(rocprim::reduce(nullptr, need, in, res, identity, n, FMax(), c->stream));
-    } else if (isMin) {
-        HIPCK(rocprim::reduce(nullptr, need, in, res, identity, n, FMin(), c->stream));
-    } else {
-        HIPCK(rocprim::reduce(nullptr, need, in, res, identity, n, rocprim::plus<float>(), c->stream));
-    }
-    if (int rc = ensure(c, c->sortTmp, need))
+    if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+            return isMax   ? rocprim::reduce(tmp, bytes, in, res, identity, n, FMax(), c->stream)
+                   : isMin ? rocprim::reduce(tmp, bytes, in, res, identity, n, FMin(), c->stream)
+                           : rocprim::reduce(tmp, bytes, in, res, identity, n, rocprim::plus<float>(), c->stream);
+        }))
         return rc;
-    need = c->sortTmp.bytes;
-    if (isMax) {
-        HIPCK(rocprim::reduce(c->sortTmp.p, need, in, res, identity, n, FMax(), c->stream));
-    } else if (isMin) {
-        HIPCK(rocprim::reduce(c->sortTmp.p, need, in, res, identity, n, FMin(), c->stream));
-    } else {
-        HIPCK(rocprim::reduce(c->sortTmp.p, need, in, res, identity, n, rocprim::plus<float>(), c->stream));
-    }
     HIPCK(hipMemcpyAsync(out, res, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
     return DEME_OK;
@@ -4297,15 +4292,14 @@ static int resize_collect(deme_ctx* c, const uint32_t* ids, const uint32_t* fb, 
     uint64_t* kSorted = c->rsKeys[1].as<uint64_t>();
     uint32_t* runLen = c->rsRuns.as<uint32_t>();
     // (a key holds 48 bits: the 16-bit component index above the 32 factor bits)
-    size_t need = 0, need2 = 0;
-    HIPCK(rocprim::radix_sort_keys(nullptr, need, kIn, kSorted, (size_t)nK, 0, 48, c->stream));
-    HIPCK(rocprim::run_length_encode(nullptr, need2, kSorted, (size_t)nK, kIn, runLen, dCnt + 1, c->stream));
-    if (int rc = ensure(c, c->sortTmp, std::max(need, need2)))
+    if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, kIn, kSorted, (size_t)nK, 0, 48, c->stream);
+        }))
         return rc;
-    need = c->sortTmp.bytes;
-    HIPCK(rocprim::radix_sort_keys(c->sortTmp.p, need, kIn, kSorted, (size_t)nK, 0, 48, c->stream));
-    need2 = c->sortTmp.bytes;
-    HIPCK(rocprim::run_length_encode(c->sortTmp.p, need2, kSorted, (size_t)nK, kIn, runLen, dCnt + 1, c->stream));
+    if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+            return rocprim::run_length_encode(tmp, bytes, kSorted, (size_t)nK, kIn, runLen, dCnt + 1, c->stream);
+        }))
+        return rc;
     uint32_t nU = 0;
     HIPCK(hipMemcpyAsync(&nU, dCnt + 1, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));

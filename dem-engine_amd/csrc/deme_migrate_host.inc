@@ -52,21 +52,17 @@ struct MigScratch {  // everything one slab allocates during a migration: bump a
     } while (0)
 
 int mig_scan_u32(deme_halo_group* g, deme_ctx* c, const uint32_t* in, uint32_t* out, size_t n) {  // exclusive plus-scan on the slab's stream
-    size_t need = 0;
-    MIGCK(rocprim::exclusive_scan(nullptr, need, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
-    if (ensure(c, c->scanTmp, need))
-        return gfail(g, c->lastStatus, "migrate: %s", c->err.c_str());
-    need = c->scanTmp.bytes;
-    MIGCK(rocprim::exclusive_scan(c->scanTmp.p, need, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
+    if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream);
+        }))
+        return gfail(g, rc, "migrate: %s", c->err.c_str());
     return DEME_OK;
 }
 int mig_scan_count(deme_halo_group* g, deme_ctx* c, const MigCount* in, MigCount* out, size_t n) {
-    size_t need = 0;
-    MIGCK(rocprim::exclusive_scan(nullptr, need, in, out, MigCount{}, n, MigCountPlus(), c->stream));
-    if (ensure(c, c->scanTmp, need))
-        return gfail(g, c->lastStatus, "migrate: %s", c->err.c_str());
-    need = c->scanTmp.bytes;
-    MIGCK(rocprim::exclusive_scan(c->scanTmp.p, need, in, out, MigCount{}, n, MigCountPlus(), c->stream));
+    if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, in, out, MigCount{}, n, MigCountPlus(), c->stream);
+        }))
+        return gfail(g, rc, "migrate: %s", c->err.c_str());
     return DEME_OK;
 }
 
@@ -691,24 +687,17 @@ int deme_halo_group_migrate(deme_halo_group* g, uint32_t* clumpsMoved) {
                 return rc;
             // global -> local sphere ids of the re-assembled slab
             hipLaunchKernelGGL(k_mig_iota_gid, dim3(grid_for(std::max(nSNew, 1u))), dim3(256), 0, c->stream, nSNew, (const uint32_t*)newSGid, sk, sv);
-            if (nSNew) {
-                size_t need = 0;
-                MIGCK(rocprim::radix_sort_pairs(nullptr, need, sk, sk2, sv, sv2, (size_t)nSNew, 0, 32, c->stream));
-                if (ensure(c, c->sortTmp, need))
-                    return gfail(g, c->lastStatus, "migrate: %s", c->err.c_str());
-                need = c->sortTmp.bytes;
-                MIGCK(rocprim::radix_sort_pairs(c->sortTmp.p, need, sk, sk2, sv, sv2, (size_t)nSNew, 0, 32, c->stream));
-            }
+            if (nSNew)
+                if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                        return rocprim::radix_sort_pairs(tmp, bytes, sk, sk2, sv, sv2, (size_t)nSNew, 0, 32, c->stream);
+                    }))
+                    return gfail(g, rc, "migrate: %s", c->err.c_str());
             hipLaunchKernelGGL(k_mig_localise, dim3(grid_for(nCand)), dim3(256), 0, c->stream, nCand, w.nW, q.flipMask, ch, cw, sk2, sv2, nSNew, ns_,
                                w.nOwnNew, k0, r0);
-            {
-                size_t need = 0;
-                MIGCK(rocprim::radix_sort_pairs(nullptr, need, k0, k1, r0, r1, (size_t)nCand, 0, 64, c->stream));
-                if (ensure(c, c->sortTmp, need))
-                    return gfail(g, c->lastStatus, "migrate: %s", c->err.c_str());
-                need = c->sortTmp.bytes;
-                MIGCK(rocprim::radix_sort_pairs(c->sortTmp.p, need, k0, k1, r0, r1, (size_t)nCand, 0, 64, c->stream));
-            }
+            if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                    return rocprim::radix_sort_pairs(tmp, bytes, k0, k1, r0, r1, (size_t)nCand, 0, 64, c->stream);
+                }))
+                return gfail(g, rc, "migrate: %s", c->err.c_str());
             hipLaunchKernelGGL(k_mig_keep_flags, dim3(grid_for((size_t)nCand + 1)), dim3(256), 0, c->stream, nCand, k1, keep);
             if (int rc = mig_scan_u32(g, c, keep, kpos, (size_t)nCand + 1))
                 return rc;
@@ -778,9 +767,8 @@ int deme_halo_group_migrate(deme_halo_group* g, uint32_t* clumpsMoved) {
             MIGCK(hipMemcpyAsync(c->sharedIds.p, c->hShared.data(), c->hShared.size() * 4, hipMemcpyHostToDevice, c->stream));
         }
         c->haveList = true, c->seeded = true, c->mapFresh = false, c->conValid = false, c->listStale = false;
-        c->tileActive = c->conTile = false;
-        c->nHeavy = c->nHeavyFree = 0;
-        c->hrPending = false;
+        c->list[c->cur].invalidate();
+        c->conTile = false;
         c->prescDirty = true;
         c->nextAccPending = false;
         c->hNextAcc.clear();

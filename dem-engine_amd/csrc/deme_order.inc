@@ -385,8 +385,8 @@ static int order_apply(deme_ctx* c, const std::vector<uint32_t>& ord, const std:
         HIPCK(hipMemcpyAsync(c->persistKeys.p, c->hPersist.data(), c->hPersist.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
     // what was built for the old slots
-    c->conValid = false, c->conTile = false, c->tileActive = false, c->legacyLists = false;
-    c->fusedList = c->fusedPrevValid = false;
+    c->list[c->cur].invalidate();
+    c->conValid = false, c->conTile = false, c->fusedPrevValid = false;
     c->prescDirty = true;
     c->listStale = true;
     // The re-keyed list is a SEED of the detection that follows, not a list anything may be evaluated or downloaded from: the

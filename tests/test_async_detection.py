@@ -133,3 +133,39 @@ def test_async_detection_in_a_pair_of_slabs(pkg):
         assert len(common) > 500 and all(wl[q] == wa[q] for q in common)
         assert all(wl[q] == 0.0 for q in wl if q not in wa) and all(wa[q] == 0.0 for q in wa if q not in wl)
     g0.close(), g1.close()
+
+
+def test_async_detection_swaps_in_a_tiled_list(pkg, orc):
+    """the fast mode's owner-tile structures are most of what an asynchronous detection swaps in: a settled bed (the one of
+    test_fast_mode.py, with its stated bounds for N = 100) stepped with asynchronous detection against the oracle stepped
+    lock-step -- then contact recording switched on, which evaluates the swapped-in list through the recording instances"""
+    from tests.test_fast_mode import _bed as fast_bed, _positions, _settled
+    n, K, D, N = 3000, 20, 6, 100
+    b = fast_bed(pkg, n=n, cd_freq=K)
+    b.SetExpandSafetyAdder(1.0)
+    p, sc, st = _settled(pkg, b)
+    ctx = pkg.Context(0)
+    ctx.set_arith_mode("fast")
+    ctx.set_params(p), ctx.upload_scene(sc), ctx.upload_state(st)
+    ctx.set_async_detection(D)
+    ctx.set_timing(1)
+    sim = orc.make_sim(pkg, p, sc)
+    sim.upload_state(st)
+    ctx.step(N), sim.step(N)
+    assert ctx.force_kernel()[0] == "k_tile_forces<0, false>", ctx.force_kernel()
+    assert ctx.kernel_time_ms("detect_async_part1")[1] >= N // K - 1  # (the asynchronous path really served)
+    g, o = ctx.download_state(), sim.download_state()
+    dx = np.abs(_positions(pkg, p, g) - _positions(pkg, p, o)).max()
+    dv = max(np.abs(g[k] - o[k]).max() for k in ("vX", "vY", "vZ"))
+    print(f"asynchronous fast vs lock-step oracle after {N} steps (K={K}, D={D}): |dx| {dx:.3e} m, |dv| {dv:.3e} m/s")
+    assert dx <= 5e-8 and dv <= 2e-4
+    wo = {q: w for q, w in zip(zip(*[x.tolist() for x in sim.contacts()[:3]]), sim.wildcard(3).tolist())}
+    wa = {q: w for q, w in zip(zip(*[x.tolist() for x in ctx.contacts()[:3]]), ctx.wildcard(3).tolist())}
+    assert sum(1 for q in wo if wo[q] != 0.0) > n // 40 and all(q in wa for q in wo if wo[q] != 0.0)
+    assert all(wo[q] == 0.0 for q in wo if q not in wa) and all(wa[q] == 0.0 for q in wa if q not in wo)
+    ctx.set_record_contacts(True)
+    ctx.step(K)
+    recs = ctx.contact_records()
+    nC = int(ctx.counts().nContacts)
+    assert nC > n // 10 and all(r.shape == (nC, 3) and np.isfinite(r).all() for r in recs)
+    ctx.close()
