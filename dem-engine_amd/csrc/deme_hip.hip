@@ -357,6 +357,13 @@ int with_temp(deme_ctx* c, DevBuf& tmp, Call&& call) {
 }
 
 inline unsigned grid_for(size_t n, unsigned block = 256) { return (unsigned)((n + block - 1) / block); }
+// bits that tell n values apart (the width of a radix sort's keys): at least one, at most `cap`
+inline unsigned bits_for(uint64_t n, unsigned cap) {
+    unsigned b = 1;
+    while (b < cap && (1ull << b) < n)
+        b++;
+    return b;
+}
 
 // ---- kernel timing (HIP events on the context stream) ------------------------------------------
 hipEvent_t get_event(deme_ctx* c) {
@@ -617,13 +624,14 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
         }
         uint32_t P = 0;
         bool filled = false;
-        if (nS && c->incCap) {  // the incidences go out before the host knows how many there are (the kernel guards the arena's end):
-                                // the GPU works through the read-back below instead of idling; repeated if the arena has to grow
+        auto fill_incidence = [&]() {
             hipLaunchKernelGGL(k_fill_incidence, dim3(grid_for(nS)), dim3(256), 0, st, c->dp,
                                c->binLo.as<uint4>(), c->binN.as<uint2>(), c->offsets.as<uint32_t>(),
                                c->incKeys[0].as<uint32_t>(), c->incVals[0].as<uint32_t>(), (uint64_t)c->incCap);
             filled = true;
-        }
+        };
+        if (nS && c->incCap)  // the incidences go out before the host knows how many there are (the kernel guards the arena's end):
+            fill_incidence();  // the GPU works through the read-back below instead of idling; repeated if the arena has to grow
         if (nS) {
             // (read-backs land in pinned memory: a copy into pageable memory goes through the runtime's staging buffer and costs
             // tens of microseconds of host time before the wait even starts)
@@ -664,16 +672,10 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             filled = false;
         }
         c->nInc = P;
-        int sortedIdx = 0;
+        const unsigned bits = bits_for((uint64_t)c->hp.nbX * c->hp.nbY * c->hp.nbZ, 32);  // of a bin id
         if (P) {
             if (!filled)
-                hipLaunchKernelGGL(k_fill_incidence, dim3(grid_for(nS)), dim3(256), 0, st, c->dp,
-                                   c->binLo.as<uint4>(), c->binN.as<uint2>(), c->offsets.as<uint32_t>(),
-                                   c->incKeys[0].as<uint32_t>(), c->incVals[0].as<uint32_t>(), (uint64_t)c->incCap);
-            const uint64_t nBins = (uint64_t)c->hp.nbX * c->hp.nbY * c->hp.nbZ;
-            unsigned bits = 1;
-            while (bits < 32 && (1ull << bits) < nBins)
-                bits++;
+                fill_incidence();
             // bin ids of up to 22 bits: two passes of 11 bits (16 keys per thread) take as long as three of 8 and save a pass's launches
             const bool twoPass = bits > 16 && bits <= 22;
             if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
@@ -683,7 +685,6 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
                                                                                 c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P, 0, bits, st);
                 }))
                 return rc;
-            sortedIdx = 1;
             const uint32_t nWin = (uint32_t)grid_for(P, SW_T);
             if (int rc = ensure(c, c->binStat, (size_t)nWin * sizeof(uint2)))
                 return rc;
@@ -694,7 +695,6 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             hipLaunchKernelGGL(k_bin_stats_final, dim3((nWin + 2047u) / 2048u), dim3(256), 0, st, c->binStat.as<uint2>(), nWin,
                                c->ctr.as<DetectCounters>());
         }
-        (void)sortedIdx;
         // ---- sphere-triangle contacts (only when a mesh is loaded and some sphere is registered in a bin)
         c->nTriInc = 0;
         if (c->nTri && P) {
@@ -721,10 +721,6 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
                                    c->triWorld.as<TriWorld>(), c->triLo.as<int4>(), c->triHi.as<int4>(),
                                    c->triOffsets.as<uint32_t>(), c->triKeys[0].as<uint32_t>(), c->triVals[0].as<uint32_t>(),
                                    (uint64_t)c->triCap);
-                const uint64_t nBins = (uint64_t)c->hp.nbX * c->hp.nbY * c->hp.nbZ;
-                unsigned bits = 1;
-                while (bits < 32 && (1ull << bits) < nBins)
-                    bits++;
                 if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
                         return rocprim::radix_sort_pairs(tmp, bytes, c->triKeys[0].as<uint32_t>(), c->triKeys[1].as<uint32_t>(),
                                                          c->triVals[0].as<uint32_t>(), c->triVals[1].as<uint32_t>(), (size_t)TP, 0, bits, st);
@@ -807,13 +803,7 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             // key = A << 33 | class << 31 | B.  One radix sort over the occupied upper bits [31, 33 + bits(A)) groups the keys by
             // (sphere A, class) -- 3 passes at 3e6 spheres, where a full 64-bit order took 6 to 8 -- and k_segment_rank_sort puts each
             // group's few partners in order (DEMCubContactDetection.cu:811-1110 runs five full sorts for the same list order)
-            auto bits_of = [](uint64_t n) {
-                unsigned b = 1;
-                while (b < 31 && (1ull << b) < n)
-                    b++;
-                return b;
-            };
-            const unsigned bitsA = bits_of(c->dp.nSpheres);
+            const unsigned bitsA = bits_for(c->dp.nSpheres, 31);
             if (int rc = ensure(c, c->keysMid, (size_t)c->cntCap * 8))  // (its own scratch: an asynchronous detection runs beside force passes)
                 return rc;
             uint64_t* mid = c->keysMid.as<uint64_t>();
@@ -848,9 +838,7 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
 int build_legacy_lists(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st) {
     const uint64_t nC = L.nListed;
     if (nC) {
-        unsigned obits = 1;
-        while (obits < 32 && (1ull << obits) < (uint64_t)c->nOwners)
-            obits++;
+        const unsigned obits = bits_for(c->nOwners, 32);
         if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
                 return rocprim::radix_sort_pairs(tmp, bytes, L.ownerB[0].as<uint32_t>(), L.ownerB[1].as<uint32_t>(), L.bIdx[0].as<uint32_t>(),
                                                  L.bIdx[1].as<uint32_t>(), (size_t)nC, 0, obits, st);
@@ -901,6 +889,22 @@ int ensure_legacy_lists(deme_ctx* c) {
     return read_legacy_counts(c, L, c->stream, hr);
 }
 
+// May a list of nC contacts get tile structures (deme_tile.h)?  The fast mode; a user model only with its tile kernels compiled and
+// enough contacts per tile to pay for them; no replicated free owners; tables that the tile kernels can stage.
+bool tile_eligible(const deme_ctx* c, uint64_t nC) {
+    const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
+    if (!nC || c->arith != DEME_ARITH_FAST || !c->hShared.empty())
+        return false;
+    if (c->hp.forceModel == DEME_FORCE_CUSTOM && !(c->customTileFn[0] && nC >= (uint64_t)c->tileMinContactsCustom * nTiles))
+        return false;
+    // the tables are loaded in one round of 16-byte pieces, one per thread.  tInfo names a material in 4 bits: a table of 17 or
+    // more materials has more pieces than a round by itself, so no test of nMat <= 16 is needed beside this one.
+    static_assert(DEME_TILE_T < 2 * 17 * 17, "a tile's tables may hold more than 16 materials: tInfo has 4-bit material fields");
+    const uint64_t pieces = (uint64_t)c->nComp + 2ull * c->nMat * c->nMat + 4ull * c->nAnal;
+    return pieces <= DEME_TILE_T && c->nMassProps <= DEME_TILE_T && c->nAnal <= 65535 && c->nComp <= 65535 &&
+           tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial) <= DEME_TILE_TABLE_MAX;
+}
+
 // Part 2 of a detection: the history map and the structures of `L`, built on `st` from the owner records `ow` (the live ones --
 // or, beside steps that are integrating them, the snapshot part 1 was made from) and the nC keys part 1 left in the next key
 // buffer.  Everything fallible comes first and touches `L` only; the context turns to the new list in the last lines.
@@ -914,12 +918,7 @@ int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st
     }
     // per-owner gather lists for the atomics-free accumulation
     HIPCK(hipMemsetAsync(L.rangeCtr.p, 0, sizeof(RangeCounters), st));
-    const bool tileEligible = nC && c->arith == DEME_ARITH_FAST &&
-                              (c->hp.forceModel != DEME_FORCE_CUSTOM ||
-                               (c->customTileFn[0] && nC >= (uint64_t)c->tileMinContactsCustom * ((c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB))) &&
-                              c->hShared.empty() && c->nMat <= 16 && c->nAnal <= 65535 && c->nComp <= 65535 &&
-                              tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial) <= DEME_TILE_TABLE_MAX &&
-                              c->nComp + c->nMat * c->nMat * 2u + c->nAnal * 4u <= DEME_TILE_T && c->nMassProps <= DEME_TILE_T;
+    const bool tileEligible = tile_eligible(c, nC);
     const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
     if (tileEligible)
         HIPCK(hipMemsetAsync(L.tileRem.p, 0, ((size_t)nTiles + 1) * 4, st));
@@ -967,9 +966,7 @@ int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st
         nR = *pin_at<uint32_t>(c, 8), hr = *pin_at<RangeCounters>(c, 128);
         nR += hr.nExtra;  // the records of the tiles that do not fit (k_tile_forces_big): every contact of such a tile has one
         L.nBigTiles = hr.nBig;
-        unsigned obits = 1;
-        while (obits < 32 && (1ull << obits) < (uint64_t)c->nOwners)
-            obits++;
+        const unsigned obits = bits_for(c->nOwners, 32);
         if (nR) {
             if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
                     return rocprim::radix_sort_pairs<DemeRadixCfg<10>>(tmp, bytes, L.remKey[0].as<uint32_t>(), L.remKey[1].as<uint32_t>(),
@@ -1138,6 +1135,22 @@ void launch_reduce_heavy(deme_ctx* c, bool skipFixed) {
                        skipFixed ? L.fixedFlag.as<uint8_t>() : (const uint8_t*)nullptr, c->acc.as<AccRec>());
 }
 
+// the XCD-aware block maps of the force kernels are bijections on multiples of 8 G blocks (G = DevParams' xcdGroup; 0: no map)
+inline unsigned xcd_round(unsigned nBlk, uint32_t G) { return G ? (nBlk + 8u * G - 1u) / (8u * G) * (8u * G) : nBlk; }
+
+// a run-time bool as a type: f(std::true_type) or f(std::false_type), for picking a kernel instance
+template <class F>
+void as_constant(bool b, F&& f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+// the model class of a launch: 0 / 1 the built-in models (Hertzian, frictionless), 2 the one compiled at run time (deme_jit.h)
+inline int model_class(const deme_ctx* c) {
+    return c->hp.forceModel == DEME_FORCE_CUSTOM ? 2 : (c->hp.forceModel == DEME_FORCE_HERTZIAN ? 0 : 1);
+}
+
 // the stride of the staged owner records of a tile launch (TileArgs::rs16): padded by 16 bytes when that costs no workgroup per CU
 // (160 KB of LDS per CU, allocated in 512-byte blocks; the kernels' registers allow four workgroups)
 static uint32_t tile_record_stride(uint32_t hCap, uint32_t lCap, uint32_t tabBytes, int model) {
@@ -1147,6 +1160,86 @@ static uint32_t tile_record_stride(uint32_t hCap, uint32_t lCap, uint32_t tabByt
     auto groups = [&](uint32_t rs) { return std::min<uint32_t>(4u, 163840u / ((tile_lds_bytes(hCap, lCap, tabBytes, rs) + 511u) & ~511u)); };
     return groups(base + 1u) == groups(base) ? base + 1u : base;
 }
+
+// A tile launch (k_tile_forces, k_tile_step and the instances compiled at run time), described once: the list's tile structures, the
+// current owners and wildcards, and the launch's shape -- the block count and the LDS bytes, sized for a largest halo of `maxHalo`
+// staged owners (rounded up so that a launch configuration serves many detections).  The callers add what is their own.
+struct TileLaunch {
+    TileArgs a;
+    unsigned nBlk;
+    uint32_t ldsBytes;
+};
+TileLaunch tile_launch(deme_ctx* c, ContactList& L, int model, uint32_t maxHalo) {
+    TileLaunch t{};
+    TileArgs& ta = t.a;
+    ta.owners = c->owners.as<OwnerRec>();
+    ta.tInfo = L.tInfo.as<uint2>();
+    ta.aStart = L.aStart.as<uint32_t>();
+    ta.hList = L.hList.as<uint32_t>(), ta.hCount = L.hCount.as<uint32_t>(), ta.org = L.tileOrg.as<int64_t>();
+    ta.lOff = L.lOff.as<uint16_t>(), ta.lPos = L.lPos.as<uint16_t>(), ta.lCount = L.lCount.as<uint32_t>();
+    ta.wc = c->wc[c->wcCur].as<float>();
+    ta.nOwners = c->nOwners;
+    ta.nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
+    ta.xcdGroup = c->xcdGroup;
+    ta.tileBig = L.tileBig.as<uint32_t>(), ta.bigList = L.bigList.as<uint32_t>(), ta.info = L.info.as<uint4>();
+    ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (maxHalo + 15u) & ~15u);
+    ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (L.tileMaxList + 15u) & ~15u);
+    ta.nComp = c->nComp, ta.nAnal = c->nAnal, ta.nMass = c->nMassProps;
+    const uint32_t tabBytes = tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial);
+    ta.rs16 = tile_record_stride(ta.hCap, ta.lCap, tabBytes, model);
+    ta.swz = (model != 2 && ta.rs16 == tile_rec16(model)) ? 1u : 0u;
+    t.nBlk = xcd_round(ta.nTiles, ta.xcdGroup);
+    t.ldsBytes = tile_lds_bytes(ta.hCap, ta.lCap, tabBytes, ta.rs16);
+    return t;
+}
+
+// The general kernel (one contact per thread) of a model class, over nBlk blocks: its mesh variant (the sphere-triangle work list),
+// the fast kernel of the built-in models, or the exact one.  A user model has two entry points: the mesh variant and the other.
+enum class General { Mesh, Fast, Exact };
+int launch_general(deme_ctx* c, int model, General which, unsigned nBlk, ForceArgs& a) {
+    if (model == 2) {
+        void* args[] = {&c->dp, &a};
+        HIPCK(hipModuleLaunchKernel(c->customFn[which == General::Mesh ? 1 : 0], nBlk, 1, 1, DEME_FORCE_BLOCK, 1, 1, 0, c->stream, args,
+                                    nullptr));
+        return DEME_OK;
+    }
+    as_constant(model == 1, [&](auto frictionless) {
+        constexpr int M = decltype(frictionless)::value ? 1 : 0;
+        const dim3 g(nBlk), b(DEME_FORCE_BLOCK);
+        if (which == General::Mesh)
+            hipLaunchKernelGGL((k_calc_forces<M, 1>), g, b, 0, c->stream, c->dp, a);
+        else if (which == General::Fast)
+            hipLaunchKernelGGL((k_forces_fast<M>), g, b, 0, c->stream, c->dp, a);
+        else
+            hipLaunchKernelGGL((k_calc_forces<M, 0>), g, b, 0, c->stream, c->dp, a);
+    });
+    return DEME_OK;
+}
+// The tile kernels of (model class, mesh records, recording): the tiles that fit LDS, then one workgroup for each of the list's tiles
+// that do not, with the same outputs (deme_tile.h).  A user model's are the same kernels compiled around its statements (deme_jit.h).
+int launch_tiles(deme_ctx* c, const ContactList& L, int model, bool mesh, bool rec, TileLaunch& t) {
+    const unsigned nBig = L.nBigTiles;
+    if (model == 2) {
+        void* args[] = {&c->dp, &t.a};
+        HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 1 : 0], t.nBlk, 1, 1, DEME_TILE_T, 1, 1, t.ldsBytes, c->stream, args, nullptr));
+        if (nBig)
+            HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 3 : 2], nBig, 1, 1, DEME_TILE_T, 1, 1, 0, c->stream, args, nullptr));
+        return DEME_OK;
+    }
+    as_constant(model == 1, [&](auto frictionless) {
+        as_constant(mesh, [&](auto withMesh) {
+            as_constant(rec, [&](auto withRec) {
+                constexpr int M = decltype(frictionless)::value ? 1 : 0;
+                constexpr bool MESH = decltype(withMesh)::value, REC = decltype(withRec)::value;
+                hipLaunchKernelGGL((k_tile_forces<M, MESH, REC>), dim3(t.nBlk), dim3(DEME_TILE_T), t.ldsBytes, c->stream, c->dp, t.a);
+                if (nBig)
+                    hipLaunchKernelGGL((k_tile_forces_big<M, MESH, REC>), dim3(nBig), dim3(DEME_TILE_T), 0, c->stream, c->dp, t.a);
+            });
+        });
+    });
+    return DEME_OK;
+}
+
 // pass: -1 everything in one launch; 0 / 1 the two halves of a split step (contacts that read no ghost owner / the rest)
 int launch_forces(deme_ctx* c, int pass = -1) {
     ContactList& L = c->list[c->cur];
@@ -1181,144 +1274,90 @@ int launch_forces(deme_ctx* c, int pass = -1) {
         a.blockMode = L.blockMode.as<uint32_t>();
         a.pass = (uint32_t)pass;
     }
+    if (c->record) {  // (on the tile path these serve the mesh variant of the general kernel, which records its own contacts)
+        a.recForce = c->rec[0].as<float>(), a.recTorque = c->rec[1].as<float>(), a.recCPA = c->rec[2].as<float>(),
+        a.recCPB = c->rec[3].as<float>();
+    }
     a.nContacts = (uint32_t)c->nContacts;
     a.timeElapsed = (float)c->timeElapsed;
     a.xcdGroup = c->xcdGroup;
     const bool fastMode = c->arith == DEME_ARITH_FAST;
     a.world = fastMode ? 1u : 0u;
-    // the fast kernel covers the built-in models' hot classes; contact recording (body-frame contact points) and user
-    // fragments (the reference's body-frame vocabulary) run the general kernel, with world-frame contributions in fast mode
-    // contact recording: the tile pass writes the records itself (REC instances) for the built-in models; user models record
-    // through the general kernel
-    const bool fastKernel = fastMode && c->hp.forceModel != DEME_FORCE_CUSTOM;
-    const bool customTile = fastMode && !c->record && c->hp.forceModel == DEME_FORCE_CUSTOM && c->customTileFn[0];
-    if ((fastKernel || customTile) && L.tileActive) {  // owner tiles: deme_tile.h
+    // The owner tiles (deme_tile.h) serve the fast mode: the built-in models with or without contact recording (REC instances), a
+    // user model when it is not recording.  Everything else -- the exact mode, a recording user model (the reference's body-frame
+    // vocabulary), a list without tile structures -- runs the general kernel, the fast one where there is one and nothing is recorded.
+    const int model = model_class(c);
+    const bool tiles = fastMode && L.tileActive && (model != 2 || (!c->record && c->customTileFn[0]));
+    if (tiles) {
         if (L.fusedList && !L.fusedChecked)
             resolve_heavy_counts(c, L);
-        TileArgs ta{};
-        ta.owners = a.owners;
-        ta.tInfo = L.tInfo.as<uint2>();
-        ta.aStart = a.aStart;
-        ta.hList = L.hList.as<uint32_t>(), ta.hCount = L.hCount.as<uint32_t>(), ta.org = L.tileOrg.as<int64_t>();
-        ta.lOff = L.lOff.as<uint16_t>(), ta.lPos = L.lPos.as<uint16_t>(), ta.lCount = L.lCount.as<uint32_t>();
-        ta.wc = a.wc;
+    } else {
+        c->conTile = false;
+        if (int rc = ensure_legacy_lists(c))  // (a list with tile structures that is evaluated by the other kernels after all: recording switched on, ...)
+            return rc;
+    }
+    ScopedTimer tm(c, "calc_forces");
+    // sphere-triangle contacts: the mesh variant of the general kernel, ahead of the kernels that take its records in (the tiles read
+    // them, the hot variant folds its A-side records into the in-block sums).  They read no ghost owner -- meshes are replicated,
+    // not ghosted --: all of them go with pass 0.
+    const bool mesh = c->nTri > 0 && L.nSM > 0;
+    if (mesh && pass != 1)
+        if (int rc = launch_general(c, model, General::Mesh, grid_for(L.nSM, DEME_FORCE_BLOCK), a))
+            return rc;
+    if (tiles) {
+        TileLaunch t = tile_launch(c, L, model, L.tileMaxHalo);
+        TileArgs& ta = t.a;
         ta.tSum = a.aSum;
         ta.rec32 = c->rec32.as<float4>(), ta.rankC = L.rankC.as<uint32_t>();
-        ta.nOwners = c->nOwners;
-        ta.nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
-        ta.xcdGroup = c->xcdGroup;
-        ta.tileBig = L.tileBig.as<uint32_t>(), ta.bigList = L.bigList.as<uint32_t>(), ta.info = a.info;
         ta.keys = a.keys, ta.timeElapsed = a.timeElapsed;
-        if (c->record) {
-            for (int k = 0; k < 4; k++)
-                ta.rec[k] = c->rec[k].as<float>();
-            a.recForce = c->rec[0].as<float>(), a.recTorque = c->rec[1].as<float>(), a.recCPA = c->rec[2].as<float>(),
-            a.recCPB = c->rec[3].as<float>();  // (the mesh variant of the general kernel records its own contacts)
-        }
         for (int k = 0; k < 8; k++)
             ta.ownerWc[k] = a.ownerWc[k], ta.geoWcSph[k] = a.geoWcSph[k], ta.geoWcAnal[k] = a.geoWcAnal[k];
+        if (c->record)
+            for (int k = 0; k < 4; k++)
+                ta.rec[k] = c->rec[k].as<float>();
+        if (mesh)
+            ta.conA4 = a.conA4, ta.conA2 = a.conA2, ta.conB4 = a.conB4, ta.conB2 = a.conB2;
         if (pass >= 0 && c->hasGhosts) {
             ta.tileMode = L.tileMode.as<uint32_t>();
             ta.pass = (uint32_t)pass;
         }
-        unsigned nBlk = ta.nTiles;
-        if (ta.xcdGroup)
-            nBlk = (nBlk + 8u * ta.xcdGroup - 1u) / (8u * ta.xcdGroup) * (8u * ta.xcdGroup);
-        // LDS sized from this list's largest tile (rounded up so that a launch configuration serves many detections)
-        ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (L.tileMaxHalo + 15u) & ~15u);
-        ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (L.tileMaxList + 15u) & ~15u);
-        ta.nComp = c->nComp, ta.nAnal = c->nAnal, ta.nMass = c->nMassProps;
-        const uint32_t tabBytes = tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial);
-        ta.rs16 = tile_record_stride(ta.hCap, ta.lCap, tabBytes, customTile ? 2 : 0);
-        ta.swz = (!customTile && ta.rs16 == tile_rec16(0)) ? 1u : 0u;
-        const uint32_t ldsBytes = tile_lds_bytes(ta.hCap, ta.lCap, tabBytes, ta.rs16);
-        ScopedTimer tm(c, "calc_forces");
-        const bool mesh = c->nTri > 0 && L.nSM > 0;
-        if (mesh) {
-            ta.conA4 = a.conA4, ta.conA2 = a.conA2, ta.conB4 = a.conB4, ta.conB2 = a.conB2;
-            if (pass != 1) {  // sphere-triangle contacts: the mesh variant of the general kernel, before the tiles that read its records
-                              // (they read no ghost owner -- meshes are replicated, not ghosted --: all of them go with pass 0)
-                const dim3 gm(grid_for(std::max<uint32_t>(L.nSM, 1u), DEME_FORCE_BLOCK)), bm(DEME_FORCE_BLOCK);
-                if (customTile) {
-                    void* args0[] = {&c->dp, &a};
-                    HIPCK(hipModuleLaunchKernel(c->customFn[1], gm.x, 1, 1, DEME_FORCE_BLOCK, 1, 1, 0, c->stream, args0, nullptr));
-                } else if (c->hp.forceModel == DEME_FORCE_HERTZIAN)
-                    hipLaunchKernelGGL((k_calc_forces<0, 1>), gm, bm, 0, c->stream, c->dp, a);
-                else
-                    hipLaunchKernelGGL((k_calc_forces<1, 1>), gm, bm, 0, c->stream, c->dp, a);
-            }
-        }
-        const unsigned nBig = L.nBigTiles;  // tiles that do not fit LDS: one workgroup each, the same outputs (deme_tile.h)
-        if (customTile) {  // the same kernels compiled at run time around the user's statements (deme_jit.h)
-            void* argsT[] = {&c->dp, &ta};
-            HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 1 : 0], nBlk, 1, 1, DEME_TILE_T, 1, 1, ldsBytes, c->stream, argsT, nullptr));
-            if (nBig)
-                HIPCK(hipModuleLaunchKernel(c->customTileFn[mesh ? 3 : 2], nBig, 1, 1, DEME_TILE_T, 1, 1, 0, c->stream, argsT, nullptr));
-        } else {
-            // (model, mesh records, recording) -> the instance of the two kernels
-            const int model = c->hp.forceModel == DEME_FORCE_HERTZIAN ? 0 : 1;
-            const int which = model * 4 + (mesh ? 2 : 0) + (c->record ? 1 : 0);
-            auto go = [&](auto tileK, auto bigK) {
-                hipLaunchKernelGGL(tileK, dim3(nBlk), dim3(DEME_TILE_T), ldsBytes, c->stream, c->dp, ta);
-                if (nBig)
-                    hipLaunchKernelGGL(bigK, dim3(nBig), dim3(DEME_TILE_T), 0, c->stream, c->dp, ta);
-            };
-            switch (which) {
-                case 0: go(k_tile_forces<0, false, false>, k_tile_forces_big<0, false, false>); break;
-                case 1: go(k_tile_forces<0, false, true>, k_tile_forces_big<0, false, true>); break;
-                case 2: go(k_tile_forces<0, true, false>, k_tile_forces_big<0, true, false>); break;
-                case 3: go(k_tile_forces<0, true, true>, k_tile_forces_big<0, true, true>); break;
-                case 4: go(k_tile_forces<1, false, false>, k_tile_forces_big<1, false, false>); break;
-                case 5: go(k_tile_forces<1, false, true>, k_tile_forces_big<1, false, true>); break;
-                case 6: go(k_tile_forces<1, true, false>, k_tile_forces_big<1, true, false>); break;
-                default: go(k_tile_forces<1, true, true>, k_tile_forces_big<1, true, true>); break;
-            }
-        }
-        c->conValid = true;
-        c->conTile = true;
-        return DEME_OK;
-    }
-    c->conTile = false;
-    if (int rc = ensure_legacy_lists(c))  // (a list with tile structures that is evaluated by the other kernels after all: recording switched on, ...)
-        return rc;
-
-    if (c->record) {
-        a.recForce = c->rec[0].as<float>(), a.recTorque = c->rec[1].as<float>(), a.recCPA = c->rec[2].as<float>(),
-        a.recCPB = c->rec[3].as<float>();
-    }
-    {
-        ScopedTimer tm(c, "calc_forces");
-        unsigned nBlk = grid_for(a.nContacts, DEME_FORCE_BLOCK);
-        if (a.xcdGroup)  // the XCD-aware block map is a bijection on multiples of 8 G blocks
-            nBlk = (nBlk + 8u * a.xcdGroup - 1u) / (8u * a.xcdGroup) * (8u * a.xcdGroup);
-        const dim3 g(nBlk), b(DEME_FORCE_BLOCK);
-        // sphere-mesh contacts read no ghost owner (meshes are replicated, not ghosted): all of them go with pass 0
-        const bool hasSM = c->nTri > 0 && L.nSM > 0 && pass != 1;
-        const dim3 gm(grid_for(std::max<uint32_t>(L.nSM, 1u), DEME_FORCE_BLOCK));
-        if (c->hp.forceModel == DEME_FORCE_HERTZIAN) {
-            if (hasSM)  // mesh variant first: the hot variant folds its A-side records into the in-block sums
-                hipLaunchKernelGGL((k_calc_forces<0, 1>), gm, b, 0, c->stream, c->dp, a);
-            if (fastKernel && !c->record)
-                hipLaunchKernelGGL((k_forces_fast<0>), g, b, 0, c->stream, c->dp, a);
-            else
-                hipLaunchKernelGGL((k_calc_forces<0, 0>), g, b, 0, c->stream, c->dp, a);
-        } else if (c->hp.forceModel == DEME_FORCE_HERTZIAN_FRICTIONLESS) {
-            if (hasSM)
-                hipLaunchKernelGGL((k_calc_forces<1, 1>), gm, b, 0, c->stream, c->dp, a);
-            if (fastKernel && !c->record)
-                hipLaunchKernelGGL((k_forces_fast<1>), g, b, 0, c->stream, c->dp, a);
-            else
-                hipLaunchKernelGGL((k_calc_forces<1, 0>), g, b, 0, c->stream, c->dp, a);
-        }
-        else {  // user model: two entry points of the same code object (hot variant, mesh variant)
-            void* args0[] = {&c->dp, &a};
-            if (hasSM)
-                HIPCK(hipModuleLaunchKernel(c->customFn[1], gm.x, 1, 1, DEME_FORCE_BLOCK, 1, 1, 0,
-                                            c->stream, args0, nullptr));
-            HIPCK(hipModuleLaunchKernel(c->customFn[0], g.x, 1, 1, DEME_FORCE_BLOCK, 1, 1, 0, c->stream, args0, nullptr));
-        }
+        if (int rc = launch_tiles(c, L, model, mesh, c->record, t))
+            return rc;
+    } else {
+        const General which = (fastMode && model != 2 && !c->record) ? General::Fast : General::Exact;
+        if (int rc = launch_general(c, model, which, xcd_round(grid_for(a.nContacts, DEME_FORCE_BLOCK), a.xcdGroup), a))
+            return rc;
     }
     c->conValid = true;
+    c->conTile = tiles;
+    return DEME_OK;
+}
+
+// accelerations a script added for the coming step (deme_add_owner_acc): both copies to zero ...
+int zero_next_acc(deme_ctx* c) {
+    std::fill(c->hNextAcc.begin(), c->hNextAcc.end(), AccRec{});
+    HIPCK(hipMemsetAsync(c->nextAcc.p, 0, (size_t)c->nOwners * sizeof(AccRec), c->stream));
+    return DEME_OK;
+}
+// ... which the step that has read them does: they hold for one step only (cleanUpAcc clears the flag when it honours it,
+// DEMPrepForceKernels.cu:14-31)
+int clear_next_acc(deme_ctx* c) {
+    if (!c->nextAccPending)
+        return DEME_OK;
+    c->nextAccPending = false;
+    return zero_next_acc(c);
+}
+// the step counter and the clock (on their own for deme_integrate: a staged caller schedules its own detections)
+void advance_clock(deme_ctx* c) {
+    c->nSteps++;
+    c->timeElapsed += (double)c->hp.h;
+}
+// the end of a step of deme_step and its kin: the list is a step older, and the halo stream may pack the owners just integrated
+int finish_step(deme_ctx* c) {
+    c->stepsSinceCD++;
+    advance_clock(c);
+    if (c->evStepDone)
+        HIPCK(hipEventRecord(c->evStepDone, c->stream));
     return DEME_OK;
 }
 
@@ -1335,60 +1374,37 @@ bool fused_ready(deme_ctx* c) {
 }
 int launch_fused_step(deme_ctx* c, bool dry) {
     ContactList& L = c->list[c->cur];
+    const int model = c->hp.forceModel == DEME_FORCE_HERTZIAN ? 0 : 1;  // (never a user model: fused_ready)
+    const TileLaunch t = tile_launch(c, L, model, L.tileMaxHaloIn);  // (the halos with the incoming contacts' owners: k_tile_incoming)
     StepArgs sa{};
-    TileArgs& ta = sa.t;
+    sa.t = t.a;
     const int cur = dry ? (c->wcCur ^ 1) : c->wcCur;  // (dry: the step is over, the names are swapped already)
-    ta.owners = dry ? c->ownersNext.as<OwnerRec>() : c->owners.as<OwnerRec>();
-    ta.tInfo = L.tInfo.as<uint2>();
-    ta.aStart = L.aStart.as<uint32_t>();
-    ta.hList = L.hList.as<uint32_t>(), ta.hCount = c->hCountIn.as<uint32_t>(), ta.org = L.tileOrg.as<int64_t>();
-    ta.lOff = L.lOff.as<uint16_t>(), ta.lPos = L.lPos.as<uint16_t>(), ta.lCount = L.lCount.as<uint32_t>();
-    ta.wc = c->wc[cur].as<float>();
-    ta.nOwners = c->nOwners;
-    ta.nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
-    ta.xcdGroup = c->xcdGroup;
-    ta.tileBig = L.tileBig.as<uint32_t>(), ta.bigList = L.bigList.as<uint32_t>(), ta.info = L.info.as<uint4>();
-    ta.hCap = std::min<uint32_t>(DEME_TILE_HMAX, (L.tileMaxHaloIn + 15u) & ~15u);
-    ta.lCap = std::min<uint32_t>(DEME_TILE_LMAX, (L.tileMaxList + 15u) & ~15u);
-    ta.nComp = c->nComp, ta.nAnal = c->nAnal, ta.nMass = c->nMassProps;
+    sa.t.owners = dry ? c->ownersNext.as<OwnerRec>() : c->owners.as<OwnerRec>();
+    sa.t.wc = c->wc[cur].as<float>();
+    sa.t.hCount = c->hCountIn.as<uint32_t>();
     sa.ownersNext = dry ? c->owners.as<OwnerRec>() : c->ownersNext.as<OwnerRec>();
     sa.wcNext = c->wc[cur ^ 1].as<float>();
     sa.tInfoIn = c->tInfoIn.as<uint2>(), sa.inContact = c->inContact.as<uint32_t>(), sa.inStart = c->inStart.as<uint32_t>();
     sa.acc = c->acc.as<AccRec>();
     sa.nextAcc = (!dry && c->nextAccPending) ? c->nextAcc.as<AccRec>() : nullptr;
     sa.dry = dry ? 1u : 0u;
-    unsigned nBlk = ta.nTiles;
-    if (ta.xcdGroup)
-        nBlk = (nBlk + 8u * ta.xcdGroup - 1u) / (8u * ta.xcdGroup) * (8u * ta.xcdGroup);
-    const uint32_t tabBytes = tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial);
-    ta.rs16 = tile_record_stride(ta.hCap, ta.lCap, tabBytes, 0);
-    ta.swz = ta.rs16 == tile_rec16(0) ? 1u : 0u;
-    const uint32_t ldsBytes = tile_lds_bytes(ta.hCap, ta.lCap, tabBytes, ta.rs16);
     {
         ScopedTimer tm(c, dry ? "fused_replay" : "calc_forces");
-        if (c->hp.forceModel == DEME_FORCE_HERTZIAN)
-            hipLaunchKernelGGL((k_tile_step<0>), dim3(nBlk), dim3(DEME_TILE_T), ldsBytes, c->stream, c->dp, sa);
-        else
-            hipLaunchKernelGGL((k_tile_step<1>), dim3(nBlk), dim3(DEME_TILE_T), ldsBytes, c->stream, c->dp, sa);
+        as_constant(model == 1, [&](auto frictionless) {
+            hipLaunchKernelGGL((k_tile_step<decltype(frictionless)::value ? 1 : 0>), dim3(t.nBlk), dim3(DEME_TILE_T), t.ldsBytes, c->stream,
+                               c->dp, sa);
+        });
     }
     if (dry)
         return DEME_OK;
     std::swap(c->owners, c->ownersNext);
     c->wcCur ^= 1;
-    if (c->nextAccPending) {
-        c->nextAccPending = false;
-        std::fill(c->hNextAcc.begin(), c->hNextAcc.end(), AccRec{});
-        HIPCK(hipMemsetAsync(c->nextAcc.p, 0, (size_t)c->nOwners * sizeof(AccRec), c->stream));
-    }
+    if (int rc = clear_next_acc(c))
+        return rc;
     c->conValid = false, c->conTile = false;
     c->fusedPrevValid = true;
     c->nFusedSteps++;
-    c->stepsSinceCD++;
-    c->nSteps++;
-    c->timeElapsed += (double)c->hp.h;
-    if (c->evStepDone)
-        HIPCK(hipEventRecord(c->evStepDone, c->stream));
-    return DEME_OK;
+    return finish_step(c);
 }
 
 // owners of prescribed families (rebuilt when families were uploaded); host-side: this is a set-up path
@@ -1426,9 +1442,13 @@ int rebuild_presc_list(deme_ctx* c) {
     return DEME_OK;
 }
 
-// `laterIds` (slab group, one evaluation per cross-cut contact): the owners that wait for a reverse share are left out of this launch
-// (GatherArgs::revPhase) and integrated by launch_integrate_later once the share has arrived
-int launch_integrate(deme_ctx* c, bool fused, bool heavyDone = false, bool splitLater = false) {
+// Where k_integrate finds an owner's a / alpha -- stored in `acc` by a full reduction, or gathered by itself from the contributions
+// (heavy owners excepted: launch_reduce_heavy has stored theirs) -- and which owners it moves.  NotWaiting (slab group, one
+// evaluation per cross-cut contact): the owners that wait for a reverse share are left out (GatherArgs::revPhase) and the step is
+// not over; launch_integrate_later integrates them once the share has arrived.
+enum class AccFrom { Stored, Contributions };
+enum class Owners { All, NotWaiting };
+int launch_integrate(deme_ctx* c, AccFrom from, Owners who = Owners::All) {
     ContactList& L = c->list[c->cur];
     ScopedTimer tm(c, "integrate");
     PrescArgs pa{nullptr, nullptr};
@@ -1448,13 +1468,11 @@ int launch_integrate(deme_ctx* c, bool fused, bool heavyDone = false, bool split
             pa.slot = c->prescSlot.as<uint32_t>();
         }
     }
-    if (fused) {
-        if (!heavyDone)
-            launch_reduce_heavy(c, true);
+    if (from == AccFrom::Contributions) {
         if (L.heavyOverflow)
             return c->lastStatus;
         GatherArgs ga = gather_args(c);
-        ga.revPhase = splitLater ? 1u : 0u;
+        ga.revPhase = who == Owners::NotWaiting ? 1u : 0u;
         hipLaunchKernelGGL(k_integrate<true>, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp,
                            c->owners.as<OwnerRec>(), c->acc.as<AccRec>(), ga, pa);
     } else {
@@ -1462,14 +1480,9 @@ int launch_integrate(deme_ctx* c, bool fused, bool heavyDone = false, bool split
                            c->owners.as<OwnerRec>(), c->acc.as<AccRec>(), gather_args(c), pa);
     }
     c->laterPa = pa;
-    if (splitLater)
-        return DEME_OK;  // (launch_integrate_later finishes the step)
-    if (c->nextAccPending) {  // one step only (cleanUpAcc clears the flag when it honours it, DEMPrepForceKernels.cu:14-31)
-        c->nextAccPending = false;
-        std::fill(c->hNextAcc.begin(), c->hNextAcc.end(), AccRec{});
-        HIPCK(hipMemsetAsync(c->nextAcc.p, 0, (size_t)c->nOwners * sizeof(AccRec), c->stream));
-    }
-    return DEME_OK;
+    if (who == Owners::NotWaiting)
+        return DEME_OK;
+    return clear_next_acc(c);
 }
 int launch_integrate_later(deme_ctx* c, const uint32_t* ids, uint32_t n) {
     if (n) {
@@ -1477,12 +1490,7 @@ int launch_integrate_later(deme_ctx* c, const uint32_t* ids, uint32_t n) {
         hipLaunchKernelGGL(k_integrate_list, dim3(grid_for(n)), dim3(256), 0, c->stream, c->dp, c->owners.as<OwnerRec>(),
                            c->acc.as<AccRec>(), gather_args(c), c->laterPa, ids, n);
     }
-    if (c->nextAccPending) {
-        c->nextAccPending = false;
-        std::fill(c->hNextAcc.begin(), c->hNextAcc.end(), AccRec{});
-        HIPCK(hipMemsetAsync(c->nextAcc.p, 0, (size_t)c->nOwners * sizeof(AccRec), c->stream));
-    }
-    return DEME_OK;
+    return clear_next_acc(c);
 }
 
 // a/alpha of every owner from the current contributions (stand-alone force pass and state downloads)
@@ -2158,10 +2166,9 @@ int deme_integrate(deme_ctx* c) {
     if (c->rulesFn)  // routineChecks(): family changes sit between the force evaluation and the integration (dT.cpp:2437-2443)
         if (int rc = launch_family_rules(c, c->acc.as<AccRec>()))  // the staged path always has a/alpha stored
             return rc;
-    if (int rc = launch_integrate(c, false))  // from the stored a/alpha
+    if (int rc = launch_integrate(c, AccFrom::Stored))
         return rc;
-    c->nSteps++;
-    c->timeElapsed += (double)c->hp.h;
+    advance_clock(c);
     return DEME_OK;
 }
 
@@ -2502,19 +2509,12 @@ static int step_tail_pre(deme_ctx* c) {
         return c->lastStatus;
     return DEME_OK;
 }
-// `later` / `nLater` (slab group, one evaluation per cross-cut contact): the owners that wait for a reverse share; this half of the
-// step leaves them out and returns before the step's bookkeeping -- step_tail_later finishes it when the share has arrived
-static int step_tail_post(deme_ctx* c, bool splitLater = false) {
-    if (int rc = launch_integrate(c, c->tailFused, true, splitLater))
+// Owners::NotWaiting (slab group, one evaluation per cross-cut contact): this half of the step leaves out the owners that wait for a
+// reverse share and returns before the step's bookkeeping -- step_tail_later finishes it when the share has arrived
+static int step_tail_post(deme_ctx* c, Owners who = Owners::All) {
+    if (int rc = launch_integrate(c, c->tailFused ? AccFrom::Contributions : AccFrom::Stored, who))
         return rc;
-    if (splitLater)
-        return DEME_OK;
-    c->stepsSinceCD++;
-    c->nSteps++;
-    c->timeElapsed += (double)c->hp.h;
-    if (c->evStepDone)
-        HIPCK(hipEventRecord(c->evStepDone, c->stream));
-    return DEME_OK;
+    return who == Owners::NotWaiting ? DEME_OK : finish_step(c);
 }
 static int step_tail(deme_ctx* c) {
     if (int rc = step_tail_pre(c))
@@ -2524,12 +2524,7 @@ static int step_tail(deme_ctx* c) {
 static int step_tail_later(deme_ctx* c, const uint32_t* ids, uint32_t n) {
     if (int rc = launch_integrate_later(c, ids, n))
         return rc;
-    c->stepsSinceCD++;
-    c->nSteps++;
-    c->timeElapsed += (double)c->hp.h;
-    if (c->evStepDone)
-        HIPCK(hipEventRecord(c->evStepDone, c->stream));
-    return DEME_OK;
+    return finish_step(c);
 }
 
 static bool detection_due(deme_ctx* c) {
@@ -3235,7 +3230,7 @@ int deme_halo_group_step(deme_halo_group* g, uint32_t nsteps) {
                 for (auto& s : g->slabs) {
                     if (int rc = step_tail_pre(s.ctx))
                         return gfail(g, rc, "step (reductions): %s", s.ctx->err.c_str());
-                    if (int rc = step_tail_post(s.ctx, true))
+                    if (int rc = step_tail_post(s.ctx, Owners::NotWaiting))
                         return gfail(g, rc, "step (integration beside the reverse exchange): %s", s.ctx->err.c_str());
                 }
                 for (auto& s : g->slabs) {
@@ -3828,10 +3823,11 @@ int deme_add_owner_acc(deme_ctx* c, uint32_t owner, uint32_t n, const float* acc
     if ((uint64_t)owner + n > c->nOwners || (!acc && !angAcc))
         return fail(c, DEME_ERR_INVALID, "deme_add_owner_acc: owners [%u, %u) out of range or nothing to set", owner, owner + n);
     if (c->hNextAcc.size() != c->nOwners) {
-        c->hNextAcc.assign(c->nOwners, AccRec{});
+        c->hNextAcc.resize(c->nOwners);
         if (int rc = ensure(c, c->nextAcc, std::max<size_t>(c->nOwners, 1) * sizeof(AccRec)))
             return rc;
-        HIPCK(hipMemsetAsync(c->nextAcc.p, 0, (size_t)c->nOwners * sizeof(AccRec), c->stream));
+        if (int rc = zero_next_acc(c))
+            return rc;
     }
     uint32_t lo = 0xFFFFFFFFu, hi = 0u;
     for (uint32_t k = 0; k < n; k++) {

@@ -770,10 +770,11 @@ int deme_halo_group_migrate(deme_halo_group* g, uint32_t* clumpsMoved) {
         c->list[c->cur].invalidate();
         c->conTile = false;
         c->prescDirty = true;
+        // per-owner records of the slab as it was do not carry over (as in deme_upload_scene; not clear_next_acc, which zeroes the
+        // records of the same owners after their step): without its host mirror the device copy is not read before the next
+        // deme_add_owner_acc, which sizes and zeroes both for the new owner count
         c->nextAccPending = false;
         c->hNextAcc.clear();
-        if (c->nextAcc.p)
-            hipMemsetAsync(c->nextAcc.p, 0, c->nextAcc.bytes, c->stream);
         // ---- exchange lists: what I receive sits in the two ghost sections, what I send is what I packed
         for (int k = 0; k < 2; k++) {
             HaloSide& sd = sl.side[k];

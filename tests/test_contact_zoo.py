@@ -20,8 +20,8 @@ dumbbells whose two components touch different partners, sphere-plane (the plane
 outward.  Off-centre components carry the fp32 rounding of rot_apply(R, rel) (1e-10 m) into the overlap, so they are used with
 d / r >= 0.03 only; the shallow classes use centred spheres.
 
-Materials: the tile pass takes a scene only when nMat <= 16 AND its tables fit (nComp + 2 nMat^2 + 4 nAnal <= 256 sixteen-byte pieces,
-4096 bytes with the family margins).  The second condition is the binding one: with this zoo's 7 components, 3 analytical objects
+Materials: the tile pass takes a scene only when its tables fit (nComp + 2 nMat^2 + 4 nAnal <= 256 sixteen-byte pieces, 4096 bytes
+with the family margins), which keeps nMat within the 4-bit material fields of tInfo by itself.  With this zoo's 7 components, 3 analytical objects
 and a family margin it allows NINE materials, and no scene with 16 can be tiled (2 x 16^2 = 512 pieces).  So the zoo has 9 materials
 (7 for spheres, one for the plane, one for the cylinders; pairwise distinct E, nu, CoR, mu, Crr; ~20 pair overrides), every ordered
 pair of sphere materials occurs in both roles, and the scene is built three times: 9 materials (tile kernels), 10 (the first table
