@@ -209,6 +209,9 @@ def load_library():
         "deme_set_record_contacts": [_P, C.c_int],
         "deme_download_contact_records": [_P, _P, _P, _P, _P, C.c_size_t],
         "deme_download_sphere_geometry": [_P, _P, _P, _P, _P, C.c_size_t],
+        "deme_query_owner_contacts": [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                      C.POINTER(C.c_size_t)],
+        "deme_query_host_bytes": [_P, C.POINTER(C.c_uint64)],
         "deme_change_owner_sizes": [_P, _P, _P, C.c_size_t], "deme_num_components": [_P, C.POINTER(C.c_uint32)],
         "deme_download_components": [_P, _P, _P, _P, _P, C.c_size_t], "deme_download_sphere_components": [_P, _P, C.c_size_t],
         "deme_set_template_components": [_P, C.c_uint32], "deme_multi_change_owner_sizes": [_P, _P, _P, C.c_size_t],
@@ -1020,6 +1023,38 @@ class Context:
         self._ck(self.lib.deme_download_contact_records(self.h, *[_ptr(a) for a in arrs], n),
                  "deme_download_contact_records")
         return arrs
+
+    def owner_contacts(self, owner_ids, records=False):
+        """deme_query_owner_contacts: the rows of the current list that touch one of owner_ids, selected on the device, in the
+        order contacts() lists them.  A dict of arrays: idA, idB, type, ownerA, ownerB, side (0: A's owner was asked for, 1: only
+        B's) and, with records=True, force, torqueOnly, cpA, cpB (n x 3).  The buffers start at the size of the last answer (a
+        script usually asks the same question again); when the call reports more rows they are sized for those and it is repeated."""
+        ids = np.ascontiguousarray(owner_ids, dtype=np.uint32).ravel()
+        cap = max(64, getattr(self, "_query_rows", 0))
+        unset = C.c_size_t(-1).value
+        while True:
+            out = {"idA": np.zeros(cap, np.uint32), "idB": np.zeros(cap, np.uint32), "type": np.zeros(cap, np.uint8),
+                   "ownerA": np.zeros(cap, np.uint32), "ownerB": np.zeros(cap, np.uint32), "side": np.zeros(cap, np.uint8)}
+            rec = {k: np.zeros((cap, 3), np.float32) for k in ("force", "torqueOnly", "cpA", "cpB")} if records else {}
+            ptrs = [_ptr(out[k]) for k in ("idA", "idB", "type", "ownerA", "ownerB", "side")]
+            ptrs += [_ptr(rec[k]) if records else None for k in ("force", "torqueOnly", "cpA", "cpB")]
+            n = C.c_size_t(unset)
+            rc = self.lib.deme_query_owner_contacts(self.h, _ptr(ids), ids.size, int(bool(records)), *ptrs, cap, C.byref(n))
+            if rc == 0:
+                break
+            if n.value == unset or n.value <= cap:  # a refusal ("too small" leaves the count)
+                self._ck(rc, "deme_query_owner_contacts")
+            cap = int(n.value)
+        m = int(n.value)
+        self._query_rows = m
+        out.update(rec)
+        return {k: v[:m].copy() for k, v in out.items()}
+
+    def query_host_bytes(self):
+        """bytes owner_contacts calls have copied to the host since the context was created (count read-backs and hit rows)"""
+        v = C.c_uint64(0)
+        self._ck(self.lib.deme_query_host_bytes(self.h, C.byref(v)), "deme_query_host_bytes")
+        return int(v.value)
 
     def sphere_geometry(self):
         n = self.n_spheres

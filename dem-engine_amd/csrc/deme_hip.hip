@@ -47,6 +47,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_migrate.h"
 #include "deme_mesh_kernels.h"
 #include "deme_resize.h"
+#include "deme_query.h"
 
 using namespace deme_dev;
 
@@ -124,6 +125,10 @@ struct deme_ctx {
     std::vector<float4> hComp;
     uint32_t nTemplateComps = 0;
     DevBuf rsMark, rsKeys[2], rsRuns, rsUKeys, rsIdx, rsOldR, rsUses, rsRemap;  // resize scratch (deme_resize.h), allocated by the first resize
+    // owner-filtered contact queries (deme_query.h): marks per owner, the hit rows and their records, the hit counter; allocated by
+    // the first query and kept, so that a script asking every frame selects once per call
+    DevBuf qMark, qHits, qRecs, qCtr;
+    uint64_t qHostBytes = 0;  // bytes the queries have copied to the host so far (deme_query_host_bytes)
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
     DevBuf geo, binLo, binN, counts, offsets, incKeys[2], incVals[2], keysRaw, keysMid, keysSorted[2], wc[2], ctr, segCtr,
@@ -1594,7 +1599,7 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->wc[0], &c->wc[1], &c->ctr,
                      &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
-                     &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap};
+                     &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -4448,6 +4453,116 @@ int deme_download_sphere_components(deme_ctx* c, uint16_t* comp, size_t cap) {
     HIPCK(hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < n; k++)
         comp[order_sphere_out(c, (uint32_t)k)] = h[k].comp;
+    return DEME_OK;
+}
+
+// ---- contacts of a few owners (deme_query.h) ----------------------------------------------------------------------------------
+// The selection runs on the engine's list as it stands; what comes to the host is the hit count and the hit rows, which are then
+// put in the caller's canonical order by their caller-id keys (keys of a list are unique) -- the sub-sequence of what
+// deme_download_contacts returns, without the caller's view of the whole list (order_current_view) ever being built.
+int deme_query_owner_contacts(deme_ctx* c, const uint32_t* ownerIds, size_t nOwners, int withRecords, uint32_t* idA, uint32_t* idB,
+                              uint8_t* type, uint32_t* ownerA, uint32_t* ownerB, uint8_t* side, float* force, float* torqueOnly,
+                              float* cpA, float* cpB, size_t cap, size_t* nOut) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (!nOut || (nOwners && !ownerIds))
+        return fail(c, DEME_ERR_INVALID, "deme_query_owner_contacts: null %s", nOut ? "owner id array" : "nOut");
+    for (size_t i = 0; i < nOwners; i++)
+        if (ownerIds[i] >= c->nOwners)
+            return fail(c, DEME_ERR_INVALID, "deme_query_owner_contacts: owner id %u is out of range (%u owners)", ownerIds[i], c->nOwners);
+    if (withRecords && !c->record)
+        return fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
+    if (withRecords && c->seeded)
+        return fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+    std::vector<uint32_t> ids(ownerIds, ownerIds + nOwners);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const size_t n = c->haveList ? (size_t)c->nContacts : 0, nIds = ids.size();
+    uint32_t nHit = 0;
+    if (n && nIds) {
+        if (ensure(c, c->qMark, (size_t)c->nOwners) || ensure(c, c->qCtr, 256) || ensure(c, c->stage, nIds * 4))
+            return c->lastStatus;
+        HIPCK(hipMemsetAsync(c->qMark.p, 0, (size_t)c->nOwners, c->stream));
+        HIPCK(hipMemcpyAsync(c->stage.p, ids.data(), nIds * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_query_mark, dim3(grid_for(nIds)), dim3(256), 0, c->stream, (uint32_t)nIds, c->stage.as<uint32_t>(),
+                           c->qMark.as<uint8_t>());
+        QueryTables t{};
+        t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
+        t.s2e = c->dp.s2e, t.o2e = c->dp.o2e;
+        t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
+        size_t want = 256;  // rows of scratch a first query starts with
+        for (int pass = 0;; pass++) {
+            if (ensure(c, c->qHits, want * sizeof(QueryHit)) || (withRecords && ensure(c, c->qRecs, want * 48)))
+                return c->lastStatus;
+            // the kernel's bound is what the allocations hold, whatever was asked for
+            size_t rows = c->qHits.bytes / sizeof(QueryHit);
+            if (withRecords)
+                rows = std::min(rows, c->qRecs.bytes / 48);
+            rows = std::min<size_t>(rows, 0xFFFFFFFFu);
+            HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
+            hipLaunchKernelGGL(k_query_select, dim3(grid_for(n)), dim3(256), 0, c->stream, (uint32_t)n,
+                               c->keysSorted[c->keysCur].as<uint64_t>(), t, c->qMark.as<uint8_t>(),
+                               withRecords ? c->rec[0].as<float>() : nullptr, withRecords ? c->rec[1].as<float>() : nullptr,
+                               withRecords ? c->rec[2].as<float>() : nullptr, withRecords ? c->rec[3].as<float>() : nullptr,
+                               c->qHits.as<QueryHit>(), withRecords ? c->qRecs.as<float>() : nullptr, (uint32_t)rows,
+                               c->qCtr.as<uint32_t>());
+            HIPCK(hipMemcpyAsync(&nHit, c->qCtr.p, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCK(hipStreamSynchronize(c->stream));
+            c->qHostBytes += 4;
+            if (nHit <= rows)
+                break;
+            if (pass)  // (the list cannot change between two selections)
+                return fail(c, DEME_ERR_OVERFLOW, "deme_query_owner_contacts: %u hits after the scratch was sized for them", nHit);
+            want = nHit;
+        }
+    }
+    *nOut = nHit;
+    if (cap < nHit)
+        return fail(c, DEME_ERR_INVALID, "buffer too small: need %zu", (size_t)nHit);
+    if (!nHit)
+        return DEME_OK;
+    std::vector<QueryHit> h(nHit);
+    std::vector<float> r(withRecords ? (size_t)nHit * 12 : 0);
+    HIPCK(hipMemcpyAsync(h.data(), c->qHits.p, (size_t)nHit * sizeof(QueryHit), hipMemcpyDeviceToHost, c->stream));
+    if (withRecords)
+        HIPCK(hipMemcpyAsync(r.data(), c->qRecs.p, (size_t)nHit * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->qHostBytes += (uint64_t)nHit * (sizeof(QueryHit) + (withRecords ? 48 : 0));
+    std::vector<uint32_t> perm(nHit);
+    for (uint32_t i = 0; i < nHit; i++)
+        perm[i] = i;
+    std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h[a].key < h[b].key; });
+    float* dst[4] = {force, torqueOnly, cpA, cpB};
+    for (uint32_t i = 0; i < nHit; i++) {
+        const QueryHit& q = h[perm[i]];
+        const uint32_t cls = key_class(q.key);
+        if (idA)
+            idA[i] = key_a(q.key);
+        if (idB)
+            idB[i] = key_b(q.key);
+        if (type)
+            type[i] = cls == DEME_KEY_CLASS_SS   ? DEME_SPHERE_SPHERE_CONTACT
+                      : cls == DEME_KEY_CLASS_SM ? DEME_SPHERE_MESH_CONTACT
+                      : c->hObjType[key_b(q.key)] == DEME_ANAL_OBJ_TYPE_PLANE ? DEME_SPHERE_PLANE_CONTACT
+                                                                              : DEME_SPHERE_CYL_CONTACT;
+        if (ownerA)
+            ownerA[i] = q.ownerA;
+        if (ownerB)
+            ownerB[i] = q.ownerB;
+        if (side)
+            side[i] = (uint8_t)q.side;
+        if (withRecords)
+            for (int k = 0; k < 4; k++)
+                if (dst[k])
+                    memcpy(dst[k] + 3 * (size_t)i, r.data() + 12 * (size_t)perm[i] + 3 * k, 12);
+    }
+    return DEME_OK;
+}
+
+int deme_query_host_bytes(const deme_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes)
+        return DEME_ERR_INVALID;
+    *bytes = c->qHostBytes;
     return DEME_OK;
 }
 

@@ -1350,42 +1350,53 @@ class DEMSolver {
     /// `owners` on either side and a non-negligible force; the force as the tracked owner feels it (A's side first), the contact
     /// point in global coordinates, optionally the contact torque in the owner's local or the global frame.  Needs the
     /// per-contact records (on unless SetNoForceRecord).  Returns the number of pairs.
+    /// On one context the rows come from a device-side selection (deme_query_owner_contacts) and only they cross the bus; a
+    /// decomposed run keeps the whole-list path below (owner_contact_forces_whole_list), which is also what DEME_QUERY_HOST=1
+    /// selects for the tests that hold the two against each other.
     size_t GetOwnerContactForces(const std::vector<bodyID_t>& owners, std::vector<float3>& points, std::vector<float3>& forces,
                                  std::vector<float3>* torques = nullptr, bool torque_in_local = false) {
-        const Snapshot sn = snapshot(true);
-        const size_t nc = sn.idA.size();
-        std::vector<float> cpB(3 * nc);
-        {
-            std::vector<float> f(3 * nc), t(3 * nc), a(3 * nc);
-            dl_contact_records(f.data(), t.data(), a.data(), cpB.data(), nc);
-        }
-        std::vector<bodyID_t> sorted = owners;
-        std::sort(sorted.begin(), sorted.end());
+        if (m_multi || query_on_host())
+            return owner_contact_forces_whole_list(owners, points, forces, torques, torque_in_local);
+        std::vector<bodyID_t> known;  // (an id past the last owner concerns no contact: it is left out, as the whole-list path ignores it)
+        for (bodyID_t o : owners)
+            if ((size_t)o < m_n_owners)
+                known.push_back(o);
+        const OwnerContacts oc = query_owner_contacts(known, true);
         points.clear(), forces.clear();
         if (torques)
             torques->clear();
-        for (size_t i = 0; i < nc; i++) {
-            const uint8_t ty = sn.type[i];
-            const bodyID_t oA = m_keep.sphOwner[sn.idA[i]];
-            const bodyID_t oB = ty == 1 ? m_keep.sphOwner[sn.idB[i]] : ty == 2 ? m_keep.triOwner[sn.idB[i]] : m_keep.objOwner[sn.idB[i]];
-            bool isA;
-            if (std::binary_search(sorted.begin(), sorted.end(), oA))
-                isA = true;
-            else if (std::binary_search(sorted.begin(), sorted.end(), oB))
-                isA = false;
-            else
-                continue;
-            float3 force = {sn.F[3 * i], sn.F[3 * i + 1], sn.F[3 * i + 2]}, torque = {sn.T[3 * i], sn.T[3 * i + 1], sn.T[3 * i + 2]};
+        if (!oc.n)
+            return 0;
+        // orientation and position: the columns of one state download, decoded for the owners of the hit rows only
+        const size_t n = m_n_owners;
+        std::vector<uint64_t> vid(n);
+        std::vector<uint16_t> lx(n), ly(n), lz(n);
+        std::vector<float> qw(n), qx(n), qy(n), qz(n);
+        DemeOwnerState st{};
+        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
+        st.oriQw = qw.data(), st.oriQx = qx.data(), st.oriQy = qy.data(), st.oriQz = qz.data();
+        dl_state(&st);
+        const float vs = (float)m_p.voxelSize, l = (float)m_p.l;
+        auto com_of = [&](size_t i) {  // (as snapshot(): voxelIDToPosition<float, ...> then + LBF, all fp32)
+            const uint64_t vx = vid[i] & ((1ull << m_p.nvXp2) - 1), vy = (vid[i] >> m_p.nvXp2) & ((1ull << m_p.nvYp2) - 1),
+                           vz = vid[i] >> (m_p.nvXp2 + m_p.nvYp2);
+            return make_float3(((float)vx * vs + (float)lx[i] * l) + m_p.LBFX, ((float)vy * vs + (float)ly[i] * l) + m_p.LBFY,
+                               ((float)vz * vs + (float)lz[i] * l) + m_p.LBFZ);
+        };
+        for (size_t i = 0; i < oc.n; i++) {
+            const bool isA = oc.side[i] == 0;
+            float3 force = {oc.F[3 * i], oc.F[3 * i + 1], oc.F[3 * i + 2]}, torque = {oc.T[3 * i], oc.T[3 * i + 1], oc.T[3 * i + 2]};
             auto len = [](float3 v) { return std::sqrt(v.x * v.x + v.y * v.y + v.z * v.z); };
             if ((torques ? len(force) + len(torque) : len(force)) < DEME_TINY_FLOAT_HOST)
                 continue;
-            float3 pnt = isA ? make_float3(sn.cpA[3 * i], sn.cpA[3 * i + 1], sn.cpA[3 * i + 2]) : make_float3(cpB[3 * i], cpB[3 * i + 1], cpB[3 * i + 2]);
-            const bodyID_t o = isA ? oA : oB;
+            float3 pnt = isA ? make_float3(oc.cpA[3 * i], oc.cpA[3 * i + 1], oc.cpA[3 * i + 2])
+                             : make_float3(oc.cpB[3 * i], oc.cpB[3 * i + 1], oc.cpB[3 * i + 2]);
+            const bodyID_t o = isA ? oc.ownerA[i] : oc.ownerB[i];
             if (!isA) {
                 force = force * -1.f;
                 torque = torque * -1.f;
             }
-            const float4 q = sn.q[o];
+            const float4 q = {qx[o], qy[o], qz[o], qw[o]};
             if (torques) {  // the torque-only force becomes a torque about the contact point, in the owner's frame
                 rotate(torque, {-q.x, -q.y, -q.z, q.w});
                 torque = {pnt.y * torque.z - pnt.z * torque.y, pnt.z * torque.x - pnt.x * torque.z, pnt.x * torque.y - pnt.y * torque.x};
@@ -1394,10 +1405,49 @@ class DEMSolver {
                 torques->push_back(torque);
             }
             rotate(pnt, q);
-            points.push_back(pnt + sn.com[o]);
+            points.push_back(pnt + com_of(o));
             forces.push_back(force);
         }
         return points.size();
+    }
+    /// GetOwnerContactClumps (API.h:430, APIPublic.cpp:323-395): the clumps on the contact list with `ownerID`, one entry per
+    /// listed pair, in list order.  Potential contacts: no force filter, no de-duplication (the reference applies neither).  A
+    /// clump owner: the other side's owner of every sphere--sphere row it is on; a mesh owner: sphere A's owner of every
+    /// sphere--mesh row whose triangle is its own; an analytical owner: sphere A's owner of every analytical row whose component
+    /// is its own.
+    std::vector<bodyID_t> GetOwnerContactClumps(bodyID_t ownerID) {
+        if ((size_t)ownerID >= m_n_owners)
+            throw std::runtime_error("GetOwnerContactClumps: owner " + std::to_string(ownerID) + " does not exist (" +
+                                     std::to_string(m_n_owners) + " owners)");
+        std::vector<bodyID_t> out;
+        // owners are numbered: clumps, analytical objects, meshes (tracker_first_owner)
+        const bool clump = (size_t)ownerID < m_n_clumps, mesh = (size_t)ownerID >= m_n_owners - m_meshes.size();
+        auto take = [&](uint8_t ty, bodyID_t oA, bodyID_t oB) {
+            if (clump) {
+                if (ty != DEME_SPHERE_SPHERE_CONTACT)
+                    return;
+                if (oA == ownerID)
+                    out.push_back(oB);
+                else if (oB == ownerID)
+                    out.push_back(oA);
+            } else if (oB == ownerID && (mesh ? ty == DEME_SPHERE_MESH_CONTACT : ty >= DEME_SPHERE_PLANE_CONTACT)) {
+                out.push_back(oA);
+            }
+        };
+        if (m_multi) {  // the merged list of the slabs, filtered here (global ids)
+            const size_t nc = n_contacts();
+            std::vector<uint32_t> a(nc), b(nc);
+            std::vector<uint8_t> ty(nc);
+            dl_contacts(a.data(), b.data(), ty.data(), nullptr, nc);
+            for (size_t i = 0; i < nc; i++)
+                take(ty[i], m_keep.sphOwner[a[i]],
+                     ty[i] == 1 ? m_keep.sphOwner[b[i]] : ty[i] == 2 ? m_keep.triOwner[b[i]] : m_keep.objOwner[b[i]]);
+            return out;
+        }
+        const OwnerContacts oc = query_owner_contacts({ownerID}, false);
+        for (size_t i = 0; i < oc.n; i++)
+            take(oc.type[i], oc.ownerA[i], oc.ownerB[i]);
+        return out;
     }
     /// ShowTimingStats / ShowThreadCollaborationStats (API.h:1290-1300): the kernels' mean times from HIP events
     void ShowTimingStats() {
@@ -1973,6 +2023,99 @@ class DEMSolver {
         else
             check(deme_download_contact_records(m_ctx, f, t, a, b, nc));
     }
+    /// GetOwnerContactForces over downloads of the whole list: a decomposed run (the merged list's flip rules live in
+    /// deme_multi_download_contact_records), and DEME_QUERY_HOST=1
+    size_t owner_contact_forces_whole_list(const std::vector<bodyID_t>& owners, std::vector<float3>& points, std::vector<float3>& forces,
+                                           std::vector<float3>* torques, bool torque_in_local) {
+        const Snapshot sn = snapshot(true);
+        const size_t nc = sn.idA.size();
+        std::vector<float> cpB(3 * nc);
+        {
+            std::vector<float> f(3 * nc), t(3 * nc), a(3 * nc);
+            dl_contact_records(f.data(), t.data(), a.data(), cpB.data(), nc);
+        }
+        std::vector<bodyID_t> sorted = owners;
+        std::sort(sorted.begin(), sorted.end());
+        points.clear(), forces.clear();
+        if (torques)
+            torques->clear();
+        for (size_t i = 0; i < nc; i++) {
+            const uint8_t ty = sn.type[i];
+            const bodyID_t oA = m_keep.sphOwner[sn.idA[i]];
+            const bodyID_t oB = ty == 1 ? m_keep.sphOwner[sn.idB[i]] : ty == 2 ? m_keep.triOwner[sn.idB[i]] : m_keep.objOwner[sn.idB[i]];
+            bool isA;
+            if (std::binary_search(sorted.begin(), sorted.end(), oA))
+                isA = true;
+            else if (std::binary_search(sorted.begin(), sorted.end(), oB))
+                isA = false;
+            else
+                continue;
+            float3 force = {sn.F[3 * i], sn.F[3 * i + 1], sn.F[3 * i + 2]}, torque = {sn.T[3 * i], sn.T[3 * i + 1], sn.T[3 * i + 2]};
+            auto len = [](float3 v) { return std::sqrt(v.x * v.x + v.y * v.y + v.z * v.z); };
+            if ((torques ? len(force) + len(torque) : len(force)) < DEME_TINY_FLOAT_HOST)
+                continue;
+            float3 pnt = isA ? make_float3(sn.cpA[3 * i], sn.cpA[3 * i + 1], sn.cpA[3 * i + 2]) : make_float3(cpB[3 * i], cpB[3 * i + 1], cpB[3 * i + 2]);
+            const bodyID_t o = isA ? oA : oB;
+            if (!isA) {
+                force = force * -1.f;
+                torque = torque * -1.f;
+            }
+            const float4 q = sn.q[o];
+            if (torques) {  // the torque-only force becomes a torque about the contact point, in the owner's frame
+                rotate(torque, {-q.x, -q.y, -q.z, q.w});
+                torque = {pnt.y * torque.z - pnt.z * torque.y, pnt.z * torque.x - pnt.x * torque.z, pnt.x * torque.y - pnt.y * torque.x};
+                if (!torque_in_local)
+                    rotate(torque, q);
+                torques->push_back(torque);
+            }
+            rotate(pnt, q);
+            points.push_back(pnt + sn.com[o]);
+            forces.push_back(force);
+        }
+        return points.size();
+    }
+    /// the rows of the context's list that touch one of `owners`, selected on the device (deme_query_owner_contacts), in list
+    /// order; the per-contact records with them when asked for.  One context only.
+    struct OwnerContacts {
+        size_t n = 0;
+        std::vector<uint32_t> idA, idB, ownerA, ownerB;
+        std::vector<uint8_t> type, side;
+        std::vector<float> F, T, cpA, cpB;
+    };
+    OwnerContacts query_owner_contacts(const std::vector<bodyID_t>& owners, bool records) {
+        OwnerContacts oc;
+        for (size_t cap = m_query_rows;;) {  // the last answer's size is the first guess: a script usually asks the same question again
+            oc.idA.resize(cap), oc.idB.resize(cap), oc.ownerA.resize(cap), oc.ownerB.resize(cap), oc.type.resize(cap), oc.side.resize(cap);
+            if (records)
+                oc.F.resize(3 * cap), oc.T.resize(3 * cap), oc.cpA.resize(3 * cap), oc.cpB.resize(3 * cap);
+            const size_t unset = ~(size_t)0;
+            size_t n = unset;
+            const int rc = deme_query_owner_contacts(m_ctx, owners.data(), owners.size(), records ? 1 : 0, oc.idA.data(), oc.idB.data(),
+                                                     oc.type.data(), oc.ownerA.data(), oc.ownerB.data(), oc.side.data(),
+                                                     records ? oc.F.data() : nullptr, records ? oc.T.data() : nullptr,
+                                                     records ? oc.cpA.data() : nullptr, records ? oc.cpB.data() : nullptr, cap, &n);
+            if (rc && (n == unset || n <= cap))  // a refusal; "too small" leaves the count
+                check(rc);
+            if (!rc) {
+                oc.n = n;
+                break;
+            }
+            cap = n;
+        }
+        m_query_rows = std::max<size_t>(oc.n, 64);
+        oc.idA.resize(oc.n), oc.idB.resize(oc.n), oc.ownerA.resize(oc.n), oc.ownerB.resize(oc.n), oc.type.resize(oc.n), oc.side.resize(oc.n);
+        if (records)
+            oc.F.resize(3 * oc.n), oc.T.resize(3 * oc.n), oc.cpA.resize(3 * oc.n), oc.cpB.resize(3 * oc.n);
+        return oc;
+    }
+    /// DEME_QUERY_HOST=1 (tests): GetOwnerContactForces takes the whole-list path on one context too
+    static bool query_on_host() {
+        static const bool on = [] {
+            const char* e = std::getenv("DEME_QUERY_HOST");
+            return e && std::atoi(e) != 0;
+        }();
+        return on;
+    }
     void add_owner_acc(uint32_t owner, uint32_t n, const float* acc, const float* angAcc) {
         if (m_multi)
             mcheck(deme_multi_add_owner_acc(m_multi, owner, n, acc, angAcc));
@@ -2010,6 +2153,7 @@ class DEMSolver {
     uint8_t m_family_flags[DEME_NUM_FAMILIES] = {0};
     DemeParams m_p{};
     size_t m_n_clumps = 0, m_n_owners = 0;
+    size_t m_query_rows = 64;  // rows the last owner query returned: the first guess of the next one's buffers
     // a user model's owner / geometry wildcard arrays across a scene re-upload (UpdateClumps, ResortClumps)
     struct SavedWildcards {
         std::vector<std::vector<float>> owner, sphere, tri, anal;
@@ -3164,6 +3308,8 @@ class DEMTracker {
     }
     void AddAngAcc(const std::vector<float3>& angAcc) { add_many(angAcc, false); }
     /// every contact force on one tracked owner / on all of them (AuxClasses.h:335-410)
+    /// GetContactClumps (AuxClasses.h:174): the clumps on the contact list with the tracked owner
+    std::vector<bodyID_t> GetContactClumps(size_t offset = 0) { return m_sys->GetOwnerContactClumps(GetOwnerID(offset)); }
     size_t GetContactForces(std::vector<float3>& points, std::vector<float3>& forces, size_t offset = 0) {
         return m_sys->GetOwnerContactForces({GetOwnerID(offset)}, points, forces);
     }

@@ -299,6 +299,22 @@ int deme_seed_contacts(deme_ctx* ctx, const uint32_t* idA, const uint32_t* idB, 
  * points; each nContacts*3 floats; any pointer may be NULL. Recording must have been enabled. */
 int deme_set_record_contacts(deme_ctx* ctx, int enable);
 int deme_download_contact_records(deme_ctx* ctx, float* force, float* torqueOnly, float* cpA, float* cpB, size_t cap);
+/* The contacts of a few owners, selected on the device (reference: getContactForcesConcerningOwners,
+ * algorithms/DEMDynamicMisc.cu:14-100, DEM/dT.cpp:2740-2852; DEMSolver::GetOwnerContactClumps, DEM/APIPublic.cpp:323-395): every
+ * row of the current list whose sphere A or whose geometry B belongs to one of ownerIds (the caller's numbering; a repeated id
+ * counts once).  Rows come back in the order deme_download_contacts lists them -- the result is a sub-sequence of that list,
+ * whether or not the engine keeps an order of its own -- with idA, idB, type and, when withRecords != 0, the four per-contact
+ * records bitwise what deme_download_contacts / deme_download_contact_records give for the same rows; ownerA / ownerB: the owners
+ * of the two geometries; side: 0 when A's owner is one of ownerIds, 1 when only B's is.  Any output pointer may be NULL.  *nOut
+ * receives the hit count; with cap < *nOut no row is written and the call returns DEME_ERR_INVALID, so a caller asks with cap 0,
+ * sizes its arrays and asks again.  Only the count and the hit rows come to the host (24 bytes a row, 72 with records):
+ * deme_query_host_bytes reports what these calls have copied since the context was created (4 bytes per count read-back --
+ * two when the scratch had to grow -- and the rows).  Refused, with nothing written (nOut included): an owner id out of
+ * range; withRecords while recording is off or the list is a seed (the messages of deme_download_contact_records). */
+int deme_query_owner_contacts(deme_ctx* ctx, const uint32_t* ownerIds, size_t nOwners, int withRecords, uint32_t* idA, uint32_t* idB,
+                              uint8_t* type, uint32_t* ownerA, uint32_t* ownerB, uint8_t* side, float* force, float* torqueOnly,
+                              float* cpA, float* cpB, size_t cap, size_t* nOut);
+int deme_query_host_bytes(const deme_ctx* ctx, uint64_t* bytes);
 /* per-sphere world position (LBF-shifted frame, as kT sees it) and inflated radius */
 int deme_download_sphere_geometry(deme_ctx* ctx, double* X, double* Y, double* Z, float* R, size_t cap);
 
