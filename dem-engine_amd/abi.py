@@ -212,6 +212,8 @@ def load_library():
         "deme_query_owner_contacts": [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                       C.POINTER(C.c_size_t)],
         "deme_query_host_bytes": [_P, C.POINTER(C.c_uint64)],
+        "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
+        "deme_sort_keys_u64": [C.c_int, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P],
         "deme_change_owner_sizes": [_P, _P, _P, C.c_size_t], "deme_num_components": [_P, C.POINTER(C.c_uint32)],
         "deme_download_components": [_P, _P, _P, _P, _P, C.c_size_t], "deme_download_sphere_components": [_P, _P, C.c_size_t],
         "deme_set_template_components": [_P, C.c_uint32], "deme_multi_change_owner_sizes": [_P, _P, _P, C.c_size_t],
@@ -229,6 +231,8 @@ def load_library():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
+    lib.deme_sort_tile_keys.argtypes = []
+    lib.deme_sort_tile_keys.restype = C.c_uint
     lib.deme_halo_unique_id.argtypes = [_P]
     lib.deme_halo_unique_id.restype = C.c_int
     lib.deme_halo_group_create.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]
@@ -688,6 +692,35 @@ def exported_symbols():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def sort_tile_keys():
+    """keys one workgroup of the project's radix sort takes (the sizes around which its tests place their cases)"""
+    return int(load_library().deme_sort_tile_keys())
+
+
+def sort_pairs_u32(keys, vals, begin_bit, end_bit, force_own=True, device=0):
+    """The detection's stable radix sort alone: (keys, vals) ordered by the bits [begin_bit, end_bit) of the uint32 keys.
+    force_own: the project's sort whatever the size; otherwise what the detection's call sites take at this size."""
+    keys, vals = np.ascontiguousarray(keys, np.uint32), np.ascontiguousarray(vals, np.uint32)
+    assert keys.shape == vals.shape and keys.ndim == 1
+    ko, vo = np.empty_like(keys), np.empty_like(vals)
+    rc = load_library().deme_sort_pairs_u32(device, _ptr(keys), _ptr(vals), keys.size, begin_bit, end_bit, int(bool(force_own)), _ptr(ko),
+                                            _ptr(vo))
+    if rc:
+        raise DemeError(f"deme_sort_pairs_u32 failed with code {rc}")
+    return ko, vo
+
+
+def sort_keys_u64(keys, begin_bit, end_bit, force_own=True, device=0):
+    """As sort_pairs_u32, for uint64 keys alone."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    assert keys.ndim == 1
+    ko = np.empty_like(keys)
+    rc = load_library().deme_sort_keys_u64(device, _ptr(keys), keys.size, begin_bit, end_bit, int(bool(force_own)), _ptr(ko))
+    if rc:
+        raise DemeError(f"deme_sort_keys_u64 failed with code {rc}")
+    return ko
 
 
 def jit_probe(src, wildcard_names=(), prerequisites="", owner_wildcards=(), geo_wildcards=()):

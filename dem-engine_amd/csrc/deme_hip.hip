@@ -48,6 +48,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_mesh_kernels.h"
 #include "deme_resize.h"
 #include "deme_query.h"
+#include "deme_sort.h"
 
 using namespace deme_dev;
 
@@ -359,6 +360,33 @@ int with_temp(deme_ctx* c, DevBuf& tmp, Call&& call) {
     bytes = tmp.bytes;
     HIPCK(call(tmp.p, bytes));
     return DEME_OK;
+}
+
+// The detection's radix sorts: the project's own sort (deme_sort.h) from `ownFrom` entries on, rocprim with RocCfg below -- a pass
+// of the own sort is three launches whatever n is, which a list of a few thousand entries does not earn back.  The thresholds
+// are where tools/sortbench finds the two level on MI355X (profiles/r07/sort_ab.txt).  `cap`: the capacity of the arena the list
+// lives in; the scratch is sized for it, so that a list growing inside its arena never makes a sort allocate.
+// -DDEME_SORT_ROCPRIM=1 builds a library whose every site takes rocprim (A/B runs: make variant).
+#ifndef DEME_SORT_ROCPRIM
+#define DEME_SORT_ROCPRIM 0
+#endif
+// (each the smallest size measured at which the own sort is ahead, a tenth of which rocprim is; us, best of 9 -- at 82 000 pairs
+// one repeat of nine was an outlier, the medians are 45 against 52)
+constexpr size_t DEME_SORT_OWN_FROM_INCIDENCES = 82000;  // (bin, sphere) pairs, 21-22 key bits: 45 us against 51
+constexpr size_t DEME_SORT_OWN_FROM_KEYS64 = 430000;     // contact keys, 24 key bits from bit 31: 48 us against 120
+constexpr size_t DEME_SORT_OWN_FROM_RECORDS = 180000;    // crossing records by B owner, <= 20 key bits: 46 us against 60
+inline bool sort_takes_own(size_t n, size_t cap, size_t ownFrom) {
+    return !DEME_SORT_ROCPRIM && n >= ownFrom && std::max(n, cap) <= deme_sort::MAX_N;
+}
+template <class RocCfg, bool HAS_V, typename K>
+hipError_t deme_radix_sort(void* tmp, size_t& bytes, const K* keysIn, K* keysOut, const uint32_t* valsIn, uint32_t* valsOut, size_t n, size_t cap,
+                           unsigned beginBit, unsigned endBit, size_t ownFrom, hipStream_t st) {
+    if (sort_takes_own(n, cap, ownFrom))
+        return deme_sort::radix_sort<K, HAS_V>(tmp, bytes, keysIn, keysOut, valsIn, valsOut, n, cap, beginBit, endBit, st);
+    if constexpr (HAS_V)
+        return rocprim::radix_sort_pairs<RocCfg>(tmp, bytes, keysIn, keysOut, valsIn, valsOut, n, beginBit, endBit, st);
+    else
+        return rocprim::radix_sort_keys<RocCfg>(tmp, bytes, keysIn, keysOut, n, beginBit, endBit, st);
 }
 
 inline unsigned grid_for(size_t n, unsigned block = 256) { return (unsigned)((n + block - 1) / block); }
@@ -684,10 +712,12 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             // bin ids of up to 22 bits: two passes of 11 bits (16 keys per thread) take as long as three of 8 and save a pass's launches
             const bool twoPass = bits > 16 && bits <= 22;
             if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                    return twoPass ? rocprim::radix_sort_pairs<DemeRadixCfg<11, 16>>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
-                                                                                     c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P, 0, bits, st)
-                                   : rocprim::radix_sort_pairs<DemeRadixCfg<8>>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
-                                                                                c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P, 0, bits, st);
+                    return twoPass ? deme_radix_sort<DemeRadixCfg<11, 16>, true>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
+                                                                                 c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P,
+                                                                                 (size_t)c->incCap, 0, bits, DEME_SORT_OWN_FROM_INCIDENCES, st)
+                                   : deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
+                                                                            c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P,
+                                                                            (size_t)c->incCap, 0, bits, DEME_SORT_OWN_FROM_INCIDENCES, st);
                 }))
                 return rc;
             const uint32_t nWin = (uint32_t)grid_for(P, SW_T);
@@ -813,7 +843,8 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
                 return rc;
             uint64_t* mid = c->keysMid.as<uint64_t>();
             if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                    return rocprim::radix_sort_keys<DemeRadixCfg<8>>(tmp, bytes, rawKeys, mid, (size_t)nC, 31, 33 + bitsA, st);
+                    return deme_radix_sort<DemeRadixCfg<8>, false>(tmp, bytes, rawKeys, mid, nullptr, nullptr, (size_t)nC, (size_t)c->cntCap, 31,
+                                                                   33 + bitsA, DEME_SORT_OWN_FROM_KEYS64, st);
                 }))
                 return rc;
             hipLaunchKernelGGL(k_segment_rank_sort, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, mid,
@@ -974,8 +1005,9 @@ int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st
         const unsigned obits = bits_for(c->nOwners, 32);
         if (nR) {
             if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                    return rocprim::radix_sort_pairs<DemeRadixCfg<10>>(tmp, bytes, L.remKey[0].as<uint32_t>(), L.remKey[1].as<uint32_t>(),
-                                                                       L.remVal.as<uint32_t>(), L.rIdx.as<uint32_t>(), (size_t)nR, 0, obits, st);
+                    return deme_radix_sort<DemeRadixCfg<10>, true>(tmp, bytes, L.remKey[0].as<uint32_t>(), L.remKey[1].as<uint32_t>(),
+                                                                   L.remVal.as<uint32_t>(), L.rIdx.as<uint32_t>(), (size_t)nR, (size_t)c->cntCap, 0, obits,
+                                                                   DEME_SORT_OWN_FROM_RECORDS, st);
                 }))
                 return rc;
             hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nR)), dim3(256), 0, st, nR, L.remKey[1].as<uint32_t>(), c->nOwners,
@@ -4564,6 +4596,77 @@ int deme_query_host_bytes(const deme_ctx* c, uint64_t* bytes) {
         return DEME_ERR_INVALID;
     *bytes = c->qHostBytes;
     return DEME_OK;
+}
+
+// ---- the radix sort alone, on host arrays (tests/test_radix_sort.py) -----------------------------
+namespace {
+struct SortScratch {  // device copies of one call's arrays, freed however the call ends
+    std::vector<void*> held;
+    ~SortScratch() {
+        for (void* p : held)
+            (void)hipFree(p);
+    }
+    template <typename T>
+    T* room(size_t n) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess)
+            return nullptr;
+        held.push_back(p);
+        return reinterpret_cast<T*>(p);
+    }
+};
+template <class RocCfg, bool HAS_V, typename K>
+int sort_host_arrays(int device, const K* keys, const uint32_t* vals, size_t n, unsigned beginBit, unsigned endBit, size_t ownFrom, K* keysOut,
+                     uint32_t* valsOut) {
+    if (endBit < beginBit || endBit > 8 * sizeof(K) || (n && (!keys || !keysOut || (HAS_V && (!vals || !valsOut)))))
+        return DEME_ERR_INVALID;
+    if (!ownFrom && (DEME_SORT_ROCPRIM || n > deme_sort::MAX_N))  // the own sort was asked for and this build or size has none
+        return DEME_ERR_INVALID;
+    if (!n)
+        return DEME_OK;
+    if (hipSetDevice(device) != hipSuccess)
+        return DEME_ERR_HIP;
+    SortScratch s;
+    K *dIn = s.room<K>(n), *dOut = s.room<K>(n);
+    uint32_t *vIn = HAS_V ? s.room<uint32_t>(n) : nullptr, *vOut = HAS_V ? s.room<uint32_t>(n) : nullptr;
+    if (!dIn || !dOut || (HAS_V && (!vIn || !vOut)))
+        return DEME_ERR_HIP;
+    size_t bytes = 0;
+    if (deme_radix_sort<RocCfg, HAS_V>(nullptr, bytes, dIn, dOut, vIn, vOut, n, n, beginBit, endBit, ownFrom, nullptr) != hipSuccess)
+        return DEME_ERR_HIP;
+    void* tmp = s.room<char>(bytes);
+    if (!tmp)
+        return DEME_ERR_HIP;
+    bool ok = hipMemcpy(dIn, keys, n * sizeof(K), hipMemcpyHostToDevice) == hipSuccess;
+    if (HAS_V)
+        ok = ok && hipMemcpy(vIn, vals, n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && deme_radix_sort<RocCfg, HAS_V>(tmp, bytes, dIn, dOut, vIn, vOut, n, n, beginBit, endBit, ownFrom, nullptr) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    ok = ok && hipMemcpy(keysOut, dOut, n * sizeof(K), hipMemcpyDeviceToHost) == hipSuccess;
+    if (HAS_V)
+        ok = ok && hipMemcpy(valsOut, vOut, n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    return ok ? DEME_OK : DEME_ERR_HIP;
+}
+}  // namespace
+
+unsigned deme_sort_tile_keys(void) { return deme_sort::TILE; }
+
+int deme_sort_pairs_u32(int device, const uint32_t* keys, const uint32_t* vals, size_t n, unsigned beginBit, unsigned endBit, int forceOwn,
+                        uint32_t* keysOut, uint32_t* valsOut) {
+    const unsigned bits = endBit >= beginBit ? endBit - beginBit : 0;
+    if (bits <= 20)  // the short keys of the crossing records
+        return sort_host_arrays<DemeRadixCfg<10>, true>(device, keys, vals, n, beginBit, endBit, forceOwn ? 0 : DEME_SORT_OWN_FROM_RECORDS, keysOut,
+                                                        valsOut);
+    if (bits <= 22)  // (the incidence sort's two configurations)
+        return sort_host_arrays<DemeRadixCfg<11, 16>, true>(device, keys, vals, n, beginBit, endBit, forceOwn ? 0 : DEME_SORT_OWN_FROM_INCIDENCES,
+                                                            keysOut, valsOut);
+    return sort_host_arrays<DemeRadixCfg<8>, true>(device, keys, vals, n, beginBit, endBit, forceOwn ? 0 : DEME_SORT_OWN_FROM_INCIDENCES, keysOut,
+                                                   valsOut);
+}
+
+int deme_sort_keys_u64(int device, const uint64_t* keys, size_t n, unsigned beginBit, unsigned endBit, int forceOwn, uint64_t* keysOut) {
+    return sort_host_arrays<DemeRadixCfg<8>, false>(device, keys, nullptr, n, beginBit, endBit, forceOwn ? 0 : DEME_SORT_OWN_FROM_KEYS64, keysOut,
+                                                    nullptr);
 }
 
 #include "deme_decomp.inc"

@@ -315,6 +315,15 @@ int deme_query_owner_contacts(deme_ctx* ctx, const uint32_t* ownerIds, size_t nO
                               uint8_t* type, uint32_t* ownerA, uint32_t* ownerB, uint8_t* side, float* force, float* torqueOnly,
                               float* cpA, float* cpB, size_t cap, size_t* nOut);
 int deme_query_host_bytes(const deme_ctx* ctx, uint64_t* bytes);
+/* The detection's radix sort alone, on host arrays (tests): a stable sort of keys (and vals with them) by the bits
+ * [beginBit, endBit) of the key; the other bits take no part in the order and arrive unchanged.  forceOwn 1: the project's own
+ * sort whatever n is (DEME_ERR_INVALID from a library built with rocprim at every site); 0: what the detection's call sites
+ * take for a list of this kind and size -- rocprim below a threshold (pairs: keys of up to 20 bits count as crossing records,
+ * wider ones as incidences).  deme_sort_tile_keys: the keys one workgroup of the own sort takes. */
+int deme_sort_pairs_u32(int device, const uint32_t* keys, const uint32_t* vals, size_t n, unsigned beginBit, unsigned endBit, int forceOwn,
+                        uint32_t* keysOut, uint32_t* valsOut);
+int deme_sort_keys_u64(int device, const uint64_t* keys, size_t n, unsigned beginBit, unsigned endBit, int forceOwn, uint64_t* keysOut);
+unsigned deme_sort_tile_keys(void);
 /* per-sphere world position (LBF-shifted frame, as kT sees it) and inflated radius */
 int deme_download_sphere_geometry(deme_ctx* ctx, double* X, double* Y, double* Z, float* R, size_t cap);
 
