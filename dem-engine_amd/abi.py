@@ -212,6 +212,7 @@ def load_library():
         "deme_query_owner_contacts": [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                       C.POINTER(C.c_size_t)],
         "deme_query_host_bytes": [_P, C.POINTER(C.c_uint64)],
+        "deme_query_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
         "deme_sort_keys_u64": [C.c_int, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P],
         "deme_change_owner_sizes": [_P, _P, _P, C.c_size_t], "deme_num_components": [_P, C.POINTER(C.c_uint32)],
@@ -670,6 +671,46 @@ class Multi:
         self._ck(self.lib.deme_multi_download_contact_records(self.h, *[_ptr(a) for a in arrs], n), "deme_multi_download_contact_records")
         return arrs
 
+    def owner_contacts(self, owner_ids, records=False):
+        """deme_multi_query_owner_contacts: the rows of the merged list (contacts(), GLOBAL ids) that touch one of owner_ids,
+        selected on every slab's device, in that list's order.  The dict of Context.owner_contacts, owners as global ids."""
+        ids = np.ascontiguousarray(owner_ids, dtype=np.uint32).ravel()
+        self.lib.deme_multi_query_owner_contacts.argtypes = [_P, _P, C.c_size_t, C.c_int] + [_P] * 10 + [C.c_size_t, C.POINTER(C.c_size_t)]
+        cap = max(64, getattr(self, "_query_rows", 0))
+        unset = C.c_size_t(-1).value
+        while True:
+            out = {"idA": np.zeros(cap, np.uint32), "idB": np.zeros(cap, np.uint32), "type": np.zeros(cap, np.uint8),
+                   "ownerA": np.zeros(cap, np.uint32), "ownerB": np.zeros(cap, np.uint32), "side": np.zeros(cap, np.uint8)}
+            rec = {k: np.zeros((cap, 3), np.float32) for k in ("force", "torqueOnly", "cpA", "cpB")} if records else {}
+            ptrs = [_ptr(out[k]) for k in ("idA", "idB", "type", "ownerA", "ownerB", "side")]
+            ptrs += [_ptr(rec[k]) if records else None for k in ("force", "torqueOnly", "cpA", "cpB")]
+            n = C.c_size_t(unset)
+            rc = self.lib.deme_multi_query_owner_contacts(self.h, _ptr(ids), ids.size, int(bool(records)), *ptrs, cap, C.byref(n))
+            if rc == 0:
+                break
+            if n.value == unset or n.value <= cap:  # a refusal ("too small" leaves the count)
+                self._ck(rc, "deme_multi_query_owner_contacts")
+            cap = int(n.value)
+        m = int(n.value)
+        self._query_rows = m
+        out.update(rec)
+        return {k: v[:m].copy() for k, v in out.items()}
+
+    def query_host_bytes(self):
+        """bytes owner_contacts / owner_state calls have copied from the devices to the host since the run was created"""
+        v = C.c_uint64(0)
+        self.lib.deme_multi_query_host_bytes.argtypes = [_P, C.POINTER(C.c_uint64)]
+        self._ck(self.lib.deme_multi_query_host_bytes(self.h, C.byref(v)), "deme_multi_query_host_bytes")
+        return int(v.value)
+
+    def owner_state(self, owner_ids, columns=None):
+        """deme_multi_query_owner_state: the named columns of download_state() at the GLOBAL owner_ids, gathered on the slabs'
+        devices"""
+        ids, st, out = _owner_state_request(owner_ids, QUERY_STATE_COLUMNS if columns is None else columns)
+        self.lib.deme_multi_query_owner_state.argtypes = [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)]
+        self._ck(self.lib.deme_multi_query_owner_state(self.h, _ptr(ids), ids.size, C.byref(st)), "deme_multi_query_owner_state")
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.deme_multi_destroy(self.h)
@@ -680,6 +721,23 @@ class Multi:
             self.close()
         except Exception:
             pass
+
+
+QUERY_STATE_COLUMNS = ("voxelID", "locX", "locY", "locZ", "oriQw", "oriQx", "oriQy", "oriQz", "vX", "vY", "vZ", "omgBarX", "omgBarY",
+                       "omgBarZ", "familyID")
+
+
+def _owner_state_request(owner_ids, columns):
+    """the ids, a DemeOwnerState whose named columns hold len(ids) entries (the others null) and the dict of those columns"""
+    ids = np.ascontiguousarray(owner_ids, dtype=np.uint32).ravel()
+    st, out = DemeOwnerState(), {}
+    for name in STATE_DTYPES:
+        setattr(st, name, None)
+    for name in columns:
+        out[name] = np.zeros(max(ids.size, 1), STATE_DTYPES[name])
+        setattr(st, name, out[name].ctypes.data)
+    st._keep = out
+    return ids, st, {k: v[:ids.size] for k, v in out.items()}
 
 
 def exported_symbols():
@@ -1084,10 +1142,18 @@ class Context:
         return {k: v[:m].copy() for k, v in out.items()}
 
     def query_host_bytes(self):
-        """bytes owner_contacts calls have copied to the host since the context was created (count read-backs and hit rows)"""
+        """bytes owner_contacts / owner_state calls have copied to the host since the context was created (count read-backs, hit
+        rows and gathered owner records)"""
         v = C.c_uint64(0)
         self._ck(self.lib.deme_query_host_bytes(self.h, C.byref(v)), "deme_query_host_bytes")
         return int(v.value)
+
+    def owner_state(self, owner_ids, columns=QUERY_STATE_COLUMNS):
+        """deme_query_owner_state: the named columns of download_state() at owner_ids (any order, repeats allowed), gathered on the
+        device.  A dict column -> array of len(owner_ids)."""
+        ids, st, out = _owner_state_request(owner_ids, columns)
+        self._ck(self.lib.deme_query_owner_state(self.h, _ptr(ids), ids.size, C.byref(st)), "deme_query_owner_state")
+        return out
 
     def sphere_geometry(self):
         n = self.n_spheres

@@ -602,6 +602,7 @@ struct deme_multi {
     std::vector<MultiRow> rows;  // the merged list, built on demand and kept until the next step / upload
     uint64_t rowsAtStep = 0;
     bool rowsValid = false;
+    uint64_t qHostBytes = 0;  // bytes the by-owner queries have copied to the host (deme_multi_query_host_bytes)
     std::string err;
 };
 
@@ -1363,6 +1364,272 @@ int deme_multi_download_contact_records(deme_multi* m, float* force, float* torq
                 cpB[3 * i + k] = (r.flipped ? a : b)[r.slab][3 * (size_t)r.row + k];
         }
     }
+    return DEME_OK;
+}
+
+// ---- the contacts and the state of a few owners of a decomposed run, selected on every slab's device (deme_query.h) -----------------
+// Every slab selects from its own list with the rule of multi_contact_rows (k_query_select_slab: global ids from the books the
+// migration keeps on the device) and hands over a count and its hit rows; the host sorts the hits of all slabs by the merged key
+// (a pair is reported once, so keys are unique).  The cached merged rows are neither used nor invalidated.
+namespace {
+// the distinct ids of a question, marked in the slab context's byte array over GLOBAL owner ids
+int slab_query_mark(deme_ctx* c, const std::vector<uint32_t>& ids, uint32_t nOwnersGlobal) {
+    if (ensure(c, c->qMark, std::max<size_t>(nOwnersGlobal, 1)) || ensure(c, c->qCtr, 256) || ensure(c, c->stage, std::max<size_t>(ids.size(), 1) * 4))
+        return c->lastStatus;
+    HIPCK(hipMemsetAsync(c->qMark.p, 0, std::max<size_t>(nOwnersGlobal, 1), c->stream));
+    if (!ids.empty()) {
+        HIPCK(hipMemcpyAsync(c->stage.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_query_mark, dim3(grid_for(ids.size())), dim3(256), 0, c->stream, (uint32_t)ids.size(), c->stage.as<uint32_t>(),
+                           c->qMark.as<uint8_t>());
+    }
+    return DEME_OK;
+}
+// one slab's selection: the hit count in nHit, the hits (and records) left in the context's scratch; passes: count read-backs made
+int slab_query_select(deme_ctx* c, const HaloSlab& s, uint32_t nOwnersGlobal, int withRecords, uint32_t& nHit, uint32_t& passes) {
+    nHit = 0, passes = 0;
+    const size_t n = c->haveList ? (size_t)c->nContacts : 0;
+    if (!n)
+        return DEME_OK;
+    QueryTables t{};
+    t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
+    t.s2e = c->dp.s2e, t.o2e = c->dp.o2e;
+    t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
+    SlabBooksDev bk{};
+    bk.sphereGid = (const uint32_t*)s.geo.sphereGid, bk.ownerGid = (const uint32_t*)s.geo.ownerGid;
+    bk.nOwn = s.geo.nOwn, bk.nOwnersGlobal = nOwnersGlobal;
+    size_t want = 256;  // rows of scratch a first query starts with
+    for (int pass = 0;; pass++) {
+        if (ensure(c, c->qHits, want * sizeof(QueryHit)) || (withRecords && ensure(c, c->qRecs, want * 48)))
+            return c->lastStatus;
+        size_t rows = c->qHits.bytes / sizeof(QueryHit);  // the kernel's bound is what the allocations hold
+        if (withRecords)
+            rows = std::min(rows, c->qRecs.bytes / 48);
+        rows = std::min<size_t>(rows, 0xFFFFFFFFu);
+        HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
+        hipLaunchKernelGGL(k_query_select_slab, dim3(grid_for(n)), dim3(256), 0, c->stream, (uint32_t)n,
+                           c->keysSorted[c->keysCur].as<uint64_t>(), t, bk, c->qMark.as<uint8_t>(),
+                           withRecords ? c->rec[0].as<float>() : nullptr, withRecords ? c->rec[1].as<float>() : nullptr,
+                           withRecords ? c->rec[2].as<float>() : nullptr, withRecords ? c->rec[3].as<float>() : nullptr,
+                           c->qHits.as<QueryHit>(), withRecords ? c->qRecs.as<float>() : nullptr, (uint32_t)rows, c->qCtr.as<uint32_t>());
+        HIPCK(hipMemcpyAsync(&nHit, c->qCtr.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipStreamSynchronize(c->stream));
+        passes++;
+        if (nHit <= rows)
+            return DEME_OK;
+        if (pass)  // (the list cannot change between two selections)
+            return fail(c, DEME_ERR_OVERFLOW, "deme_multi_query_owner_contacts: %u hits after the scratch was sized for them", nHit);
+        want = nHit;
+    }
+}
+int slab_query_fetch(deme_ctx* c, uint32_t nHit, int withRecords, QueryHit* h, float* r) {
+    HIPCK(hipMemcpyAsync(h, c->qHits.p, (size_t)nHit * sizeof(QueryHit), hipMemcpyDeviceToHost, c->stream));
+    if (withRecords)
+        HIPCK(hipMemcpyAsync(r, c->qRecs.p, (size_t)nHit * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+// one slab's owners of a question: their records gathered into the context's scratch (at most ids.size() of them), the count in nHit
+int slab_query_state(deme_ctx* c, const HaloSlab& s, uint32_t nOwnersGlobal, bool takeReplicated, size_t nIds, uint32_t& nHit) {
+    nHit = 0;
+    if (!c->nOwners)
+        return DEME_OK;
+    if (ensure(c, c->qState, nIds * sizeof(OwnerRec)))
+        return c->lastStatus;
+    SlabBooksDev bk{};
+    bk.sphereGid = (const uint32_t*)s.geo.sphereGid, bk.ownerGid = (const uint32_t*)s.geo.ownerGid;
+    bk.nOwn = s.geo.nOwn, bk.nOwnersGlobal = nOwnersGlobal;
+    HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
+    hipLaunchKernelGGL(k_query_owner_state, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->nOwners, c->owners.as<OwnerRec>(),
+                       (const uint32_t*)nullptr, c->dp.o2e, bk, c->nOwnerClumps, takeReplicated ? 1u : 0u, c->qMark.as<uint8_t>(),
+                       c->qState.as<OwnerRec>(), (uint32_t)std::min<size_t>(c->qState.bytes / sizeof(OwnerRec), 0xFFFFFFFFu),
+                       c->qCtr.as<uint32_t>());
+    HIPCK(hipMemcpyAsync(&nHit, c->qCtr.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+int slab_query_fetch_state(deme_ctx* c, uint32_t nHit, OwnerRec* h) {
+    HIPCK(hipMemcpyAsync(h, c->qState.p, (size_t)nHit * sizeof(OwnerRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+}  // namespace
+
+int deme_multi_query_owner_contacts(deme_multi* m, const uint32_t* ownerIds, size_t nOwners, int withRecords, uint32_t* idA, uint32_t* idB,
+                                    uint8_t* type, uint32_t* ownerA, uint32_t* ownerB, uint8_t* side, float* force, float* torqueOnly,
+                                    float* cpA, float* cpB, size_t cap, size_t* nOut) {
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    if (!nOut || (nOwners && !ownerIds))
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_contacts: null %s", nOut ? "owner id array" : "nOut");
+    const uint32_t nOG = m->plan->nOwnersGlobal;
+    for (size_t i = 0; i < nOwners; i++)
+        if (ownerIds[i] >= nOG)
+            return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_contacts: owner id %u is out of range (%u owners)", ownerIds[i], nOG);
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    if (withRecords)  // what deme_multi_download_contact_records would say, slab by slab
+        for (auto* g : m->groups)
+            for (auto& s : g->slabs) {
+                deme_ctx* c = s.ctx;
+                if (!c->nContacts)
+                    continue;
+                int rc = DEME_OK;  // (fail() writes c->err: called on its own, before the message is read)
+                if (!c->record)
+                    rc = fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
+                else if (c->seeded)
+                    rc = fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+                if (rc)
+                    return mfail(m, rc, "%s", c->err.c_str());
+            }
+    std::vector<uint32_t> ids(ownerIds, ownerIds + nOwners);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    struct Part {
+        deme_halo_group* g;
+        deme_ctx* c;
+        uint32_t nHit;
+    };
+    std::vector<Part> parts;
+    size_t total = 0;
+    if (!ids.empty())
+        for (auto* g : m->groups) {
+            if (hipSetDevice(g->device) != hipSuccess)
+                return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+            for (auto& s : g->slabs) {
+                deme_ctx* c = s.ctx;
+                if (!s.geo.set)
+                    return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_contacts: a slab has no books (deme_halo_group_set_slab / _build)");
+                uint32_t nHit = 0, passes = 0;
+                if (c->haveList && c->nContacts) {
+                    if (int rc = slab_query_mark(c, ids, nOG))
+                        return mfail(m, rc, "%s", c->err.c_str());
+                    if (int rc = slab_query_select(c, s, nOG, withRecords, nHit, passes))
+                        return mfail(m, rc, "%s", c->err.c_str());
+                }
+                m->qHostBytes += 4ull * passes;  // (a slab with an empty list is not asked)
+                parts.push_back({g, c, nHit});
+                total += nHit;
+            }
+        }
+    *nOut = total;
+    if (cap < total)
+        return mfail(m, DEME_ERR_INVALID, "buffer too small: need %zu", total);
+    if (!total)
+        return DEME_OK;
+    std::vector<QueryHit> h(total);
+    std::vector<float> r(withRecords ? total * 12 : 0);
+    std::vector<const deme_ctx*> ctxOf(total);
+    size_t at = 0;
+    for (const Part& p : parts) {
+        if (!p.nHit)
+            continue;
+        if (hipSetDevice(p.g->device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", p.g->device);
+        if (int rc = slab_query_fetch(p.c, p.nHit, withRecords, h.data() + at, withRecords ? r.data() + 12 * at : nullptr))
+            return mfail(m, rc, "%s", p.c->err.c_str());
+        for (uint32_t i = 0; i < p.nHit; i++)
+            ctxOf[at + i] = p.c;
+        at += p.nHit;
+    }
+    m->qHostBytes += (uint64_t)total * (sizeof(QueryHit) + (withRecords ? 48 : 0));
+    std::vector<uint32_t> perm(total);
+    for (size_t i = 0; i < total; i++)
+        perm[i] = (uint32_t)i;
+    std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h[a].key < h[b].key; });
+    float* dst[4] = {force, torqueOnly, cpA, cpB};
+    for (size_t i = 0; i < total; i++) {
+        const QueryHit& q = h[perm[i]];
+        const uint32_t cls = key_class(q.key), gB = merged_key_b(q.key);
+        if (idA)
+            idA[i] = merged_key_a(q.key);
+        if (idB)
+            idB[i] = gB;
+        if (type)
+            type[i] = cls == DEME_KEY_CLASS_SS   ? DEME_SPHERE_SPHERE_CONTACT
+                      : cls == DEME_KEY_CLASS_SM ? DEME_SPHERE_MESH_CONTACT
+                      : ctxOf[perm[i]]->hObjType[gB] == DEME_ANAL_OBJ_TYPE_PLANE ? DEME_SPHERE_PLANE_CONTACT
+                                                                                 : DEME_SPHERE_CYL_CONTACT;
+        if (ownerA)
+            ownerA[i] = q.ownerA;
+        if (ownerB)
+            ownerB[i] = q.ownerB;
+        if (side)
+            side[i] = (uint8_t)(q.side & 1u);
+        if (withRecords)
+            for (int k = 0; k < 4; k++)
+                if (dst[k])
+                    memcpy(dst[k] + 3 * i, r.data() + 12 * (size_t)perm[i] + 3 * k, 12);
+    }
+    return DEME_OK;
+}
+
+int deme_multi_query_host_bytes(const deme_multi* m, uint64_t* bytes) {
+    if (!m || !bytes)
+        return DEME_ERR_INVALID;
+    *bytes = m->qHostBytes;
+    return DEME_OK;
+}
+
+int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_t n, DemeOwnerState* out) {
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    if (!out || (n && !globalIds))
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: null %s", out ? "owner id array" : "state");
+    if (owner_state_wants_acc(out))
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: a / alpha need the reduction a full download launches (deme_multi_download_state)");
+    const uint32_t nOG = m->plan->nOwnersGlobal;
+    for (size_t i = 0; i < n; i++)
+        if (globalIds[i] >= nOG)
+            return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: owner id %u is out of range (%u owners)", globalIds[i], nOG);
+    if (!n)
+        return DEME_OK;
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    // the rows of `out` every distinct id fills: (id, row) sorted by id
+    std::vector<std::pair<uint32_t, uint32_t>> rowsOf(n);
+    for (size_t i = 0; i < n; i++)
+        rowsOf[i] = {globalIds[i], (uint32_t)i};
+    std::sort(rowsOf.begin(), rowsOf.end());
+    std::vector<uint32_t> ids;
+    for (auto& pr : rowsOf)
+        if (ids.empty() || ids.back() != pr.first)
+            ids.push_back(pr.first);
+    size_t found = 0;
+    std::vector<OwnerRec> h;
+    for (auto* g : m->groups) {
+        if (hipSetDevice(g->device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+        for (size_t k = 0; k < g->slabs.size(); k++) {
+            HaloSlab& s = g->slabs[k];
+            deme_ctx* c = s.ctx;
+            if (!s.geo.set)
+                return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: a slab has no books (deme_halo_group_set_slab / _build)");
+            uint32_t nHit = 0;
+            if (int rc = slab_query_mark(c, ids, nOG))
+                return mfail(m, rc, "%s", c->err.c_str());
+            if (int rc = slab_query_state(c, s, nOG, g->firstSlab + k == 0, ids.size(), nHit))
+                return mfail(m, rc, "%s", c->err.c_str());
+            m->qHostBytes += 4;
+            if (nHit > ids.size())
+                return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: a slab holds %u owners for %zu ids", nHit, ids.size());
+            if (!nHit)
+                continue;
+            h.resize(nHit);
+            if (int rc = slab_query_fetch_state(c, nHit, h.data()))
+                return mfail(m, rc, "%s", c->err.c_str());
+            m->qHostBytes += (uint64_t)nHit * sizeof(OwnerRec);
+            for (uint32_t i = 0; i < nHit; i++) {
+                uint32_t gid;
+                memcpy(&gid, &h[i].margin, 4);
+                auto it = std::lower_bound(rowsOf.begin(), rowsOf.end(), std::make_pair(gid, 0u));
+                for (; it != rowsOf.end() && it->first == gid; ++it)
+                    owner_state_row(out, it->second, h[i]);
+                found++;
+            }
+        }
+    }
+    if (found != ids.size())
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: %zu of %zu owners were found on the slabs", found, ids.size());
     return DEME_OK;
 }
 

@@ -128,7 +128,7 @@ struct deme_ctx {
     DevBuf rsMark, rsKeys[2], rsRuns, rsUKeys, rsIdx, rsOldR, rsUses, rsRemap;  // resize scratch (deme_resize.h), allocated by the first resize
     // owner-filtered contact queries (deme_query.h): marks per owner, the hit rows and their records, the hit counter; allocated by
     // the first query and kept, so that a script asking every frame selects once per call
-    DevBuf qMark, qHits, qRecs, qCtr;
+    DevBuf qMark, qHits, qRecs, qCtr, qState;  // (qState: the owner records deme_query_owner_state gathers)
     uint64_t qHostBytes = 0;  // bytes the queries have copied to the host so far (deme_query_host_bytes)
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
@@ -1631,7 +1631,7 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->wc[0], &c->wc[1], &c->ctr,
                      &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
-                     &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr};
+                     &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr, &c->qState};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -4595,6 +4595,63 @@ int deme_query_host_bytes(const deme_ctx* c, uint64_t* bytes) {
     if (!c || !bytes)
         return DEME_ERR_INVALID;
     *bytes = c->qHostBytes;
+    return DEME_OK;
+}
+
+// ---- pose, velocity and family of a few owners (deme_query.h: k_query_owner_state) ------------------------------------------------
+namespace {
+// the columns of DemeOwnerState a gathered record fills: row `at` of every non-null column from record r
+inline void owner_state_row(const DemeOwnerState* out, size_t at, const OwnerRec& r) {
+    if (out->voxelID) out->voxelID[at] = r.voxelID;
+    if (out->locX) out->locX[at] = r.locX;
+    if (out->locY) out->locY[at] = r.locY;
+    if (out->locZ) out->locZ[at] = r.locZ;
+    if (out->oriQw) out->oriQw[at] = r.qw;
+    if (out->oriQx) out->oriQx[at] = r.qx;
+    if (out->oriQy) out->oriQy[at] = r.qy;
+    if (out->oriQz) out->oriQz[at] = r.qz;
+    if (out->vX) out->vX[at] = r.vx;
+    if (out->vY) out->vY[at] = r.vy;
+    if (out->vZ) out->vZ[at] = r.vz;
+    if (out->omgBarX) out->omgBarX[at] = r.wx;
+    if (out->omgBarY) out->omgBarY[at] = r.wy;
+    if (out->omgBarZ) out->omgBarZ[at] = r.wz;
+    if (out->familyID) out->familyID[at] = (uint8_t)r.family;
+}
+inline bool owner_state_wants_acc(const DemeOwnerState* st) {
+    return st->aX || st->aY || st->aZ || st->alphaX || st->alphaY || st->alphaZ;
+}
+}  // namespace
+
+int deme_query_owner_state(deme_ctx* c, const uint32_t* ownerIds, size_t n, DemeOwnerState* out) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (!out || (n && !ownerIds))
+        return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: null %s", out ? "owner id array" : "state");
+    if (owner_state_wants_acc(out))
+        return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: a / alpha need the reduction a full download launches (deme_download_owner_state)");
+    if (n > 0xFFFFFFFFull)
+        return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: %zu ids", n);
+    for (size_t i = 0; i < n; i++)
+        if (ownerIds[i] >= c->nOwners)
+            return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: owner id %u is out of range (%u owners)", ownerIds[i], c->nOwners);
+    if (!n)
+        return DEME_OK;
+    std::vector<uint32_t> slots(n);
+    for (size_t i = 0; i < n; i++)
+        slots[i] = c->permuted ? c->hE2O[ownerIds[i]] : ownerIds[i];
+    if (ensure(c, c->stage, n * 4) || ensure(c, c->qState, n * sizeof(OwnerRec)))
+        return c->lastStatus;
+    HIPCK(hipMemcpyAsync(c->stage.p, slots.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_query_owner_state, dim3(grid_for(n)), dim3(256), 0, c->stream, (uint32_t)n, c->owners.as<OwnerRec>(),
+                       c->stage.as<uint32_t>(), (const uint32_t*)nullptr, SlabBooksDev{}, 0u, 0u, (const uint8_t*)nullptr,
+                       c->qState.as<OwnerRec>(), (uint32_t)n, (uint32_t*)nullptr);
+    std::vector<OwnerRec> h(n);
+    HIPCK(hipMemcpyAsync(h.data(), c->qState.p, n * sizeof(OwnerRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->qHostBytes += (uint64_t)n * sizeof(OwnerRec);
+    for (size_t i = 0; i < n; i++)
+        owner_state_row(out, i, h[i]);
     return DEME_OK;
 }
 

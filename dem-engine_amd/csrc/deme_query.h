@@ -7,6 +7,9 @@
 //   k_query_select  one thread per row of the current list: both owners looked up in the tables the force pass uses, translated to
 //                   the caller's ids, tested against the marks; the hit rows compacted per wavefront into a scratch buffer, with
 //                   the row's four 12-byte records when they are asked for
+//   k_query_select_slab  the same for one slab of a decomposed run: global ids from the device books, the merged list's
+//                   report-once and flip rules (deme_multi_query_owner_contacts)
+//   k_query_owner_state  the 64-byte records of a few owners: a gather by slot, or one slab's share of a question in global ids
 // A thread writes only below the scratch's capacity while the counter counts every hit: the host reads the count, grows the
 // scratch and selects again when it was too small (deme_hip.hip).  The order of the hits is the atomics'; the host sorts them.
 #pragma once
@@ -95,6 +98,144 @@ __global__ __launch_bounds__(256) void k_query_select(uint32_t n, const uint64_t
         o[6] = rec2[r], o[7] = rec2[r + 1], o[8] = rec2[r + 2];
         o[9] = rec3[r], o[10] = rec3[r + 1], o[11] = rec3[r + 2];
     }
+}
+
+// ---- one slab of a decomposed run (deme_multi_query_owner_contacts) -------------------------------------------------------------
+// The slab lists its contacts in its own numbering; the question and the answer are in GLOBAL ids.  The books the migration keeps
+// on the device translate (SlabGeom::sphereGid / ownerGid, indexed by the slab scene's ids), so no host copy of them is needed.
+struct SlabBooksDev {
+    const uint32_t* sphereGid;  // the slab scene's sphere id -> global sphere id
+    const uint32_t* ownerGid;   // the slab scene's owner id -> global owner id
+    uint32_t nOwn;              // the slab's own clumps are its first nOwn owners
+    uint32_t nOwnersGlobal;     // entries of the mark array
+};
+
+#define DEME_QUERY_FLIPPED 2u  // QueryHit::side bit 1 of a slab's hit: the slab holds the pair the other way round
+
+__host__ __device__ inline uint64_t merged_key(uint64_t cls, uint32_t gA, uint32_t gB) {  // the key of multi_contact_rows
+    return ((uint64_t)gA << 34) | (cls << 31) | (uint64_t)gB;
+}
+__host__ __device__ inline uint32_t merged_key_a(uint64_t k) { return (uint32_t)(k >> 34); }  // (the class sits where key_class reads it)
+__host__ __device__ inline uint32_t merged_key_b(uint64_t k) { return (uint32_t)(k & 0x7FFFFFFFull); }
+
+// The compaction of k_query_select for the kernels below: one reservation of the counter per wavefront; returns the slot of this
+// lane's hit, 0xFFFFFFFF for a lane without one.  Every lane of the wavefront calls it.
+__device__ inline uint32_t query_append_slot(bool hit, uint32_t* nHits) {
+    const unsigned long long m = __ballot(hit);
+    if (!m)
+        return 0xFFFFFFFFu;
+    const uint32_t lane = __lane_id();
+    const uint32_t leader = (uint32_t)__ffsll((long long)m) - 1u;
+    uint32_t base = 0;
+    if (lane == leader)
+        base = atomicAdd(nHits, (uint32_t)__popcll(m));
+    base = __shfl(base, (int)leader);
+    return hit ? base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)) : 0xFFFFFFFFu;
+}
+
+// The rule of multi_contact_rows, row by row: a sphere-sphere pair is (smaller, larger) global sphere id; the row is reported only
+// by the slab that owns the clump of the (post-swap) sphere A; sphere-mesh and sphere-analytical rows go with sphere A's clump.  A
+// reported row is a hit when global owner A or B is marked.  Hits carry the merged key, the global owners, side (bit 0, in the
+// merged orientation) and the flipped bit (bit 1); the records of a flipped row as deme_multi_download_contact_records gives them:
+// force and torque-only force times -1.0f, cpA and cpB swapped.
+__global__ __launch_bounds__(256) void k_query_select_slab(uint32_t n, const uint64_t* __restrict__ keys, QueryTables t, SlabBooksDev bk,
+                                                           const uint8_t* __restrict__ mark, const float* __restrict__ rec0,
+                                                           const float* __restrict__ rec1, const float* __restrict__ rec2,
+                                                           const float* __restrict__ rec3, QueryHit* __restrict__ hits,
+                                                           float* __restrict__ recOut, uint32_t cap, uint32_t* nHits) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool hit = false, flipped = false;
+    QueryHit h{};
+    if (i < n) {
+        const uint64_t k = keys[i];
+        const uint32_t cls = key_class(k), a = key_a(k), b = key_b(k);
+        uint32_t oA = 0xFFFFFFFFu, oB = 0xFFFFFFFFu;
+        if (a < t.nSpheres)
+            oA = load_sphere(t.spheres, a).owner;
+        if (cls == DEME_KEY_CLASS_SS) {
+            if (b < t.nSpheres)
+                oB = load_sphere(t.spheres, b).owner;
+        } else if (cls == DEME_KEY_CLASS_SM) {
+            if (b < t.nTri)
+                oB = t.tris[b].owner;
+        } else if (b < t.nAnal) {
+            oB = t.anal[b].owner;
+        }
+        if (oA < t.nOwners && oB < t.nOwners) {
+            if (t.o2e)  // (a context with ghosts keeps the order it is uploaded in: null today)
+                oA = t.o2e[oA], oB = t.o2e[oB];
+            uint32_t sA = t.s2e ? t.s2e[a] : a, sB = (t.s2e && cls == DEME_KEY_CLASS_SS) ? t.s2e[b] : b;
+            if (oA < t.nOwners && oB < t.nOwners && sA < t.nSpheres && (cls != DEME_KEY_CLASS_SS || sB < t.nSpheres)) {
+                uint32_t gA = bk.sphereGid[sA], gB = cls == DEME_KEY_CLASS_SS ? bk.sphereGid[sB] : sB;
+                if (cls == DEME_KEY_CLASS_SS && gA > gB) {
+                    uint32_t x = gA;
+                    gA = gB, gB = x;
+                    x = oA, oA = oB, oB = x;
+                    flipped = true;
+                }
+                if (oA < bk.nOwn) {  // the neighbour that owns that clump reports the pair otherwise
+                    const uint32_t goA = bk.ownerGid[oA], goB = bk.ownerGid[oB];
+                    const bool mA = goA < bk.nOwnersGlobal && mark[goA] != 0, mB = goB < bk.nOwnersGlobal && mark[goB] != 0;
+                    hit = mA || mB;
+                    h.key = merged_key(cls, gA, gB);
+                    h.row = i, h.ownerA = goA, h.ownerB = goB, h.side = (mA ? 0u : 1u) | (flipped ? DEME_QUERY_FLIPPED : 0u);
+                }
+            }
+        }
+    }
+    const uint32_t at = query_append_slot(hit, nHits);
+    if (at >= cap)  // (no hit, or the counter has counted the row: the host selects again with room for all of them)
+        return;
+    hits[at] = h;
+    if (recOut) {
+        float* o = recOut + (size_t)at * 12;
+        const size_t r = (size_t)i * 3;
+        const float sgn = flipped ? -1.0f : 1.0f;  // (the recorded force acts on A; a zero changes sign too, as on the host path)
+        const float* pa = flipped ? rec3 : rec2;
+        const float* pb = flipped ? rec2 : rec3;
+        o[0] = sgn * rec0[r], o[1] = sgn * rec0[r + 1], o[2] = sgn * rec0[r + 2];
+        o[3] = sgn * rec1[r], o[4] = sgn * rec1[r + 1], o[5] = sgn * rec1[r + 2];
+        o[6] = pa[r], o[7] = pa[r + 1], o[8] = pa[r + 2];
+        o[9] = pb[r], o[10] = pb[r + 1], o[11] = pb[r + 2];
+    }
+}
+
+// ---- pose, velocity and family of a few owners (deme_query_owner_state, deme_multi_query_owner_state) ---------------------------
+// A hit is the owner's 64-byte record as it stands, with the word that holds the margin replaced by a tag: the index of the
+// question (single context) or the owner's global id (a slab).
+__device__ inline void query_state_write(OwnerRec* __restrict__ out, uint32_t at, const OwnerRec* __restrict__ owners, uint32_t slot,
+                                         uint32_t tag) {
+    OwnerRec r = owners[slot];
+    r.margin = __uint_as_float(tag);
+    out[at] = r;
+}
+
+// bk.ownerGid == null: a gather by slot -- thread i copies owner slots[i] (the host translated the caller's ids) to out[i]; nHits unused.
+// Otherwise one thread per owner slot of the slab: the owner's global id looked up, tested against the marks, and taken under the
+// rule of group_state_io -- own clumps from the slab that owns them, replicated owners (slots from nOwnerClumps on) from the first
+// slab of the chain (takeReplicated) --, hits compacted per wavefront as in k_query_select.
+__global__ __launch_bounds__(256) void k_query_owner_state(uint32_t n, const OwnerRec* __restrict__ owners, const uint32_t* __restrict__ slots,
+                                                           const uint32_t* __restrict__ o2e, SlabBooksDev bk, uint32_t nOwnerClumps, uint32_t takeReplicated,
+                                                           const uint8_t* __restrict__ mark, OwnerRec* __restrict__ out, uint32_t cap,
+                                                           uint32_t* nHits) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (!bk.ownerGid) {
+        if (i < n && i < cap)
+            query_state_write(out, i, owners, slots[i], i);
+        return;
+    }
+    bool hit = false;
+    uint32_t gid = 0;
+    if (i < n) {
+        const uint32_t s = o2e ? o2e[i] : i;  // the slab scene's id of this slot
+        if (s < n && (s < bk.nOwn || (s >= nOwnerClumps && takeReplicated))) {
+            gid = bk.ownerGid[s];
+            hit = gid < bk.nOwnersGlobal && mark[gid] != 0;
+        }
+    }
+    const uint32_t at = query_append_slot(hit, nHits);
+    if (at < cap)
+        query_state_write(out, at, owners, i, gid);
 }
 
 }  // namespace deme_dev

@@ -1350,12 +1350,13 @@ class DEMSolver {
     /// `owners` on either side and a non-negligible force; the force as the tracked owner feels it (A's side first), the contact
     /// point in global coordinates, optionally the contact torque in the owner's local or the global frame.  Needs the
     /// per-contact records (on unless SetNoForceRecord).  Returns the number of pairs.
-    /// On one context the rows come from a device-side selection (deme_query_owner_contacts) and only they cross the bus; a
-    /// decomposed run keeps the whole-list path below (owner_contact_forces_whole_list), which is also what DEME_QUERY_HOST=1
-    /// selects for the tests that hold the two against each other.
+    /// The rows come from a device-side selection (deme_query_owner_contacts; on a decomposed run deme_multi_query_owner_contacts,
+    /// every slab selecting from its own list) and the pose of the owners on them from a gather by id (deme_query_owner_state /
+    /// deme_multi_query_owner_state): only the hit rows and those owners' records cross the bus.  DEME_QUERY_HOST=1 selects the
+    /// whole-list path below (owner_contact_forces_whole_list) for the tests that hold the two against each other.
     size_t GetOwnerContactForces(const std::vector<bodyID_t>& owners, std::vector<float3>& points, std::vector<float3>& forces,
                                  std::vector<float3>* torques = nullptr, bool torque_in_local = false) {
-        if (m_multi || query_on_host())
+        if (query_on_host())
             return owner_contact_forces_whole_list(owners, points, forces, torques, torque_in_local);
         std::vector<bodyID_t> known;  // (an id past the last owner concerns no contact: it is left out, as the whole-list path ignores it)
         for (bodyID_t o : owners)
@@ -1367,15 +1368,21 @@ class DEMSolver {
             torques->clear();
         if (!oc.n)
             return 0;
-        // orientation and position: the columns of one state download, decoded for the owners of the hit rows only
-        const size_t n = m_n_owners;
+        // orientation and position of the owners the hit rows are reported for, gathered by id: entry at[o] of the columns below
+        std::vector<bodyID_t> who(oc.n);
+        for (size_t i = 0; i < oc.n; i++)
+            who[i] = oc.side[i] == 0 ? oc.ownerA[i] : oc.ownerB[i];
+        std::sort(who.begin(), who.end());
+        who.erase(std::unique(who.begin(), who.end()), who.end());
+        const size_t n = who.size();
         std::vector<uint64_t> vid(n);
         std::vector<uint16_t> lx(n), ly(n), lz(n);
         std::vector<float> qw(n), qx(n), qy(n), qz(n);
         DemeOwnerState st{};
         st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
         st.oriQw = qw.data(), st.oriQx = qx.data(), st.oriQy = qy.data(), st.oriQz = qz.data();
-        dl_state(&st);
+        query_owner_state(who, &st);
+        auto at = [&](bodyID_t o) { return (size_t)(std::lower_bound(who.begin(), who.end(), o) - who.begin()); };
         const float vs = (float)m_p.voxelSize, l = (float)m_p.l;
         auto com_of = [&](size_t i) {  // (as snapshot(): voxelIDToPosition<float, ...> then + LBF, all fp32)
             const uint64_t vx = vid[i] & ((1ull << m_p.nvXp2) - 1), vy = (vid[i] >> m_p.nvXp2) & ((1ull << m_p.nvYp2) - 1),
@@ -1391,7 +1398,7 @@ class DEMSolver {
                 continue;
             float3 pnt = isA ? make_float3(oc.cpA[3 * i], oc.cpA[3 * i + 1], oc.cpA[3 * i + 2])
                              : make_float3(oc.cpB[3 * i], oc.cpB[3 * i + 1], oc.cpB[3 * i + 2]);
-            const bodyID_t o = isA ? oc.ownerA[i] : oc.ownerB[i];
+            const size_t o = at(isA ? oc.ownerA[i] : oc.ownerB[i]);
             if (!isA) {
                 force = force * -1.f;
                 torque = torque * -1.f;
@@ -1434,7 +1441,7 @@ class DEMSolver {
                 out.push_back(oA);
             }
         };
-        if (m_multi) {  // the merged list of the slabs, filtered here (global ids)
+        if (query_on_host()) {  // DEME_QUERY_HOST=1: the whole list (a decomposed run's merged list, global ids), filtered here
             const size_t nc = n_contacts();
             std::vector<uint32_t> a(nc), b(nc);
             std::vector<uint8_t> ty(nc);
@@ -1448,6 +1455,16 @@ class DEMSolver {
         for (size_t i = 0; i < oc.n; i++)
             take(oc.type[i], oc.ownerA[i], oc.ownerB[i]);
         return out;
+    }
+    /// (no reference equivalent) bytes the by-owner queries above have copied from the device(s) to the host so far: the counter
+    /// of the context (deme_query_host_bytes) or of the decomposed run (deme_multi_query_host_bytes)
+    uint64_t GetOwnerQueryHostBytes() {
+        uint64_t v = 0;
+        if (m_multi)
+            mcheck(deme_multi_query_host_bytes(m_multi, &v));
+        else
+            check(deme_query_host_bytes(m_ctx, &v));
+        return v;
     }
     /// ShowTimingStats / ShowThreadCollaborationStats (API.h:1290-1300): the kernels' mean times from HIP events
     void ShowTimingStats() {
@@ -2023,8 +2040,7 @@ class DEMSolver {
         else
             check(deme_download_contact_records(m_ctx, f, t, a, b, nc));
     }
-    /// GetOwnerContactForces over downloads of the whole list: a decomposed run (the merged list's flip rules live in
-    /// deme_multi_download_contact_records), and DEME_QUERY_HOST=1
+    /// GetOwnerContactForces over downloads of the whole list (the merged list of a decomposed run): DEME_QUERY_HOST=1
     size_t owner_contact_forces_whole_list(const std::vector<bodyID_t>& owners, std::vector<float3>& points, std::vector<float3>& forces,
                                            std::vector<float3>* torques, bool torque_in_local) {
         const Snapshot sn = snapshot(true);
@@ -2074,8 +2090,9 @@ class DEMSolver {
         }
         return points.size();
     }
-    /// the rows of the context's list that touch one of `owners`, selected on the device (deme_query_owner_contacts), in list
-    /// order; the per-contact records with them when asked for.  One context only.
+    /// the rows of the run's list that touch one of `owners`, selected on the device (deme_query_owner_contacts; the merged list
+    /// of a decomposed run in global ids: deme_multi_query_owner_contacts), in list order; the per-contact records with them when
+    /// asked for
     struct OwnerContacts {
         size_t n = 0;
         std::vector<uint32_t> idA, idB, ownerA, ownerB;
@@ -2090,12 +2107,20 @@ class DEMSolver {
                 oc.F.resize(3 * cap), oc.T.resize(3 * cap), oc.cpA.resize(3 * cap), oc.cpB.resize(3 * cap);
             const size_t unset = ~(size_t)0;
             size_t n = unset;
-            const int rc = deme_query_owner_contacts(m_ctx, owners.data(), owners.size(), records ? 1 : 0, oc.idA.data(), oc.idB.data(),
-                                                     oc.type.data(), oc.ownerA.data(), oc.ownerB.data(), oc.side.data(),
-                                                     records ? oc.F.data() : nullptr, records ? oc.T.data() : nullptr,
-                                                     records ? oc.cpA.data() : nullptr, records ? oc.cpB.data() : nullptr, cap, &n);
-            if (rc && (n == unset || n <= cap))  // a refusal; "too small" leaves the count
-                check(rc);
+            float *f = records ? oc.F.data() : nullptr, *t = records ? oc.T.data() : nullptr, *a = records ? oc.cpA.data() : nullptr,
+                  *b = records ? oc.cpB.data() : nullptr;
+            const int rc = m_multi ? deme_multi_query_owner_contacts(m_multi, owners.data(), owners.size(), records ? 1 : 0, oc.idA.data(),
+                                                                     oc.idB.data(), oc.type.data(), oc.ownerA.data(), oc.ownerB.data(),
+                                                                     oc.side.data(), f, t, a, b, cap, &n)
+                                   : deme_query_owner_contacts(m_ctx, owners.data(), owners.size(), records ? 1 : 0, oc.idA.data(),
+                                                               oc.idB.data(), oc.type.data(), oc.ownerA.data(), oc.ownerB.data(),
+                                                               oc.side.data(), f, t, a, b, cap, &n);
+            if (rc && (n == unset || n <= cap)) {  // a refusal; "too small" leaves the count
+                if (m_multi)
+                    mcheck(rc);
+                else
+                    check(rc);
+            }
             if (!rc) {
                 oc.n = n;
                 break;
@@ -2108,7 +2133,15 @@ class DEMSolver {
             oc.F.resize(3 * oc.n), oc.T.resize(3 * oc.n), oc.cpA.resize(3 * oc.n), oc.cpB.resize(3 * oc.n);
         return oc;
     }
-    /// DEME_QUERY_HOST=1 (tests): GetOwnerContactForces takes the whole-list path on one context too
+    /// the non-null columns of `st` (one entry per id) for `ids`, gathered on the device
+    void query_owner_state(const std::vector<bodyID_t>& ids, DemeOwnerState* st) {
+        if (m_multi)
+            mcheck(deme_multi_query_owner_state(m_multi, ids.data(), ids.size(), st));
+        else
+            check(deme_query_owner_state(m_ctx, ids.data(), ids.size(), st));
+    }
+    /// DEME_QUERY_HOST=1 (tests): GetOwnerContactForces and GetOwnerContactClumps take the whole-list paths, on one context and on
+    /// a decomposed run
     static bool query_on_host() {
         static const bool on = [] {
             const char* e = std::getenv("DEME_QUERY_HOST");

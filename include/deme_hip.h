@@ -315,6 +315,12 @@ int deme_query_owner_contacts(deme_ctx* ctx, const uint32_t* ownerIds, size_t nO
                               uint8_t* type, uint32_t* ownerA, uint32_t* ownerB, uint8_t* side, float* force, float* torqueOnly,
                               float* cpA, float* cpB, size_t cap, size_t* nOut);
 int deme_query_host_bytes(const deme_ctx* ctx, uint64_t* bytes);
+/* Position code, orientation, velocity, angular velocity and family of a few owners, gathered on the device: row i of every
+ * non-null column of `out` (columns of n entries) is owner ownerIds[i]'s value, bitwise what deme_download_owner_state gives at
+ * that id.  Ids may repeat and come in any order; n == 0 is fine.  Refused (DEME_ERR_INVALID): an id out of range; a non-null a* /
+ * alpha* column (those need the reduction a full download launches).  Read-only: no reduction is launched and the list, the
+ * prescriptions and the step's buffers are left as they are.  64 bytes per id come to the host (added to deme_query_host_bytes). */
+int deme_query_owner_state(deme_ctx* ctx, const uint32_t* ownerIds, size_t n, DemeOwnerState* out);
 /* The detection's radix sort alone, on host arrays (tests): a stable sort of keys (and vals with them) by the bits
  * [beginBit, endBit) of the key; the other bits take no part in the order and arrive unchanged.  forceOwn 1: the project's own
  * sort whatever n is (DEME_ERR_INVALID from a library built with rocprim at every site); 0: what the detection's call sites
@@ -649,6 +655,28 @@ int deme_multi_num_contacts(deme_multi* m, size_t* n);
 int deme_multi_download_contacts(deme_multi* m, uint32_t* idA, uint32_t* idB, uint8_t* type, size_t cap);
 int deme_multi_download_contact_wildcard(deme_multi* m, uint32_t w, float* out, size_t cap);
 int deme_multi_download_contact_records(deme_multi* m, float* force, float* torqueOnly, float* cpA, float* cpB, size_t cap);
+/* deme_query_owner_contacts for a decomposed run, in GLOBAL ids: every slab selects from its own list on its device, with the rule
+ * of the merged list (a pair reported once, by the slab that owns the clump of the globally smaller sphere; a pair the slab holds
+ * the other way round flipped: force and torque-only force times -1, contact points swapped), and the host sorts the hits of all
+ * slabs by the merged key.  The answer is the sub-sequence of deme_multi_download_contacts / deme_multi_download_contact_records
+ * whose rows touch one of ownerIds, bit for bit, in that list's order; ownerA / ownerB are global owner ids, side as above in the
+ * merged orientation.  A repeated id counts once; *nOut receives the hit count and with cap < *nOut no row is written
+ * (DEME_ERR_INVALID).  Refused with nothing written (nOut included): an id >= the global owner count; withRecords while recording
+ * is off on a slab or a slab's list is a seed, as in the step after a migration (the messages of
+ * deme_multi_download_contact_records).  The call waits for the run (deme_multi_sync); it neither uses nor invalidates the merged
+ * list, downloads no slab's list and none of its id books.  The scratch belongs to the slabs' contexts and is kept between calls.
+ * deme_multi_query_host_bytes: every byte these calls and deme_multi_query_owner_state have copied from a device to the host since
+ * deme_multi_create -- 4 per slab and selection pass (the hit count; a slab whose hits exceed its scratch selects twice, a slab
+ * with an empty list not at all), 24 per hit row, 48 more per hit row with records; for the state call 4 per slab and 64 per owner
+ * found on it. */
+int deme_multi_query_owner_contacts(deme_multi* m, const uint32_t* ownerIds, size_t nOwners, int withRecords, uint32_t* idA, uint32_t* idB,
+                                    uint8_t* type, uint32_t* ownerA, uint32_t* ownerB, uint8_t* side, float* force, float* torqueOnly,
+                                    float* cpA, float* cpB, size_t cap, size_t* nOut);
+int deme_multi_query_host_bytes(const deme_multi* m, uint64_t* bytes);
+/* deme_query_owner_state by GLOBAL owner id: every slab gathers the listed owners it answers for (its own clumps; the replicated
+ * owners on the first slab of the chain -- the rule of deme_multi_download_state) on its device.  Values equal
+ * deme_multi_download_state indexed by the ids, bit for bit. */
+int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_t n, DemeOwnerState* out);
 /* Restart and marked pairs of a decomposed run, in GLOBAL ids: deme_seed_contacts / deme_*_persistent_contacts for every slab that holds
  * a pair (both geometries present, one of them the slab's own), in the slab's ids and with the slab's sign of the B -> A vector
  * wildcards; the downloads report a pair once (sphere-sphere pairs smaller id first, ascending). */
