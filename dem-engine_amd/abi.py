@@ -213,6 +213,7 @@ def load_library():
                                       C.POINTER(C.c_size_t)],
         "deme_query_host_bytes": [_P, C.POINTER(C.c_uint64)],
         "deme_query_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
+        "deme_scatter_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
         "deme_sort_keys_u64": [C.c_int, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P],
         "deme_change_owner_sizes": [_P, _P, _P, C.c_size_t], "deme_num_components": [_P, C.POINTER(C.c_uint32)],
@@ -711,6 +712,15 @@ class Multi:
         self._ck(self.lib.deme_multi_query_owner_state(self.h, _ptr(ids), ids.size, C.byref(st)), "deme_multi_query_owner_state")
         return out
 
+    def scatter_owner_state(self, owner_ids, arrays, n=None):
+        """deme_multi_scatter_owner_state: row i of every column of `arrays` written to GLOBAL owner owner_ids[i] on every slab that
+        holds a copy of it.  n: the count passed when owner_ids is None (tests)."""
+        ids, st = _owner_state_rows(owner_ids, arrays)
+        cnt = ids.size if ids is not None else int(n or 0)
+        self.lib.deme_multi_scatter_owner_state.argtypes = [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)]
+        self.lib.deme_multi_scatter_owner_state.restype = C.c_int
+        self._ck(self.lib.deme_multi_scatter_owner_state(self.h, _ptr(ids), cnt, C.byref(st)), "deme_multi_scatter_owner_state")
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.deme_multi_destroy(self.h)
@@ -738,6 +748,25 @@ def _owner_state_request(owner_ids, columns):
         setattr(st, name, out[name].ctypes.data)
     st._keep = out
     return ids, st, {k: v[:ids.size] for k, v in out.items()}
+
+
+def _owner_state_rows(owner_ids, arrays):
+    """the ids (None stays a null pointer) and a DemeOwnerState whose columns are those of `arrays`, one row per id, the others null"""
+    ids = None if owner_ids is None else np.ascontiguousarray(owner_ids, dtype=np.uint32).ravel()
+    st, keep = DemeOwnerState(), {}
+    for name in STATE_DTYPES:
+        a = arrays.get(name)
+        if a is None:
+            setattr(st, name, None)
+            continue
+        keep[name] = np.ascontiguousarray(a, dtype=STATE_DTYPES[name]).ravel()
+        if ids is not None and keep[name].size != ids.size:
+            raise DemeError(f"scatter_owner_state: column {name} has {keep[name].size} rows for {ids.size} ids")
+        if not keep[name].size:
+            keep[name] = np.zeros(1, STATE_DTYPES[name])  # (an empty array's pointer may be null: the column is still named)
+        setattr(st, name, keep[name].ctypes.data)
+    st._keep = keep
+    return ids, st
 
 
 def exported_symbols():
@@ -1154,6 +1183,13 @@ class Context:
         ids, st, out = _owner_state_request(owner_ids, columns)
         self._ck(self.lib.deme_query_owner_state(self.h, _ptr(ids), ids.size, C.byref(st)), "deme_query_owner_state")
         return out
+
+    def scatter_owner_state(self, owner_ids, arrays, n=None):
+        """deme_scatter_owner_state: row i of every column of the dict `arrays` written to owner owner_ids[i] on the device (ids
+        distinct, any order); the other fields and owners keep their bits.  n: the count passed when owner_ids is None (tests)."""
+        ids, st = _owner_state_rows(owner_ids, arrays)
+        cnt = ids.size if ids is not None else int(n or 0)
+        self._ck(self.lib.deme_scatter_owner_state(self.h, _ptr(ids), cnt, C.byref(st)), "deme_scatter_owner_state")
 
     def sphere_geometry(self):
         n = self.n_spheres

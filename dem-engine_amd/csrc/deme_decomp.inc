@@ -1633,6 +1633,57 @@ int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_
     return DEME_OK;
 }
 
+// deme_scatter_owner_state by GLOBAL owner id.  Every slab receives the asked ids in ascending order with their records and one
+// thread per owner slot searches its global id among them (k_scatter_owner_state): the clump in the slab that owns it, its ghost
+// copies in the neighbours and the replicated owners on every slab all take the value, as group_state_io writes them on upload.
+int deme_multi_scatter_owner_state(deme_multi* m, const uint32_t* globalIds, size_t n, const DemeOwnerState* in) {
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    if (!in || (n && !globalIds))
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: null %s", in ? "owner id array" : "state");
+    if (owner_state_wants_acc(in))
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: a / alpha columns are not written by owner id (deme_upload_owner_state hands the accumulators to the caller)");
+    if (n > 0xFFFFFFFFull)
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: %zu ids", n);
+    const uint32_t nOG = m->plan->nOwnersGlobal;
+    for (size_t i = 0; i < n; i++)
+        if (globalIds[i] >= nOG)
+            return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: owner id %u is out of range (%u owners)", globalIds[i], nOG);
+    std::vector<std::pair<uint32_t, uint32_t>> sorted;
+    uint32_t twice = 0;
+    if (!owner_ids_distinct(globalIds, n, sorted, &twice))
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: owner id %u is given twice (the order of two writes is not defined)", twice);
+    const uint32_t mask = owner_state_mask(in);
+    if (!n || !mask)
+        return DEME_OK;
+    for (auto* g : m->groups)
+        for (auto& s : g->slabs)
+            if (!s.geo.set)
+                return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: a slab has no books (deme_halo_group_set_slab / _build)");
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    std::vector<uint32_t> ids(n);
+    std::vector<OwnerRec> patch(n);
+    for (size_t i = 0; i < n; i++) {
+        ids[i] = sorted[i].first;
+        patch[i] = owner_state_patch(in, sorted[i].second);
+    }
+    m->rowsValid = false;
+    for (auto* g : m->groups) {
+        if (hipSetDevice(g->device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+        for (auto& s : g->slabs) {
+            deme_ctx* c = s.ctx;
+            if (int rc = check_ready(c))
+                return mfail(m, rc, "%s", c->err.c_str());
+            if (int rc = launch_owner_scatter(c, in, ids, patch, mask, true, (const uint32_t*)s.geo.ownerGid))
+                return mfail(m, rc, "%s", c->err.c_str());
+            m->qHostBytes += (uint64_t)n * (4 + sizeof(OwnerRec));
+        }
+    }
+    return DEME_OK;
+}
+
 // accelerations a script adds for the next step (deme_add_owner_acc), by GLOBAL owner id: a clump's go to the slab that owns it, a
 // replicated owner's (walls, meshes: the same on every slab) to every slab
 int deme_multi_add_owner_acc(deme_multi* m, uint32_t owner, uint32_t n, const float* acc, const float* angAcc) {

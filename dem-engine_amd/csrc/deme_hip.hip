@@ -2118,14 +2118,22 @@ static int owner_state_io(deme_ctx* c, const DemeOwnerState* st, int dir) {
     return DEME_OK;
 }
 
-int deme_upload_owner_state(deme_ctx* c, const DemeOwnerState* st) {
-    if (c && st && st->familyID)
+// what a write of these columns into the owner records does to the context's flags: deme_upload_owner_state (all owners) and
+// deme_scatter_owner_state (a few) both call it before they write
+static void owner_state_written(deme_ctx* c, const DemeOwnerState* st) {
+    if (st->familyID)
         c->prescDirty = true;  // owners may have changed family
-    if (c)
-        c->fusedPrevValid = false;
-    if (c && st && (st->voxelID || st->locX || st->locY || st->locZ || st->oriQw || st->oriQx || st->oriQy || st->oriQz || st->vX ||
-                    st->vY || st->vZ || st->omgBarX || st->omgBarY || st->omgBarZ || st->familyID))
+    c->fusedPrevValid = false;
+    if (st->voxelID || st->locX || st->locY || st->locZ || st->oriQw || st->oriQx || st->oriQy || st->oriQz || st->vX || st->vY || st->vZ ||
+        st->omgBarX || st->omgBarY || st->omgBarZ || st->familyID)
         c->listStale = true;  // pose, velocity (it sizes the margins) or family (masks) changed under the K-step list
+}
+
+int deme_upload_owner_state(deme_ctx* c, const DemeOwnerState* st) {
+    if (c && st)
+        owner_state_written(c, st);
+    else if (c)
+        c->fusedPrevValid = false;
     return owner_state_io(c, st, 0);
 }
 int deme_download_owner_state(deme_ctx* c, DemeOwnerState* st) { return owner_state_io(c, st, 1); }
@@ -4652,6 +4660,99 @@ int deme_query_owner_state(deme_ctx* c, const uint32_t* ownerIds, size_t n, Deme
     c->qHostBytes += (uint64_t)n * sizeof(OwnerRec);
     for (size_t i = 0; i < n; i++)
         owner_state_row(out, i, h[i]);
+    return DEME_OK;
+}
+
+// ---- writing them (deme_query.h: k_scatter_owner_state) ---------------------------------------------------------------------------
+namespace {
+// the columns a call gave as the kernel's mask, and row `at` of them as the record the kernel reads its values from
+inline uint32_t owner_state_mask(const DemeOwnerState* in) {
+    return (in->voxelID ? DEME_SCATTER_VOXEL : 0u) | (in->locX ? DEME_SCATTER_LOCX : 0u) | (in->locY ? DEME_SCATTER_LOCY : 0u) |
+           (in->locZ ? DEME_SCATTER_LOCZ : 0u) | (in->oriQw ? DEME_SCATTER_QW : 0u) | (in->oriQx ? DEME_SCATTER_QX : 0u) |
+           (in->oriQy ? DEME_SCATTER_QY : 0u) | (in->oriQz ? DEME_SCATTER_QZ : 0u) | (in->vX ? DEME_SCATTER_VX : 0u) |
+           (in->vY ? DEME_SCATTER_VY : 0u) | (in->vZ ? DEME_SCATTER_VZ : 0u) | (in->omgBarX ? DEME_SCATTER_WX : 0u) |
+           (in->omgBarY ? DEME_SCATTER_WY : 0u) | (in->omgBarZ ? DEME_SCATTER_WZ : 0u) | (in->familyID ? DEME_SCATTER_FAMILY : 0u);
+}
+inline OwnerRec owner_state_patch(const DemeOwnerState* in, size_t at) {
+    OwnerRec r{};
+    if (in->voxelID) r.voxelID = in->voxelID[at];
+    if (in->locX) r.locX = in->locX[at];
+    if (in->locY) r.locY = in->locY[at];
+    if (in->locZ) r.locZ = in->locZ[at];
+    if (in->oriQw) r.qw = in->oriQw[at];
+    if (in->oriQx) r.qx = in->oriQx[at];
+    if (in->oriQy) r.qy = in->oriQy[at];
+    if (in->oriQz) r.qz = in->oriQz[at];
+    if (in->vX) r.vx = in->vX[at];
+    if (in->vY) r.vy = in->vY[at];
+    if (in->vZ) r.vz = in->vZ[at];
+    if (in->omgBarX) r.wx = in->omgBarX[at];
+    if (in->omgBarY) r.wy = in->omgBarY[at];
+    if (in->omgBarZ) r.wz = in->omgBarZ[at];
+    if (in->familyID) r.family = in->familyID[at];
+    return r;
+}
+// (id, row of the call) sorted by id; false when an id comes twice (*twice receives it)
+inline bool owner_ids_distinct(const uint32_t* ids, size_t n, std::vector<std::pair<uint32_t, uint32_t>>& sorted, uint32_t* twice) {
+    sorted.resize(n);
+    for (size_t i = 0; i < n; i++)
+        sorted[i] = {ids[i], (uint32_t)i};
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < n; i++)
+        if (sorted[i].first == sorted[i - 1].first) {
+            *twice = sorted[i].first;
+            return false;
+        }
+    return true;
+}
+// keys (4 bytes each) and records (64 bytes each) to the device, the kernel, and the wait that lets the host arrays go
+// (the flags of a write of `in`'s columns are set once the scratch is there: a call that fails before it has changed nothing)
+int launch_owner_scatter(deme_ctx* c, const DemeOwnerState* in, const std::vector<uint32_t>& keys, const std::vector<OwnerRec>& patch,
+                         uint32_t mask, bool byGid, const uint32_t* ownerGid) {
+    const size_t n = keys.size();
+    if (ensure(c, c->stage, n * 4) || ensure(c, c->qState, n * sizeof(OwnerRec)))
+        return c->lastStatus;
+    owner_state_written(c, in);
+    HIPCK(hipMemcpyAsync(c->stage.p, keys.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(c->qState.p, patch.data(), n * sizeof(OwnerRec), hipMemcpyHostToDevice, c->stream));
+    const uint32_t threads = byGid ? c->nOwners : (uint32_t)n;
+    if (threads)
+        hipLaunchKernelGGL(k_scatter_owner_state, dim3(grid_for(threads)), dim3(256), 0, c->stream, threads, c->owners.as<OwnerRec>(), c->nOwners,
+                           c->stage.as<uint32_t>(), (uint32_t)n, c->qState.as<OwnerRec>(), mask, byGid ? c->dp.o2e : (const uint32_t*)nullptr,
+                           byGid ? ownerGid : (const uint32_t*)nullptr);
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+}  // namespace
+
+int deme_scatter_owner_state(deme_ctx* c, const uint32_t* ownerIds, size_t n, const DemeOwnerState* in) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (!in || (n && !ownerIds))
+        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: null %s", in ? "owner id array" : "state");
+    if (owner_state_wants_acc(in))
+        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: a / alpha columns are not written by owner id (deme_upload_owner_state hands the accumulators to the caller)");
+    if (n > 0xFFFFFFFFull)
+        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: %zu ids", n);
+    for (size_t i = 0; i < n; i++)
+        if (ownerIds[i] >= c->nOwners)
+            return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: owner id %u is out of range (%u owners)", ownerIds[i], c->nOwners);
+    std::vector<std::pair<uint32_t, uint32_t>> sorted;
+    uint32_t twice = 0;
+    if (!owner_ids_distinct(ownerIds, n, sorted, &twice))
+        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: owner id %u is given twice (the order of two writes is not defined)", twice);
+    const uint32_t mask = owner_state_mask(in);
+    if (!n || !mask)
+        return DEME_OK;
+    std::vector<uint32_t> slots(n);
+    std::vector<OwnerRec> patch(n);
+    for (size_t i = 0; i < n; i++) {
+        slots[i] = c->permuted ? c->hE2O[ownerIds[i]] : ownerIds[i];
+        patch[i] = owner_state_patch(in, i);
+    }
+    if (int rc = launch_owner_scatter(c, in, slots, patch, mask, false, nullptr))
+        return rc;
+    c->qHostBytes += (uint64_t)n * (4 + sizeof(OwnerRec));
     return DEME_OK;
 }
 

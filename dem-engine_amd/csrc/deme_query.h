@@ -10,6 +10,7 @@
 //   k_query_select_slab  the same for one slab of a decomposed run: global ids from the device books, the merged list's
 //                   report-once and flip rules (deme_multi_query_owner_contacts)
 //   k_query_owner_state  the 64-byte records of a few owners: a gather by slot, or one slab's share of a question in global ids
+//   k_scatter_owner_state  its counterpart: named fields of a few owners' records replaced, by slot or by global id on a slab
 // A thread writes only below the scratch's capacity while the counter counts every hit: the host reads the count, grows the
 // scratch and selects again when it was too small (deme_hip.hip).  The order of the hits is the atomics'; the host sorts them.
 #pragma once
@@ -236,6 +237,82 @@ __global__ __launch_bounds__(256) void k_query_owner_state(uint32_t n, const Own
     const uint32_t at = query_append_slot(hit, nHits);
     if (at < cap)
         query_state_write(out, at, owners, i, gid);
+}
+
+// ---- writing pose, velocity and family of a few owners (deme_scatter_owner_state, deme_multi_scatter_owner_state) ------------------
+// The host sends one 64-byte record per id with the new values in their fields (the rest of it is not read) and a mask of the
+// columns the call gave: bit k is column k of DemeOwnerState in the order below.  What a write touches is what k_pack_owners
+// touches with dir == 0: margin, inertiaOff and the flag bits of the family word keep their bits.
+#define DEME_SCATTER_VOXEL 0x0001u
+#define DEME_SCATTER_LOCX 0x0002u
+#define DEME_SCATTER_LOCY 0x0004u
+#define DEME_SCATTER_LOCZ 0x0008u
+#define DEME_SCATTER_QW 0x0010u
+#define DEME_SCATTER_QX 0x0020u
+#define DEME_SCATTER_QY 0x0040u
+#define DEME_SCATTER_QZ 0x0080u
+#define DEME_SCATTER_VX 0x0100u
+#define DEME_SCATTER_VY 0x0200u
+#define DEME_SCATTER_VZ 0x0400u
+#define DEME_SCATTER_WX 0x0800u
+#define DEME_SCATTER_WY 0x1000u
+#define DEME_SCATTER_WZ 0x2000u
+#define DEME_SCATTER_FAMILY 0x4000u
+
+__device__ inline void scatter_state_write(OwnerRec* __restrict__ owners, uint32_t slot, const OwnerRec* __restrict__ patch, uint32_t row,
+                                           uint32_t mask) {
+    OwnerRec r = owners[slot];
+    const OwnerRec p = patch[row];
+    if (mask & DEME_SCATTER_VOXEL) r.voxelID = p.voxelID;
+    if (mask & DEME_SCATTER_LOCX) r.locX = p.locX;
+    if (mask & DEME_SCATTER_LOCY) r.locY = p.locY;
+    if (mask & DEME_SCATTER_LOCZ) r.locZ = p.locZ;
+    if (mask & DEME_SCATTER_QW) r.qw = p.qw;
+    if (mask & DEME_SCATTER_QX) r.qx = p.qx;
+    if (mask & DEME_SCATTER_QY) r.qy = p.qy;
+    if (mask & DEME_SCATTER_QZ) r.qz = p.qz;
+    if (mask & DEME_SCATTER_VX) r.vx = p.vx;
+    if (mask & DEME_SCATTER_VY) r.vy = p.vy;
+    if (mask & DEME_SCATTER_VZ) r.vz = p.vz;
+    if (mask & DEME_SCATTER_WX) r.wx = p.wx;
+    if (mask & DEME_SCATTER_WY) r.wy = p.wy;
+    if (mask & DEME_SCATTER_WZ) r.wz = p.wz;
+    if (mask & DEME_SCATTER_FAMILY) r.family = (r.family & OWNER_FLAG_BITS) | (p.family & 0xFFu);  // a ghost stays a ghost
+    owners[slot] = r;
+}
+
+// ownerGid == null: a scatter by slot -- thread i writes patch[i] into owner keys[i] (the host translated the caller's ids; they
+// are distinct, so no two threads write one record).  n = nKeys threads.
+// Otherwise one thread per owner slot of the slab (n = nOwners): the slot's global id looked up as k_query_owner_state does and
+// searched in keys, the asked ids in ascending order with patch in the same order.  Every copy on the slab is written: its own
+// clump, a ghost of a neighbour's, a replicated owner (the rule of an upload of the whole state by global id).
+__global__ __launch_bounds__(256) void k_scatter_owner_state(uint32_t n, OwnerRec* __restrict__ owners, uint32_t nOwners,
+                                                             const uint32_t* __restrict__ keys, uint32_t nKeys,
+                                                             const OwnerRec* __restrict__ patch, uint32_t mask,
+                                                             const uint32_t* __restrict__ o2e, const uint32_t* __restrict__ ownerGid) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    if (!ownerGid) {
+        const uint32_t slot = keys[i];
+        if (slot < nOwners)
+            scatter_state_write(owners, slot, patch, i, mask);
+        return;
+    }
+    const uint32_t s = o2e ? o2e[i] : i;  // the slab scene's id of this slot
+    if (s >= nOwners)
+        return;
+    const uint32_t gid = ownerGid[s];
+    uint32_t lo = 0, hi = nKeys;  // the first key >= gid
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < gid)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    if (lo < nKeys && keys[lo] == gid)
+        scatter_state_write(owners, i, patch, lo, mask);
 }
 
 }  // namespace deme_dev

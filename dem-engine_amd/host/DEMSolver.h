@@ -761,7 +761,7 @@ class DEMSolver {
     }
     void ChangeFamily(unsigned int ID_from, unsigned int ID_to) {
         each_ctx([&](deme_ctx* c) { return deme_change_family(c, ID_from, ID_to); });
-        m_state_fresh = false;
+        state_changed();
     }
     // ---- wildcard values (API.h:852-868, 936-1014).  Owner and geometry wildcards belong to a user force model
     // (SetPerOwnerWildcards / SetPerGeometryWildcards); contact wildcards to whichever model runs.  Post-Initialize calls.
@@ -935,13 +935,23 @@ class DEMSolver {
     void SetOwnerAngVel(unsigned int owner, float3 w) { set_owner(owner, nullptr, nullptr, &w, nullptr); }
     void SetOwnerOriQ(unsigned int owner, float4 q) { set_owner(owner, nullptr, nullptr, nullptr, &q); }
     void SetOwnerFamily(unsigned int owner, unsigned int fam, size_t n = 1) {
+        if (!tracker_on_host()) {  // one scatter of the family of the n owners
+            std::vector<bodyID_t> ids;
+            for (size_t k = 0; k < n && owner + k < m_n_owners; k++)
+                ids.push_back((bodyID_t)(owner + k));
+            std::vector<uint8_t> f(ids.size(), (uint8_t)fam);
+            DemeOwnerState st{};
+            st.familyID = f.data();
+            scatter_owner_state(ids, &st);
+            return;
+        }
         std::vector<uint8_t> f = owner_families();
         for (size_t k = 0; k < n && owner + k < f.size(); k++)
             f[owner + k] = (uint8_t)fam;
         DemeOwnerState st{};
         st.familyID = f.data();
         ul_state(&st);
-        m_state_fresh = false;
+        state_changed();
     }
     /// every clump whose CoM lies in the box becomes family `fam_num`; returns how many did (API.h:699-709)
     size_t ChangeClumpFamily(unsigned int fam_num, const std::pair<double, double>& X = {-1e30, 1e30},
@@ -1103,7 +1113,7 @@ class DEMSolver {
             mc_seed_contacts(a.data(), b.data(), ty.data(), nW ? W.data() : nullptr, nc);
         if (nP)
             mc_upload_persistent_contacts(pa.data(), pb.data(), pt.data(), nP);
-        m_state_fresh = false;
+        state_changed();
         m_steps_since_replan = 0;
     }
     /// A decomposed run cut anew by where the clumps are now: fresh slabs in the engine's own order (the migration appends arrivals
@@ -1300,7 +1310,7 @@ class DEMSolver {
             remap(pa, pb, pt, nullptr);
             mc_upload_persistent_contacts(pa.data(), pb.data(), pt.data(), nP);
         }
-        m_state_fresh = false;
+        state_changed();
         return new_of_old;
     }
     /// UpdateStepSize (API.h:1274): takes effect from the next step
@@ -2002,6 +2012,7 @@ class DEMSolver {
             check(deme_download_owner_state(m_ctx, st));
     }
     void ul_state(const DemeOwnerState* st) {
+        m_state_epoch++;
         if (m_multi)
             mcheck(deme_multi_upload_state(m_multi, st, (uint32_t)m_n_owners));
         else
@@ -2145,6 +2156,24 @@ class DEMSolver {
     static bool query_on_host() {
         static const bool on = [] {
             const char* e = std::getenv("DEME_QUERY_HOST");
+            return e && std::atoi(e) != 0;
+        }();
+        return on;
+    }
+    /// row i of the non-null columns of `st` written to owner ids[i] (distinct ids), on the device
+    void scatter_owner_state(const std::vector<bodyID_t>& ids, const DemeOwnerState* st) {
+        if (ids.empty())
+            return;
+        if (m_multi)
+            mcheck(deme_multi_scatter_owner_state(m_multi, ids.data(), ids.size(), st));
+        else
+            check(deme_scatter_owner_state(m_ctx, ids.data(), ids.size(), st));
+        state_changed();
+    }
+    /// DEME_TRACKER_HOST=1 (tests): the tracker getters and the owner setters keep the paths that move the whole state
+    static bool tracker_on_host() {
+        static const bool on = [] {
+            const char* e = std::getenv("DEME_TRACKER_HOST");
             return e && std::atoi(e) != 0;
         }();
         return on;
@@ -2299,6 +2328,8 @@ class DEMSolver {
     }
     double m_time = 0;
     bool m_state_fresh = false;
+    uint64_t m_state_epoch = 0;  // counts the changes of the owners' state: what a tracker's gathered records are valid for
+    void state_changed() { m_state_fresh = false, m_state_epoch++; }
     std::vector<float3> m_pos;
     std::vector<float> m_st_v[3];
 
@@ -2596,8 +2627,57 @@ class DEMSolver {
             }
         each_ctx([&](deme_ctx* c) { return deme_update_tri_nodes(c, t1.data(), t2.data(), t3.data()); });
     }
-    // tracker setters: read-modify-write of the affected SoA columns (null columns keep their device values)
+    // positionToVoxelID of (pos - LBF), as at initialisation
+    void position_code(const float3& pos, uint64_t& vid, uint16_t& lx, uint16_t& ly, uint16_t& lz) const {
+        const double P[3] = {(double)(pos.x - m_p.LBFX), (double)(pos.y - m_p.LBFY), (double)(pos.z - m_p.LBFZ)};
+        uint64_t nn[3];
+        uint16_t ss[3];
+        for (int k = 0; k < 3; k++) {
+            nn[k] = (uint64_t)(P[k] / m_p.voxelSize);
+            ss[k] = (uint16_t)((P[k] - (double)nn[k] * m_p.voxelSize) / m_p.l);
+        }
+        vid = nn[0] + (nn[1] << m_p.nvXp2) + (nn[2] << (m_p.nvXp2 + m_p.nvYp2));
+        lx = ss[0], ly = ss[1], lz = ss[2];
+    }
+    // tracker setters: one scatter of the given fields for the given owners (entry k of a non-null array goes to ids[k]);
+    // DEME_TRACKER_HOST=1: a read-modify-write of the affected SoA columns over all owners, owner by owner
+    void set_owners(const std::vector<bodyID_t>& ids, const float3* pos, const float3* vel, const float3* angvel, const float4* q) {
+        if (tracker_on_host()) {
+            for (size_t k = 0; k < ids.size(); k++)
+                set_owner_whole_state(ids[k], pos ? pos + k : nullptr, vel ? vel + k : nullptr, angvel ? angvel + k : nullptr, q ? q + k : nullptr);
+            return;
+        }
+        const size_t n = ids.size();
+        std::vector<uint64_t> vid(n);
+        std::vector<uint16_t> lx(n), ly(n), lz(n);
+        std::vector<float> f[10];
+        for (auto& v : f)
+            v.resize(n);
+        DemeOwnerState st{};
+        for (size_t k = 0; k < n; k++) {
+            if (pos)
+                position_code(pos[k], vid[k], lx[k], ly[k], lz[k]);
+            if (q)
+                f[0][k] = q[k].w, f[1][k] = q[k].x, f[2][k] = q[k].y, f[3][k] = q[k].z;
+            if (vel)
+                f[4][k] = vel[k].x, f[5][k] = vel[k].y, f[6][k] = vel[k].z;
+            if (angvel)
+                f[7][k] = angvel[k].x, f[8][k] = angvel[k].y, f[9][k] = angvel[k].z;
+        }
+        if (pos)
+            st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
+        if (q)
+            st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
+        if (vel)
+            st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
+        if (angvel)
+            st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
+        scatter_owner_state(ids, &st);
+    }
     void set_owner(size_t o, const float3* pos, const float3* vel, const float3* angvel, const float4* q) {
+        set_owners({(bodyID_t)o}, pos, vel, angvel, q);
+    }
+    void set_owner_whole_state(size_t o, const float3* pos, const float3* vel, const float3* angvel, const float4* q) {
         const size_t n = m_n_owners;
         std::vector<uint64_t> vid(n);
         std::vector<uint16_t> lx(n), ly(n), lz(n);
@@ -2610,17 +2690,8 @@ class DEMSolver {
         st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
         st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
         dl_state(&st);
-        if (pos) {  // positionToVoxelID of (pos - LBF), as at initialisation
-            const double P[3] = {(double)(pos->x - m_p.LBFX), (double)(pos->y - m_p.LBFY), (double)(pos->z - m_p.LBFZ)};
-            uint64_t nn[3];
-            uint16_t ss[3];
-            for (int k = 0; k < 3; k++) {
-                nn[k] = (uint64_t)(P[k] / m_p.voxelSize);
-                ss[k] = (uint16_t)((P[k] - (double)nn[k] * m_p.voxelSize) / m_p.l);
-            }
-            vid[o] = nn[0] + (nn[1] << m_p.nvXp2) + (nn[2] << (m_p.nvXp2 + m_p.nvYp2));
-            lx[o] = ss[0], ly[o] = ss[1], lz[o] = ss[2];
-        }
+        if (pos)
+            position_code(*pos, vid[o], lx[o], ly[o], lz[o]);
         if (q)
             f[0][o] = q->w, f[1][o] = q->x, f[2][o] = q->y, f[3][o] = q->z;
         if (vel)
@@ -2628,7 +2699,7 @@ class DEMSolver {
         if (angvel)
             f[7][o] = angvel->x, f[8][o] = angvel->y, f[9][o] = angvel->z;
         ul_state(&st);
-        m_state_fresh = false;
+        state_changed();
     }
     void step(uint32_t n) {
         while (n) {
@@ -2641,7 +2712,7 @@ class DEMSolver {
                 check(deme_step(m_ctx, k));
             m_time += (double)k * (double)m_h;
             m_steps_since_replan += k;
-            m_state_fresh = false;
+            state_changed();
             n -= k;
             if (m_multi && m_replan_every && m_steps_since_replan >= m_replan_every)
                 ReplanSlabs();  // (after the steps: what a script queued for its next step -- AddAcc -- has been consumed by then)
@@ -3065,7 +3136,7 @@ class DEMSolver {
             });
         }
         m_n_clumps = nC, m_n_owners = nO;
-        m_state_fresh = false;
+        state_changed();
         {  // initial owner-wildcard values the batches carry (DEMClumpBatch::AddOwnerWildcard)
             size_t first = 0;
             for (auto& bt : m_batches) {
@@ -3219,10 +3290,26 @@ class DEMTracker {
             f[i] = GetFamily(i);
         return f;
     }
-    float3 Pos(size_t offset = 0) { return m_sys->GetOwnerPosition(GetOwnerID(offset)); }
-    float3 Vel(size_t offset = 0) { return m_sys->GetOwnerVelocity(GetOwnerID(offset)); }
-    float3 AngVelLocal(size_t offset = 0) { return column3(offset, 2); }
+    // Pos, Vel, AngVelLocal, OriQ and GetFamily read the records of the tracked owners, gathered in one query the first time one of
+    // them is asked after the solver's state changed (gathered()); DEME_TRACKER_HOST=1 keeps the downloads of the whole state
+    float3 Pos(size_t offset = 0) {
+        if (DEMSolver::tracker_on_host())
+            return m_sys->GetOwnerPosition(GetOwnerID(offset));
+        return gathered().pos[in_range(offset)];
+    }
+    float3 Vel(size_t offset = 0) {
+        if (DEMSolver::tracker_on_host())
+            return m_sys->GetOwnerVelocity(GetOwnerID(offset));
+        return gathered().vel[in_range(offset)];
+    }
+    float3 AngVelLocal(size_t offset = 0) {
+        if (DEMSolver::tracker_on_host())
+            return column3(offset, 2);
+        return gathered().w[in_range(offset)];
+    }
     float4 OriQ(size_t offset = 0) {
+        if (!DEMSolver::tracker_on_host())
+            return gathered().q[in_range(offset)];
         const DEMSolver::Snapshot sn = m_sys->snapshot(false);
         return sn.q[GetOwnerID(offset)];
     }
@@ -3242,6 +3329,7 @@ class DEMTracker {
             x += (bodyID_t)first;
         m_sys->ChangeClumpSizes(ids, factors);
     }
+    // setters: one scatter of the named fields per call, the vector forms included (DEMSolver::set_owners)
     void SetPos(float3 pos, size_t offset = 0) { m_sys->set_owner(GetOwnerID(offset), &pos, nullptr, nullptr, nullptr); }
     void SetVel(float3 vel, size_t offset = 0) { m_sys->set_owner(GetOwnerID(offset), nullptr, &vel, nullptr, nullptr); }
     void SetAngVel(float3 w, size_t offset = 0) { m_sys->set_owner(GetOwnerID(offset), nullptr, nullptr, &w, nullptr); }
@@ -3259,7 +3347,11 @@ class DEMTracker {
     }
     float Mass(size_t offset = 0) { return m_sys->GetOwnerMass(GetOwnerID(offset)); }
     float3 MOI(size_t offset = 0) { return m_sys->GetOwnerMOI(GetOwnerID(offset)); }
-    unsigned int GetFamily(size_t offset = 0) { return m_sys->GetOwnerFamily(GetOwnerID(offset)); }
+    unsigned int GetFamily(size_t offset = 0) {
+        if (DEMSolver::tracker_on_host())
+            return m_sys->GetOwnerFamily(GetOwnerID(offset));
+        return gathered().fam[in_range(offset)];
+    }
     void SetFamily(unsigned int fam_num) { m_sys->SetOwnerFamily(GetOwnerID(0), fam_num, m_n); }
     void SetFamily(unsigned int fam_num, size_t offset) { m_sys->SetOwnerFamily(GetOwnerID(offset), fam_num, 1); }
     static std::vector<float> vec3(float3 v) { return {v.x, v.y, v.z}; }
@@ -3275,22 +3367,10 @@ class DEMTracker {
         const float4 q = OriQ(offset);
         return {q.x, q.y, q.z, q.w};
     }
-    void SetPos(const std::vector<float3>& pos) {
-        for (size_t k = 0; k < pos.size() && k < m_n; k++)
-            SetPos(pos[k], k);
-    }
-    void SetVel(const std::vector<float3>& vel) {
-        for (size_t k = 0; k < vel.size() && k < m_n; k++)
-            SetVel(vel[k], k);
-    }
-    void SetAngVel(const std::vector<float3>& w) {
-        for (size_t k = 0; k < w.size() && k < m_n; k++)
-            SetAngVel(w[k], k);
-    }
-    void SetOriQ(const std::vector<float4>& q) {
-        for (size_t k = 0; k < q.size() && k < m_n; k++)
-            SetOriQ(q[k], k);
-    }
+    void SetPos(const std::vector<float3>& pos) { m_sys->set_owners(first_owner_ids(pos.size()), pos.data(), nullptr, nullptr, nullptr); }
+    void SetVel(const std::vector<float3>& vel) { m_sys->set_owners(first_owner_ids(vel.size()), nullptr, vel.data(), nullptr, nullptr); }
+    void SetAngVel(const std::vector<float3>& w) { m_sys->set_owners(first_owner_ids(w.size()), nullptr, nullptr, w.data(), nullptr); }
+    void SetOriQ(const std::vector<float4>& q) { m_sys->set_owners(first_owner_ids(q.size()), nullptr, nullptr, nullptr, q.data()); }
     std::vector<float> GetOwnerWildcardValues(const std::string& name) {
         const std::vector<float> all = m_sys->GetAllOwnerWildcardValue(name);
         const size_t o0 = GetOwnerID(0);
@@ -3413,11 +3493,55 @@ class DEMTracker {
         m_sys->add_owner_acc(GetOwnerID(0), (uint32_t)m_n, linear ? flat.data() : nullptr,
                                         linear ? nullptr : flat.data());
     }
-    std::vector<bodyID_t> all_owner_ids() const {
-        std::vector<bodyID_t> ids(m_n);
-        for (size_t k = 0; k < m_n; k++)
+    std::vector<bodyID_t> all_owner_ids() const { return first_owner_ids(m_n); }
+    std::vector<bodyID_t> first_owner_ids(size_t n) const {  // the first min(n, all) tracked owners
+        std::vector<bodyID_t> ids(std::min(n, m_n));
+        for (size_t k = 0; k < ids.size(); k++)
             ids[k] = GetOwnerID(k);
         return ids;
+    }
+    // the tracked owners' records as of the solver's state epoch `epoch`, one entry per offset
+    struct Gathered {
+        bool valid = false;
+        uint64_t epoch = 0;
+        std::vector<float3> pos, vel, w;
+        std::vector<float4> q;
+        std::vector<unsigned int> fam;
+    };
+    Gathered m_gathered;
+    const Gathered& gathered() {
+        Gathered& g = m_gathered;
+        if (g.valid && g.epoch == m_sys->m_state_epoch)
+            return g;
+        const std::vector<bodyID_t> ids = all_owner_ids();
+        const size_t n = ids.size();
+        std::vector<uint64_t> vid(n);
+        std::vector<uint16_t> lx(n), ly(n), lz(n);
+        std::vector<float> f[10];
+        for (auto& v : f)
+            v.resize(n);
+        std::vector<uint8_t> fam(n);
+        DemeOwnerState st{};
+        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
+        st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
+        st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
+        st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
+        st.familyID = fam.data();
+        m_sys->query_owner_state(ids, &st);
+        g.pos.resize(n), g.vel.resize(n), g.w.resize(n), g.q.resize(n), g.fam.resize(n);
+        const DemeParams& p = m_sys->m_p;
+        for (size_t i = 0; i < n; i++) {  // the position as DEMSolver::refresh_state() computes it
+            const uint64_t vx = vid[i] & ((1ull << p.nvXp2) - 1), vy = (vid[i] >> p.nvXp2) & ((1ull << p.nvYp2) - 1),
+                           vz = vid[i] >> (p.nvXp2 + p.nvYp2);
+            g.pos[i] = {(float)((double)vx * p.voxelSize + (double)lx[i] * p.l + p.LBFX), (float)((double)vy * p.voxelSize + (double)ly[i] * p.l + p.LBFY),
+                        (float)((double)vz * p.voxelSize + (double)lz[i] * p.l + p.LBFZ)};
+            g.q[i] = {f[1][i], f[2][i], f[3][i], f[0][i]};
+            g.vel[i] = {f[4][i], f[5][i], f[6][i]};
+            g.w[i] = {f[7][i], f[8][i], f[9][i]};
+            g.fam[i] = fam[i];
+        }
+        g.epoch = m_sys->m_state_epoch, g.valid = true;
+        return g;
     }
     size_t in_range(size_t offset) const {
         if (offset >= m_n)

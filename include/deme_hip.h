@@ -321,6 +321,19 @@ int deme_query_host_bytes(const deme_ctx* ctx, uint64_t* bytes);
  * alpha* column (those need the reduction a full download launches).  Read-only: no reduction is launched and the list, the
  * prescriptions and the step's buffers are left as they are.  64 bytes per id come to the host (added to deme_query_host_bytes). */
 int deme_query_owner_state(deme_ctx* ctx, const uint32_t* ownerIds, size_t n, DemeOwnerState* out);
+/* The counterpart: row i of every non-null column of `in` (columns of n entries) is written to owner ownerIds[i], on the device.
+ * What is written is what deme_upload_owner_state writes for those columns -- position code, orientation, velocity, angular
+ * velocity, and the family with the record's ghost / replicated bits kept --; every other field, the accumulators and every owner
+ * not named keep their bits.  Ids come in any order.  Refused with nothing changed, no flag included (DEME_ERR_INVALID): a null
+ * `in`; null ids with n > 0; an id out of range; an id given twice (the order of two writes is not defined); a non-null a* / alpha*
+ * column (the caller does not take over the accumulators through this call: deme_upload_owner_state does that).  n == 0, or no
+ * column at all, returns DEME_OK and changes nothing.  Otherwise the context's flags are set as deme_upload_owner_state sets them
+ * for the same columns: the replayable step is dropped, the contact list is stale (any pose, velocity or family column: the next
+ * step detects, also on a run with asynchronous detection), the prescriptions are looked up again (familyID).  There is no rule
+ * that keeps the list when a write stays within the margins.  An error that is not one of these refusals (no memory for the
+ * scratch, a failed copy) may leave the flags set, which costs a detection and nothing else.  Bytes: 68 * n go to the device (a 4-byte slot and a 64-byte record
+ * per id), independent of the number of owners; they are added to deme_query_host_bytes. */
+int deme_scatter_owner_state(deme_ctx* ctx, const uint32_t* ownerIds, size_t n, const DemeOwnerState* in);
 /* The detection's radix sort alone, on host arrays (tests): a stable sort of keys (and vals with them) by the bits
  * [beginBit, endBit) of the key; the other bits take no part in the order and arrive unchanged.  forceOwn 1: the project's own
  * sort whatever n is (DEME_ERR_INVALID from a library built with rocprim at every site); 0: what the detection's call sites
@@ -677,6 +690,14 @@ int deme_multi_query_host_bytes(const deme_multi* m, uint64_t* bytes);
  * owners on the first slab of the chain -- the rule of deme_multi_download_state) on its device.  Values equal
  * deme_multi_download_state indexed by the ids, bit for bit. */
 int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_t n, DemeOwnerState* out);
+/* deme_scatter_owner_state by GLOBAL owner id, with its refusals.  Every copy takes the value: the clump in the slab that owns
+ * it, its ghost copies in the neighbour slabs, a replicated owner on every slab -- as deme_multi_upload_state writes them; the state
+ * afterwards equals that upload's, bit for bit.  A position written across a cut moves no clump between slabs before the next
+ * migration, as with the whole upload.  The flags are set on every slab and the merged list is dropped.  An error that is not a
+ * refusal may leave the slabs before the failing one written.  The call waits for the
+ * run (deme_multi_sync).  Bytes: 68 * n per slab go to the devices (the sorted ids and their records; every slab searches them for
+ * the owners it holds), independent of the number of owners; added to deme_multi_query_host_bytes. */
+int deme_multi_scatter_owner_state(deme_multi* m, const uint32_t* globalIds, size_t n, const DemeOwnerState* in);
 /* Restart and marked pairs of a decomposed run, in GLOBAL ids: deme_seed_contacts / deme_*_persistent_contacts for every slab that holds
  * a pair (both geometries present, one of them the slab's own), in the slab's ids and with the slab's sign of the B -> A vector
  * wildcards; the downloads report a pair once (sphere-sphere pairs smaller id first, ascending). */
