@@ -466,25 +466,15 @@ inline void rows_in(T* dst, const T* src, const std::vector<uint32_t>& gid) {
     for (size_t i = 0; i < gid.size(); i++)  // ghosts and replicated owners included: every copy takes the caller's value
         dst[i] = src[gid[i]];
 }
-struct OwnerStateBuf {
-    std::vector<uint64_t> vox;
-    std::vector<uint16_t> l[3];
-    std::vector<float> f[16];
-    std::vector<uint8_t> fam;
+struct OwnerStateBuf {  // host room for every column of n owners, named by st
+#define DEME_COL(abi, T, Rec, f) std::vector<T> abi;
+    DEME_OWNER_COLS(DEME_COL, DEME_COL, DEME_COL)
+#undef DEME_COL
     DemeOwnerState st{};
     explicit OwnerStateBuf(size_t n) {
-        vox.resize(n), fam.resize(n);
-        for (auto& v : l)
-            v.resize(n);
-        for (auto& v : f)
-            v.resize(n);
-        st.voxelID = vox.data(), st.locX = l[0].data(), st.locY = l[1].data(), st.locZ = l[2].data();
-        st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
-        st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
-        st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
-        st.aX = f[10].data(), st.aY = f[11].data(), st.aZ = f[12].data();
-        st.alphaX = f[13].data(), st.alphaY = f[14].data(), st.alphaZ = f[15].data();
-        st.familyID = fam.data();
+#define DEME_COL(abi, T, Rec, f) abi.resize(n), st.abi = abi.data();
+        DEME_OWNER_COLS(DEME_COL, DEME_COL, DEME_COL)
+#undef DEME_COL
     }
 };
 }  // namespace
@@ -512,20 +502,16 @@ static int group_state_io(deme_halo_group* g, DemeOwnerState* glob, uint32_t nOw
         if (down) {
             if (int rc = deme_download_owner_state(c, &b.st))
                 return gfail(g, rc, "state by global id (slab %zu): %s", k, c->err.c_str());
-#define DEME_ROW(F) rows_out(glob->F, (decltype(glob->F))b.st.F, gid, nOwn, nCl, repl)
-            DEME_ROW(voxelID), DEME_ROW(locX), DEME_ROW(locY), DEME_ROW(locZ), DEME_ROW(oriQw), DEME_ROW(oriQx), DEME_ROW(oriQy), DEME_ROW(oriQz);
-            DEME_ROW(vX), DEME_ROW(vY), DEME_ROW(vZ), DEME_ROW(omgBarX), DEME_ROW(omgBarY), DEME_ROW(omgBarZ);
-            DEME_ROW(aX), DEME_ROW(aY), DEME_ROW(aZ), DEME_ROW(alphaX), DEME_ROW(alphaY), DEME_ROW(alphaZ), DEME_ROW(familyID);
-#undef DEME_ROW
+#define DEME_COL(abi, T, Rec, f) rows_out(glob->abi, (const T*)b.st.abi, gid, nOwn, nCl, repl);
+            DEME_OWNER_COLS(DEME_COL, DEME_COL, DEME_COL)
+#undef DEME_COL
         } else {
-            DemeOwnerState up{};
-#define DEME_ROW(F)                                                   \
-    if (glob->F) {                                                    \
-        rows_in(b.st.F, (decltype(b.st.F))glob->F, gid), up.F = b.st.F; \
-    }
-            DEME_ROW(voxelID) DEME_ROW(locX) DEME_ROW(locY) DEME_ROW(locZ) DEME_ROW(oriQw) DEME_ROW(oriQx) DEME_ROW(oriQy) DEME_ROW(oriQz)
-            DEME_ROW(vX) DEME_ROW(vY) DEME_ROW(vZ) DEME_ROW(omgBarX) DEME_ROW(omgBarY) DEME_ROW(omgBarZ) DEME_ROW(familyID)
-#undef DEME_ROW
+            DemeOwnerState up{};  // (a / alpha are not written by global id)
+#define DEME_COL(abi, T, Rec, f) \
+    if (glob->abi)               \
+        rows_in(b.st.abi, (const T*)glob->abi, gid), up.abi = b.st.abi;
+            DEME_OWNER_COLS(DEME_COL, DEME_COL_NONE, DEME_COL)
+#undef DEME_COL
             if (int rc = deme_upload_owner_state(c, &up))
                 return gfail(g, rc, "state by global id (slab %zu): %s", k, c->err.c_str());
         }
@@ -1368,65 +1354,16 @@ int deme_multi_download_contact_records(deme_multi* m, float* force, float* torq
 }
 
 // ---- the contacts and the state of a few owners of a decomposed run, selected on every slab's device (deme_query.h) -----------------
-// Every slab selects from its own list with the rule of multi_contact_rows (k_query_select_slab: global ids from the books the
-// migration keeps on the device) and hands over a count and its hit rows; the host sorts the hits of all slabs by the merged key
-// (a pair is reported once, so keys are unique).  The cached merged rows are neither used nor invalidated.
+// Every slab selects from its own list with the rule of multi_contact_rows (k_query_select<true> through the query_mark / _select /
+// _fetch of deme_hip.hip: global ids from the books the migration keeps on the device) and hands over a count and its hit rows;
+// the host sorts the hits of all slabs by the merged key (a pair is reported once, so keys are unique).  The cached merged rows
+// are neither used nor invalidated.
 namespace {
-// the distinct ids of a question, marked in the slab context's byte array over GLOBAL owner ids
-int slab_query_mark(deme_ctx* c, const std::vector<uint32_t>& ids, uint32_t nOwnersGlobal) {
-    if (ensure(c, c->qMark, std::max<size_t>(nOwnersGlobal, 1)) || ensure(c, c->qCtr, 256) || ensure(c, c->stage, std::max<size_t>(ids.size(), 1) * 4))
-        return c->lastStatus;
-    HIPCK(hipMemsetAsync(c->qMark.p, 0, std::max<size_t>(nOwnersGlobal, 1), c->stream));
-    if (!ids.empty()) {
-        HIPCK(hipMemcpyAsync(c->stage.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_query_mark, dim3(grid_for(ids.size())), dim3(256), 0, c->stream, (uint32_t)ids.size(), c->stage.as<uint32_t>(),
-                           c->qMark.as<uint8_t>());
-    }
-    return DEME_OK;
-}
-// one slab's selection: the hit count in nHit, the hits (and records) left in the context's scratch; passes: count read-backs made
-int slab_query_select(deme_ctx* c, const HaloSlab& s, uint32_t nOwnersGlobal, int withRecords, uint32_t& nHit, uint32_t& passes) {
-    nHit = 0, passes = 0;
-    const size_t n = c->haveList ? (size_t)c->nContacts : 0;
-    if (!n)
-        return DEME_OK;
-    QueryTables t{};
-    t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
-    t.s2e = c->dp.s2e, t.o2e = c->dp.o2e;
-    t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
+inline SlabBooksDev slab_books(const HaloSlab& s, uint32_t nOwnersGlobal) {
     SlabBooksDev bk{};
     bk.sphereGid = (const uint32_t*)s.geo.sphereGid, bk.ownerGid = (const uint32_t*)s.geo.ownerGid;
     bk.nOwn = s.geo.nOwn, bk.nOwnersGlobal = nOwnersGlobal;
-    size_t want = 256;  // rows of scratch a first query starts with
-    for (int pass = 0;; pass++) {
-        if (ensure(c, c->qHits, want * sizeof(QueryHit)) || (withRecords && ensure(c, c->qRecs, want * 48)))
-            return c->lastStatus;
-        size_t rows = c->qHits.bytes / sizeof(QueryHit);  // the kernel's bound is what the allocations hold
-        if (withRecords)
-            rows = std::min(rows, c->qRecs.bytes / 48);
-        rows = std::min<size_t>(rows, 0xFFFFFFFFu);
-        HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
-        hipLaunchKernelGGL(k_query_select_slab, dim3(grid_for(n)), dim3(256), 0, c->stream, (uint32_t)n,
-                           c->keysSorted[c->keysCur].as<uint64_t>(), t, bk, c->qMark.as<uint8_t>(),
-                           withRecords ? c->rec[0].as<float>() : nullptr, withRecords ? c->rec[1].as<float>() : nullptr,
-                           withRecords ? c->rec[2].as<float>() : nullptr, withRecords ? c->rec[3].as<float>() : nullptr,
-                           c->qHits.as<QueryHit>(), withRecords ? c->qRecs.as<float>() : nullptr, (uint32_t)rows, c->qCtr.as<uint32_t>());
-        HIPCK(hipMemcpyAsync(&nHit, c->qCtr.p, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipStreamSynchronize(c->stream));
-        passes++;
-        if (nHit <= rows)
-            return DEME_OK;
-        if (pass)  // (the list cannot change between two selections)
-            return fail(c, DEME_ERR_OVERFLOW, "deme_multi_query_owner_contacts: %u hits after the scratch was sized for them", nHit);
-        want = nHit;
-    }
-}
-int slab_query_fetch(deme_ctx* c, uint32_t nHit, int withRecords, QueryHit* h, float* r) {
-    HIPCK(hipMemcpyAsync(h, c->qHits.p, (size_t)nHit * sizeof(QueryHit), hipMemcpyDeviceToHost, c->stream));
-    if (withRecords)
-        HIPCK(hipMemcpyAsync(r, c->qRecs.p, (size_t)nHit * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return DEME_OK;
+    return bk;
 }
 // one slab's owners of a question: their records gathered into the context's scratch (at most ids.size() of them), the count in nHit
 int slab_query_state(deme_ctx* c, const HaloSlab& s, uint32_t nOwnersGlobal, bool takeReplicated, size_t nIds, uint32_t& nHit) {
@@ -1435,9 +1372,7 @@ int slab_query_state(deme_ctx* c, const HaloSlab& s, uint32_t nOwnersGlobal, boo
         return DEME_OK;
     if (ensure(c, c->qState, nIds * sizeof(OwnerRec)))
         return c->lastStatus;
-    SlabBooksDev bk{};
-    bk.sphereGid = (const uint32_t*)s.geo.sphereGid, bk.ownerGid = (const uint32_t*)s.geo.ownerGid;
-    bk.nOwn = s.geo.nOwn, bk.nOwnersGlobal = nOwnersGlobal;
+    const SlabBooksDev bk = slab_books(s, nOwnersGlobal);
     HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
     hipLaunchKernelGGL(k_query_owner_state, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->nOwners, c->owners.as<OwnerRec>(),
                        (const uint32_t*)nullptr, c->dp.o2e, bk, c->nOwnerClumps, takeReplicated ? 1u : 0u, c->qMark.as<uint8_t>(),
@@ -1459,12 +1394,10 @@ int deme_multi_query_owner_contacts(deme_multi* m, const uint32_t* ownerIds, siz
                                     float* cpA, float* cpB, size_t cap, size_t* nOut) {
     if (!m || !m->plan)
         return DEME_ERR_INVALID;
-    if (!nOut || (nOwners && !ownerIds))
-        return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_contacts: null %s", nOut ? "owner id array" : "nOut");
     const uint32_t nOG = m->plan->nOwnersGlobal;
-    for (size_t i = 0; i < nOwners; i++)
-        if (ownerIds[i] >= nOG)
-            return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_contacts: owner id %u is out of range (%u owners)", ownerIds[i], nOG);
+    char msg[320];
+    if (int rc = owner_ids_refused(msg, "deme_multi_query_owner_contacts", nOut, "nOut", ownerIds, nOwners, nOG))
+        return mfail(m, rc, "%s", msg);
     if (int rc = deme_multi_sync(m))
         return rc;
     if (withRecords)  // what deme_multi_download_contact_records would say, slab by slab
@@ -1501,9 +1434,10 @@ int deme_multi_query_owner_contacts(deme_multi* m, const uint32_t* ownerIds, siz
                     return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_contacts: a slab has no books (deme_halo_group_set_slab / _build)");
                 uint32_t nHit = 0, passes = 0;
                 if (c->haveList && c->nContacts) {
-                    if (int rc = slab_query_mark(c, ids, nOG))
+                    const SlabBooksDev bk = slab_books(s, nOG);
+                    if (int rc = query_mark(c, ids, std::max<size_t>(nOG, 1)))
                         return mfail(m, rc, "%s", c->err.c_str());
-                    if (int rc = slab_query_select(c, s, nOG, withRecords, nHit, passes))
+                    if (int rc = query_select(c, &bk, "deme_multi_query_owner_contacts", withRecords, nHit, passes))
                         return mfail(m, rc, "%s", c->err.c_str());
                 }
                 m->qHostBytes += 4ull * passes;  // (a slab with an empty list is not asked)
@@ -1525,41 +1459,14 @@ int deme_multi_query_owner_contacts(deme_multi* m, const uint32_t* ownerIds, siz
             continue;
         if (hipSetDevice(p.g->device) != hipSuccess)
             return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", p.g->device);
-        if (int rc = slab_query_fetch(p.c, p.nHit, withRecords, h.data() + at, withRecords ? r.data() + 12 * at : nullptr))
+        if (int rc = query_fetch(p.c, p.nHit, withRecords, h.data() + at, withRecords ? r.data() + 12 * at : nullptr))
             return mfail(m, rc, "%s", p.c->err.c_str());
         for (uint32_t i = 0; i < p.nHit; i++)
             ctxOf[at + i] = p.c;
         at += p.nHit;
     }
     m->qHostBytes += (uint64_t)total * (sizeof(QueryHit) + (withRecords ? 48 : 0));
-    std::vector<uint32_t> perm(total);
-    for (size_t i = 0; i < total; i++)
-        perm[i] = (uint32_t)i;
-    std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h[a].key < h[b].key; });
-    float* dst[4] = {force, torqueOnly, cpA, cpB};
-    for (size_t i = 0; i < total; i++) {
-        const QueryHit& q = h[perm[i]];
-        const uint32_t cls = key_class(q.key), gB = merged_key_b(q.key);
-        if (idA)
-            idA[i] = merged_key_a(q.key);
-        if (idB)
-            idB[i] = gB;
-        if (type)
-            type[i] = cls == DEME_KEY_CLASS_SS   ? DEME_SPHERE_SPHERE_CONTACT
-                      : cls == DEME_KEY_CLASS_SM ? DEME_SPHERE_MESH_CONTACT
-                      : ctxOf[perm[i]]->hObjType[gB] == DEME_ANAL_OBJ_TYPE_PLANE ? DEME_SPHERE_PLANE_CONTACT
-                                                                                 : DEME_SPHERE_CYL_CONTACT;
-        if (ownerA)
-            ownerA[i] = q.ownerA;
-        if (ownerB)
-            ownerB[i] = q.ownerB;
-        if (side)
-            side[i] = (uint8_t)(q.side & 1u);
-        if (withRecords)
-            for (int k = 0; k < 4; k++)
-                if (dst[k])
-                    memcpy(dst[k] + 3 * i, r.data() + 12 * (size_t)perm[i] + 3 * k, 12);
-    }
+    query_emit(h, r, true, [&](uint32_t hit) { return ctxOf[hit]; }, QueryRows{idA, idB, type, ownerA, ownerB, side, {force, torqueOnly, cpA, cpB}});
     return DEME_OK;
 }
 
@@ -1573,14 +1480,11 @@ int deme_multi_query_host_bytes(const deme_multi* m, uint64_t* bytes) {
 int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_t n, DemeOwnerState* out) {
     if (!m || !m->plan)
         return DEME_ERR_INVALID;
-    if (!out || (n && !globalIds))
-        return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: null %s", out ? "owner id array" : "state");
-    if (owner_state_wants_acc(out))
-        return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: a / alpha need the reduction a full download launches (deme_multi_download_state)");
     const uint32_t nOG = m->plan->nOwnersGlobal;
-    for (size_t i = 0; i < n; i++)
-        if (globalIds[i] >= nOG)
-            return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: owner id %u is out of range (%u owners)", globalIds[i], nOG);
+    char msg[320];
+    if (int rc = owner_ids_refused(msg, "deme_multi_query_owner_state", out, "state", globalIds, n, nOG, out,
+                                   "need the reduction a full download launches (deme_multi_download_state)"))
+        return mfail(m, rc, "%s", msg);
     if (!n)
         return DEME_OK;
     if (int rc = deme_multi_sync(m))
@@ -1605,7 +1509,7 @@ int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_
             if (!s.geo.set)
                 return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: a slab has no books (deme_halo_group_set_slab / _build)");
             uint32_t nHit = 0;
-            if (int rc = slab_query_mark(c, ids, nOG))
+            if (int rc = query_mark(c, ids, std::max<size_t>(nOG, 1)))
                 return mfail(m, rc, "%s", c->err.c_str());
             if (int rc = slab_query_state(c, s, nOG, g->firstSlab + k == 0, ids.size(), nHit))
                 return mfail(m, rc, "%s", c->err.c_str());
@@ -1639,20 +1543,11 @@ int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_
 int deme_multi_scatter_owner_state(deme_multi* m, const uint32_t* globalIds, size_t n, const DemeOwnerState* in) {
     if (!m || !m->plan)
         return DEME_ERR_INVALID;
-    if (!in || (n && !globalIds))
-        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: null %s", in ? "owner id array" : "state");
-    if (owner_state_wants_acc(in))
-        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: a / alpha columns are not written by owner id (deme_upload_owner_state hands the accumulators to the caller)");
-    if (n > 0xFFFFFFFFull)
-        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: %zu ids", n);
-    const uint32_t nOG = m->plan->nOwnersGlobal;
-    for (size_t i = 0; i < n; i++)
-        if (globalIds[i] >= nOG)
-            return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: owner id %u is out of range (%u owners)", globalIds[i], nOG);
+    char msg[320];
     std::vector<std::pair<uint32_t, uint32_t>> sorted;
-    uint32_t twice = 0;
-    if (!owner_ids_distinct(globalIds, n, sorted, &twice))
-        return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: owner id %u is given twice (the order of two writes is not defined)", twice);
+    if (int rc = owner_ids_refused(msg, "deme_multi_scatter_owner_state", in, "state", globalIds, n, m->plan->nOwnersGlobal, in,
+                                   "columns are not written by owner id (deme_upload_owner_state hands the accumulators to the caller)", true, &sorted))
+        return mfail(m, rc, "%s", msg);
     const uint32_t mask = owner_state_mask(in);
     if (!n || !mask)
         return DEME_OK;

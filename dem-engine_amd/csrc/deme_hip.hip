@@ -2054,6 +2054,12 @@ int deme_upload_scene(deme_ctx* c, const DemeScene* s) {
     return DEME_OK;
 }
 
+// which kinds of column a call names (deme_owner_cols.h)
+#define DEME_COL(abi, T, Rec, f) || st->abi
+static inline bool owner_state_wants_pose(const DemeOwnerState* st) { return false DEME_OWNER_COLS(DEME_COL, DEME_COL_NONE, DEME_COL); }
+static inline bool owner_state_wants_acc(const DemeOwnerState* st) { return false DEME_OWNER_COLS(DEME_COL_NONE, DEME_COL, DEME_COL_NONE); }
+#undef DEME_COL
+
 static int owner_state_io(deme_ctx* c, const DemeOwnerState* st, int dir) {
     if (int rc = check_ready(c))
         return rc;
@@ -2067,17 +2073,9 @@ static int owner_state_io(deme_ctx* c, const DemeOwnerState* st, int dir) {
         void** dev;
     };
     OwnerSoA soa{};
-    Col cols[] = {{st->voxelID, 8, (void**)&soa.voxelID},   {st->locX, 2, (void**)&soa.locX},
-                  {st->locY, 2, (void**)&soa.locY},         {st->locZ, 2, (void**)&soa.locZ},
-                  {st->oriQw, 4, (void**)&soa.oriQw},       {st->oriQx, 4, (void**)&soa.oriQx},
-                  {st->oriQy, 4, (void**)&soa.oriQy},       {st->oriQz, 4, (void**)&soa.oriQz},
-                  {st->vX, 4, (void**)&soa.vX},             {st->vY, 4, (void**)&soa.vY},
-                  {st->vZ, 4, (void**)&soa.vZ},             {st->omgBarX, 4, (void**)&soa.omgBarX},
-                  {st->omgBarY, 4, (void**)&soa.omgBarY},   {st->omgBarZ, 4, (void**)&soa.omgBarZ},
-                  {st->aX, 4, (void**)&soa.aX},             {st->aY, 4, (void**)&soa.aY},
-                  {st->aZ, 4, (void**)&soa.aZ},             {st->alphaX, 4, (void**)&soa.alphaX},
-                  {st->alphaY, 4, (void**)&soa.alphaY},     {st->alphaZ, 4, (void**)&soa.alphaZ},
-                  {st->familyID, 1, (void**)&soa.familyID}};
+#define DEME_COL(abi, T, Rec, f) {st->abi, sizeof(T), (void**)&soa.abi},
+    Col cols[] = {DEME_OWNER_COLS(DEME_COL, DEME_COL, DEME_COL)};
+#undef DEME_COL
     size_t total = 0;
     for (auto& cl : cols)
         if (cl.host)
@@ -2096,10 +2094,10 @@ static int owner_state_io(deme_ctx* c, const DemeOwnerState* st, int dir) {
     // downloads see a/alpha of EVERY owner (fixed and heavy ones are only reduced on demand)
     if (dir == 1 && c->conValid && c->haveList)
         launch_full_reduction(c);
-    else if (dir == 1 && c->fusedPrevValid && c->haveList && (st->aX || st->aY || st->aZ || st->alphaX || st->alphaY || st->alphaZ))
+    else if (dir == 1 && c->fusedPrevValid && c->haveList && owner_state_wants_acc(st))
         if (int rc = launch_fused_step(c, true))  // the last step was a fused one: replay its force evaluation on the buffers of its start
             return rc;
-    if (dir == 0 && (st->aX || st->aY || st->aZ || st->alphaX || st->alphaY || st->alphaZ))
+    if (dir == 0 && owner_state_wants_acc(st))
         c->conValid = false;  // the caller now owns a/alpha
     AccRec* accView = c->acc.as<AccRec>();
     if (n)
@@ -2124,8 +2122,7 @@ static void owner_state_written(deme_ctx* c, const DemeOwnerState* st) {
     if (st->familyID)
         c->prescDirty = true;  // owners may have changed family
     c->fusedPrevValid = false;
-    if (st->voxelID || st->locX || st->locY || st->locZ || st->oriQw || st->oriQx || st->oriQy || st->oriQz || st->vX || st->vY || st->vZ ||
-        st->omgBarX || st->omgBarY || st->omgBarZ || st->familyID)
+    if (owner_state_wants_pose(st))
         c->listStale = true;  // pose, velocity (it sizes the margins) or family (masks) changed under the K-step list
 }
 
@@ -4500,16 +4497,147 @@ int deme_download_sphere_components(deme_ctx* c, uint16_t* comp, size_t cap) {
 // The selection runs on the engine's list as it stands; what comes to the host is the hit count and the hit rows, which are then
 // put in the caller's canonical order by their caller-id keys (keys of a list are unique) -- the sub-sequence of what
 // deme_download_contacts returns, without the caller's view of the whole list (order_current_view) ever being built.
+// A decomposed run asks every slab the same way (deme_decomp.inc), with the slab's books: the marks are then over GLOBAL owner ids
+// and the kernel applies the merged list's rules.
+namespace {
+// (id, row of the call) sorted by id; false when an id comes twice (*twice receives it)
+inline bool owner_ids_distinct(const uint32_t* ids, size_t n, std::vector<std::pair<uint32_t, uint32_t>>& sorted, uint32_t* twice) {
+    sorted.resize(n);
+    for (size_t i = 0; i < n; i++)
+        sorted[i] = {ids[i], (uint32_t)i};
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < n; i++)
+        if (sorted[i].first == sorted[i - 1].first) {
+            *twice = sorted[i].first;
+            return false;
+        }
+    return true;
+}
+// The refusals the by-owner entry points share, in the order they make them; DEME_OK, or the code with the text in msg for the
+// caller's fail / mfail.  `who`: the entry point; `other` (named otherName): its second pointer; st with accWhy: a state whose a /
+// alpha columns are refused; count32: ids are counted in 32 bits; sorted: filled by owner_ids_distinct, an id given twice refused.
+int owner_ids_refused(char (&msg)[320], const char* who, const void* other, const char* otherName, const uint32_t* ids, size_t n, uint32_t nOwners,
+                      const DemeOwnerState* st = nullptr, const char* accWhy = nullptr, bool count32 = false,
+                      std::vector<std::pair<uint32_t, uint32_t>>* sorted = nullptr) {
+    uint32_t twice = 0;
+    if (!other || (n && !ids))
+        snprintf(msg, sizeof msg, "%s: null %s", who, other ? "owner id array" : otherName);
+    else if (st && owner_state_wants_acc(st))
+        snprintf(msg, sizeof msg, "%s: a / alpha %s", who, accWhy);
+    else if (count32 && n > 0xFFFFFFFFull)
+        snprintf(msg, sizeof msg, "%s: %zu ids", who, n);
+    else if (const uint32_t* bad = std::find_if(ids, ids + n, [&](uint32_t id) { return id >= nOwners; }); bad != ids + n)
+        snprintf(msg, sizeof msg, "%s: owner id %u is out of range (%u owners)", who, *bad, nOwners);
+    else if (sorted && !owner_ids_distinct(ids, n, *sorted, &twice))
+        snprintf(msg, sizeof msg, "%s: owner id %u is given twice (the order of two writes is not defined)", who, twice);
+    else
+        return DEME_OK;
+    return DEME_ERR_INVALID;
+}
+// the distinct ids of a question, marked in the context's byte array of nMarks entries
+int query_mark(deme_ctx* c, const std::vector<uint32_t>& ids, size_t nMarks) {
+    if (ensure(c, c->qMark, nMarks) || ensure(c, c->qCtr, 256) || ensure(c, c->stage, std::max<size_t>(ids.size(), 1) * 4))
+        return c->lastStatus;
+    HIPCK(hipMemsetAsync(c->qMark.p, 0, nMarks, c->stream));
+    if (!ids.empty()) {
+        HIPCK(hipMemcpyAsync(c->stage.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_query_mark, dim3(grid_for(ids.size())), dim3(256), 0, c->stream, (uint32_t)ids.size(), c->stage.as<uint32_t>(),
+                           c->qMark.as<uint8_t>());
+    }
+    return DEME_OK;
+}
+// one context's selection: the hit count in nHit, the hits (and records) left in the context's scratch; passes: count read-backs
+// made.  bk: the books of a slab, null for a single context; who: the entry point, for the message.
+int query_select(deme_ctx* c, const SlabBooksDev* bk, const char* who, int withRecords, uint32_t& nHit, uint32_t& passes) {
+    nHit = 0, passes = 0;
+    const size_t n = c->haveList ? (size_t)c->nContacts : 0;
+    if (!n)
+        return DEME_OK;
+    QueryTables t{};
+    t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
+    t.s2e = c->dp.s2e, t.o2e = c->dp.o2e;
+    t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
+    size_t want = 256;  // rows of scratch a first query starts with
+    for (int pass = 0;; pass++) {
+        if (ensure(c, c->qHits, want * sizeof(QueryHit)) || (withRecords && ensure(c, c->qRecs, want * 48)))
+            return c->lastStatus;
+        size_t rows = c->qHits.bytes / sizeof(QueryHit);  // the kernel's bound is what the allocations hold, whatever was asked for
+        if (withRecords)
+            rows = std::min(rows, c->qRecs.bytes / 48);
+        rows = std::min<size_t>(rows, 0xFFFFFFFFu);
+        HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
+        hipLaunchKernelGGL(bk ? k_query_select<true> : k_query_select<false>, dim3(grid_for(n)), dim3(256), 0, c->stream, (uint32_t)n,
+                           c->keysSorted[c->keysCur].as<uint64_t>(), t, bk ? *bk : SlabBooksDev{}, c->qMark.as<uint8_t>(),
+                           withRecords ? c->rec[0].as<float>() : nullptr, withRecords ? c->rec[1].as<float>() : nullptr,
+                           withRecords ? c->rec[2].as<float>() : nullptr, withRecords ? c->rec[3].as<float>() : nullptr,
+                           c->qHits.as<QueryHit>(), withRecords ? c->qRecs.as<float>() : nullptr, (uint32_t)rows, c->qCtr.as<uint32_t>());
+        HIPCK(hipMemcpyAsync(&nHit, c->qCtr.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipStreamSynchronize(c->stream));
+        passes++;
+        if (nHit <= rows)
+            return DEME_OK;
+        if (pass)  // (the list cannot change between two selections)
+            return fail(c, DEME_ERR_OVERFLOW, "%s: %u hits after the scratch was sized for them", who, nHit);
+        want = nHit;
+    }
+}
+int query_fetch(deme_ctx* c, uint32_t nHit, int withRecords, QueryHit* h, float* r) {
+    HIPCK(hipMemcpyAsync(h, c->qHits.p, (size_t)nHit * sizeof(QueryHit), hipMemcpyDeviceToHost, c->stream));
+    if (withRecords)
+        HIPCK(hipMemcpyAsync(r, c->qRecs.p, (size_t)nHit * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+// what an owner-contact query hands back, row by row; a null column is not asked
+struct QueryRows {
+    uint32_t *idA, *idB;
+    uint8_t* type;
+    uint32_t *ownerA, *ownerB;
+    uint8_t* side;
+    float* rec[4];  // force, torque-only force, cpA, cpB
+};
+// The fetched hits in the order of their keys (keys of a list are unique).  merged: the keys are merged_key's, not the caller's
+// contact keys; ctxOf(hit): the context whose hObjType answers for an analytical row.
+template <class CtxOf>
+void query_emit(const std::vector<QueryHit>& h, const std::vector<float>& r, bool merged, CtxOf ctxOf, const QueryRows& out) {
+    std::vector<uint32_t> perm(h.size());
+    for (size_t i = 0; i < perm.size(); i++)
+        perm[i] = (uint32_t)i;
+    std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h[a].key < h[b].key; });
+    for (size_t i = 0; i < perm.size(); i++) {
+        const QueryHit& q = h[perm[i]];
+        const uint32_t cls = key_class(q.key), a = merged ? merged_key_a(q.key) : key_a(q.key), b = merged ? merged_key_b(q.key) : key_b(q.key);
+        if (out.idA)
+            out.idA[i] = a;
+        if (out.idB)
+            out.idB[i] = b;
+        if (out.type)
+            out.type[i] = cls == DEME_KEY_CLASS_SS   ? DEME_SPHERE_SPHERE_CONTACT
+                          : cls == DEME_KEY_CLASS_SM ? DEME_SPHERE_MESH_CONTACT
+                          : ctxOf(perm[i])->hObjType[b] == DEME_ANAL_OBJ_TYPE_PLANE ? DEME_SPHERE_PLANE_CONTACT
+                                                                                    : DEME_SPHERE_CYL_CONTACT;
+        if (out.ownerA)
+            out.ownerA[i] = q.ownerA;
+        if (out.ownerB)
+            out.ownerB[i] = q.ownerB;
+        if (out.side)
+            out.side[i] = (uint8_t)(q.side & 1u);  // (bit 1, DEME_QUERY_FLIPPED, is a slab's own business)
+        if (!r.empty())
+            for (int k = 0; k < 4; k++)
+                if (out.rec[k])
+                    memcpy(out.rec[k] + 3 * i, r.data() + 12 * (size_t)perm[i] + 3 * k, 12);
+    }
+}
+}  // namespace
+
 int deme_query_owner_contacts(deme_ctx* c, const uint32_t* ownerIds, size_t nOwners, int withRecords, uint32_t* idA, uint32_t* idB,
                               uint8_t* type, uint32_t* ownerA, uint32_t* ownerB, uint8_t* side, float* force, float* torqueOnly,
                               float* cpA, float* cpB, size_t cap, size_t* nOut) {
     if (int rc = check_ready(c))
         return rc;
-    if (!nOut || (nOwners && !ownerIds))
-        return fail(c, DEME_ERR_INVALID, "deme_query_owner_contacts: null %s", nOut ? "owner id array" : "nOut");
-    for (size_t i = 0; i < nOwners; i++)
-        if (ownerIds[i] >= c->nOwners)
-            return fail(c, DEME_ERR_INVALID, "deme_query_owner_contacts: owner id %u is out of range (%u owners)", ownerIds[i], c->nOwners);
+    char msg[320];
+    if (int rc = owner_ids_refused(msg, "deme_query_owner_contacts", nOut, "nOut", ownerIds, nOwners, c->nOwners))
+        return fail(c, rc, "%s", msg);
     if (withRecords && !c->record)
         return fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
     if (withRecords && c->seeded)
@@ -4517,44 +4645,14 @@ int deme_query_owner_contacts(deme_ctx* c, const uint32_t* ownerIds, size_t nOwn
     std::vector<uint32_t> ids(ownerIds, ownerIds + nOwners);
     std::sort(ids.begin(), ids.end());
     ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    const size_t n = c->haveList ? (size_t)c->nContacts : 0, nIds = ids.size();
-    uint32_t nHit = 0;
-    if (n && nIds) {
-        if (ensure(c, c->qMark, (size_t)c->nOwners) || ensure(c, c->qCtr, 256) || ensure(c, c->stage, nIds * 4))
-            return c->lastStatus;
-        HIPCK(hipMemsetAsync(c->qMark.p, 0, (size_t)c->nOwners, c->stream));
-        HIPCK(hipMemcpyAsync(c->stage.p, ids.data(), nIds * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_query_mark, dim3(grid_for(nIds)), dim3(256), 0, c->stream, (uint32_t)nIds, c->stage.as<uint32_t>(),
-                           c->qMark.as<uint8_t>());
-        QueryTables t{};
-        t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
-        t.s2e = c->dp.s2e, t.o2e = c->dp.o2e;
-        t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
-        size_t want = 256;  // rows of scratch a first query starts with
-        for (int pass = 0;; pass++) {
-            if (ensure(c, c->qHits, want * sizeof(QueryHit)) || (withRecords && ensure(c, c->qRecs, want * 48)))
-                return c->lastStatus;
-            // the kernel's bound is what the allocations hold, whatever was asked for
-            size_t rows = c->qHits.bytes / sizeof(QueryHit);
-            if (withRecords)
-                rows = std::min(rows, c->qRecs.bytes / 48);
-            rows = std::min<size_t>(rows, 0xFFFFFFFFu);
-            HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
-            hipLaunchKernelGGL(k_query_select, dim3(grid_for(n)), dim3(256), 0, c->stream, (uint32_t)n,
-                               c->keysSorted[c->keysCur].as<uint64_t>(), t, c->qMark.as<uint8_t>(),
-                               withRecords ? c->rec[0].as<float>() : nullptr, withRecords ? c->rec[1].as<float>() : nullptr,
-                               withRecords ? c->rec[2].as<float>() : nullptr, withRecords ? c->rec[3].as<float>() : nullptr,
-                               c->qHits.as<QueryHit>(), withRecords ? c->qRecs.as<float>() : nullptr, (uint32_t)rows,
-                               c->qCtr.as<uint32_t>());
-            HIPCK(hipMemcpyAsync(&nHit, c->qCtr.p, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCK(hipStreamSynchronize(c->stream));
-            c->qHostBytes += 4;
-            if (nHit <= rows)
-                break;
-            if (pass)  // (the list cannot change between two selections)
-                return fail(c, DEME_ERR_OVERFLOW, "deme_query_owner_contacts: %u hits after the scratch was sized for them", nHit);
-            want = nHit;
-        }
+    uint32_t nHit = 0, passes = 0;
+    if (c->haveList && c->nContacts && !ids.empty()) {  // (a context with an empty list, or an empty question, is not asked)
+        if (int rc = query_mark(c, ids, c->nOwners))
+            return rc;
+        const int rc = query_select(c, nullptr, "deme_query_owner_contacts", withRecords, nHit, passes);
+        c->qHostBytes += 4ull * passes;
+        if (rc)
+            return rc;
     }
     *nOut = nHit;
     if (cap < nHit)
@@ -4563,39 +4661,10 @@ int deme_query_owner_contacts(deme_ctx* c, const uint32_t* ownerIds, size_t nOwn
         return DEME_OK;
     std::vector<QueryHit> h(nHit);
     std::vector<float> r(withRecords ? (size_t)nHit * 12 : 0);
-    HIPCK(hipMemcpyAsync(h.data(), c->qHits.p, (size_t)nHit * sizeof(QueryHit), hipMemcpyDeviceToHost, c->stream));
-    if (withRecords)
-        HIPCK(hipMemcpyAsync(r.data(), c->qRecs.p, (size_t)nHit * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
+    if (int rc = query_fetch(c, nHit, withRecords, h.data(), r.data()))
+        return rc;
     c->qHostBytes += (uint64_t)nHit * (sizeof(QueryHit) + (withRecords ? 48 : 0));
-    std::vector<uint32_t> perm(nHit);
-    for (uint32_t i = 0; i < nHit; i++)
-        perm[i] = i;
-    std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h[a].key < h[b].key; });
-    float* dst[4] = {force, torqueOnly, cpA, cpB};
-    for (uint32_t i = 0; i < nHit; i++) {
-        const QueryHit& q = h[perm[i]];
-        const uint32_t cls = key_class(q.key);
-        if (idA)
-            idA[i] = key_a(q.key);
-        if (idB)
-            idB[i] = key_b(q.key);
-        if (type)
-            type[i] = cls == DEME_KEY_CLASS_SS   ? DEME_SPHERE_SPHERE_CONTACT
-                      : cls == DEME_KEY_CLASS_SM ? DEME_SPHERE_MESH_CONTACT
-                      : c->hObjType[key_b(q.key)] == DEME_ANAL_OBJ_TYPE_PLANE ? DEME_SPHERE_PLANE_CONTACT
-                                                                              : DEME_SPHERE_CYL_CONTACT;
-        if (ownerA)
-            ownerA[i] = q.ownerA;
-        if (ownerB)
-            ownerB[i] = q.ownerB;
-        if (side)
-            side[i] = (uint8_t)q.side;
-        if (withRecords)
-            for (int k = 0; k < 4; k++)
-                if (dst[k])
-                    memcpy(dst[k] + 3 * (size_t)i, r.data() + 12 * (size_t)perm[i] + 3 * k, 12);
-    }
+    query_emit(h, r, false, [&](uint32_t) { return c; }, QueryRows{idA, idB, type, ownerA, ownerB, side, {force, torqueOnly, cpA, cpB}});
     return DEME_OK;
 }
 
@@ -4610,39 +4679,20 @@ int deme_query_host_bytes(const deme_ctx* c, uint64_t* bytes) {
 namespace {
 // the columns of DemeOwnerState a gathered record fills: row `at` of every non-null column from record r
 inline void owner_state_row(const DemeOwnerState* out, size_t at, const OwnerRec& r) {
-    if (out->voxelID) out->voxelID[at] = r.voxelID;
-    if (out->locX) out->locX[at] = r.locX;
-    if (out->locY) out->locY[at] = r.locY;
-    if (out->locZ) out->locZ[at] = r.locZ;
-    if (out->oriQw) out->oriQw[at] = r.qw;
-    if (out->oriQx) out->oriQx[at] = r.qx;
-    if (out->oriQy) out->oriQy[at] = r.qy;
-    if (out->oriQz) out->oriQz[at] = r.qz;
-    if (out->vX) out->vX[at] = r.vx;
-    if (out->vY) out->vY[at] = r.vy;
-    if (out->vZ) out->vZ[at] = r.vz;
-    if (out->omgBarX) out->omgBarX[at] = r.wx;
-    if (out->omgBarY) out->omgBarY[at] = r.wy;
-    if (out->omgBarZ) out->omgBarZ[at] = r.wz;
+#define DEME_COL(abi, T, Rec, f) if (out->abi) out->abi[at] = r.f;
+    DEME_OWNER_COLS(DEME_COL, DEME_COL_NONE, DEME_COL_NONE)
+#undef DEME_COL
     if (out->familyID) out->familyID[at] = (uint8_t)r.family;
-}
-inline bool owner_state_wants_acc(const DemeOwnerState* st) {
-    return st->aX || st->aY || st->aZ || st->alphaX || st->alphaY || st->alphaZ;
 }
 }  // namespace
 
 int deme_query_owner_state(deme_ctx* c, const uint32_t* ownerIds, size_t n, DemeOwnerState* out) {
     if (int rc = check_ready(c))
         return rc;
-    if (!out || (n && !ownerIds))
-        return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: null %s", out ? "owner id array" : "state");
-    if (owner_state_wants_acc(out))
-        return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: a / alpha need the reduction a full download launches (deme_download_owner_state)");
-    if (n > 0xFFFFFFFFull)
-        return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: %zu ids", n);
-    for (size_t i = 0; i < n; i++)
-        if (ownerIds[i] >= c->nOwners)
-            return fail(c, DEME_ERR_INVALID, "deme_query_owner_state: owner id %u is out of range (%u owners)", ownerIds[i], c->nOwners);
+    char msg[320];
+    if (int rc = owner_ids_refused(msg, "deme_query_owner_state", out, "state", ownerIds, n, c->nOwners, out,
+                                   "need the reduction a full download launches (deme_download_owner_state)", true))
+        return fail(c, rc, "%s", msg);
     if (!n)
         return DEME_OK;
     std::vector<uint32_t> slots(n);
@@ -4667,43 +4717,16 @@ int deme_query_owner_state(deme_ctx* c, const uint32_t* ownerIds, size_t n, Deme
 namespace {
 // the columns a call gave as the kernel's mask, and row `at` of them as the record the kernel reads its values from
 inline uint32_t owner_state_mask(const DemeOwnerState* in) {
-    return (in->voxelID ? DEME_SCATTER_VOXEL : 0u) | (in->locX ? DEME_SCATTER_LOCX : 0u) | (in->locY ? DEME_SCATTER_LOCY : 0u) |
-           (in->locZ ? DEME_SCATTER_LOCZ : 0u) | (in->oriQw ? DEME_SCATTER_QW : 0u) | (in->oriQx ? DEME_SCATTER_QX : 0u) |
-           (in->oriQy ? DEME_SCATTER_QY : 0u) | (in->oriQz ? DEME_SCATTER_QZ : 0u) | (in->vX ? DEME_SCATTER_VX : 0u) |
-           (in->vY ? DEME_SCATTER_VY : 0u) | (in->vZ ? DEME_SCATTER_VZ : 0u) | (in->omgBarX ? DEME_SCATTER_WX : 0u) |
-           (in->omgBarY ? DEME_SCATTER_WY : 0u) | (in->omgBarZ ? DEME_SCATTER_WZ : 0u) | (in->familyID ? DEME_SCATTER_FAMILY : 0u);
+#define DEME_COL(abi, T, Rec, f) | (in->abi ? DEME_SCATTER_BIT(abi) : 0u)
+    return 0u DEME_OWNER_COLS(DEME_COL, DEME_COL_NONE, DEME_COL);
+#undef DEME_COL
 }
 inline OwnerRec owner_state_patch(const DemeOwnerState* in, size_t at) {
     OwnerRec r{};
-    if (in->voxelID) r.voxelID = in->voxelID[at];
-    if (in->locX) r.locX = in->locX[at];
-    if (in->locY) r.locY = in->locY[at];
-    if (in->locZ) r.locZ = in->locZ[at];
-    if (in->oriQw) r.qw = in->oriQw[at];
-    if (in->oriQx) r.qx = in->oriQx[at];
-    if (in->oriQy) r.qy = in->oriQy[at];
-    if (in->oriQz) r.qz = in->oriQz[at];
-    if (in->vX) r.vx = in->vX[at];
-    if (in->vY) r.vy = in->vY[at];
-    if (in->vZ) r.vz = in->vZ[at];
-    if (in->omgBarX) r.wx = in->omgBarX[at];
-    if (in->omgBarY) r.wy = in->omgBarY[at];
-    if (in->omgBarZ) r.wz = in->omgBarZ[at];
-    if (in->familyID) r.family = in->familyID[at];
+#define DEME_COL(abi, T, Rec, f) if (in->abi) r.f = in->abi[at];
+    DEME_OWNER_COLS(DEME_COL, DEME_COL_NONE, DEME_COL)  // (the family's byte alone: the kernel keeps the record's flag bits)
+#undef DEME_COL
     return r;
-}
-// (id, row of the call) sorted by id; false when an id comes twice (*twice receives it)
-inline bool owner_ids_distinct(const uint32_t* ids, size_t n, std::vector<std::pair<uint32_t, uint32_t>>& sorted, uint32_t* twice) {
-    sorted.resize(n);
-    for (size_t i = 0; i < n; i++)
-        sorted[i] = {ids[i], (uint32_t)i};
-    std::sort(sorted.begin(), sorted.end());
-    for (size_t i = 1; i < n; i++)
-        if (sorted[i].first == sorted[i - 1].first) {
-            *twice = sorted[i].first;
-            return false;
-        }
-    return true;
 }
 // keys (4 bytes each) and records (64 bytes each) to the device, the kernel, and the wait that lets the host arrays go
 // (the flags of a write of `in`'s columns are set once the scratch is there: a call that fails before it has changed nothing)
@@ -4728,19 +4751,11 @@ int launch_owner_scatter(deme_ctx* c, const DemeOwnerState* in, const std::vecto
 int deme_scatter_owner_state(deme_ctx* c, const uint32_t* ownerIds, size_t n, const DemeOwnerState* in) {
     if (int rc = check_ready(c))
         return rc;
-    if (!in || (n && !ownerIds))
-        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: null %s", in ? "owner id array" : "state");
-    if (owner_state_wants_acc(in))
-        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: a / alpha columns are not written by owner id (deme_upload_owner_state hands the accumulators to the caller)");
-    if (n > 0xFFFFFFFFull)
-        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: %zu ids", n);
-    for (size_t i = 0; i < n; i++)
-        if (ownerIds[i] >= c->nOwners)
-            return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: owner id %u is out of range (%u owners)", ownerIds[i], c->nOwners);
+    char msg[320];
     std::vector<std::pair<uint32_t, uint32_t>> sorted;
-    uint32_t twice = 0;
-    if (!owner_ids_distinct(ownerIds, n, sorted, &twice))
-        return fail(c, DEME_ERR_INVALID, "deme_scatter_owner_state: owner id %u is given twice (the order of two writes is not defined)", twice);
+    if (int rc = owner_ids_refused(msg, "deme_scatter_owner_state", in, "state", ownerIds, n, c->nOwners, in,
+                                   "columns are not written by owner id (deme_upload_owner_state hands the accumulators to the caller)", true, &sorted))
+        return fail(c, rc, "%s", msg);
     const uint32_t mask = owner_state_mask(in);
     if (!n || !mask)
         return DEME_OK;

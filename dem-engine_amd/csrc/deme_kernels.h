@@ -13,6 +13,7 @@
 //   k_history       new->previous index by binary search over the previous sorted keys
 #pragma once
 #include "deme_device.h"
+#include "deme_owner_cols.h"
 
 namespace deme_dev {
 
@@ -1524,12 +1525,10 @@ __device__ inline void integrate_owner(const DevParams& p, OwnerRec& r, float4 a
 }
 
 // ---- packing between the C-ABI's SoA view and the device records -------------------------------
-struct OwnerSoA {
-    uint64_t* voxelID;
-    uint16_t *locX, *locY, *locZ;
-    float *oriQw, *oriQx, *oriQy, *oriQz, *vX, *vY, *vZ, *omgBarX, *omgBarY, *omgBarZ;
-    float *aX, *aY, *aZ, *alphaX, *alphaY, *alphaZ;
-    uint8_t* familyID;
+struct OwnerSoA {  // device pointers to the columns of DemeOwnerState (deme_owner_cols.h), and one extra
+#define DEME_COL(abi, T, Rec, f) T* abi;
+    DEME_OWNER_COLS(DEME_COL, DEME_COL, DEME_COL)
+#undef DEME_COL
     uint16_t* inertiaPropOffsets;
 };
 
@@ -1542,52 +1541,22 @@ __global__ __launch_bounds__(256) void k_pack_owners(uint32_t n, OwnerRec* owner
     AccRec a = acc[o];
     const uint32_t e = o2e ? o2e[o] : o;  // the caller's number of this owner (engine-side spatial order, deme_order.inc)
     if (dir == 0) {
-        if (s.voxelID) r.voxelID = s.voxelID[e];
-        if (s.locX) r.locX = s.locX[e];
-        if (s.locY) r.locY = s.locY[e];
-        if (s.locZ) r.locZ = s.locZ[e];
-        if (s.oriQw) r.qw = s.oriQw[e];
-        if (s.oriQx) r.qx = s.oriQx[e];
-        if (s.oriQy) r.qy = s.oriQy[e];
-        if (s.oriQz) r.qz = s.oriQz[e];
-        if (s.vX) r.vx = s.vX[e];
-        if (s.vY) r.vy = s.vY[e];
-        if (s.vZ) r.vz = s.vZ[e];
-        if (s.omgBarX) r.wx = s.omgBarX[e];
-        if (s.omgBarY) r.wy = s.omgBarY[e];
-        if (s.omgBarZ) r.wz = s.omgBarZ[e];
+#define DEME_COL_R(abi, T, Rec, f) if (s.abi) r.f = s.abi[e];
+#define DEME_COL_A(abi, T, Rec, f) if (s.abi) a.f = s.abi[e];
+        DEME_OWNER_COLS(DEME_COL_R, DEME_COL_A, DEME_COL_NONE)
+#undef DEME_COL_R
+#undef DEME_COL_A
         if (s.familyID) r.family = (r.family & OWNER_FLAG_BITS) | s.familyID[e];
         if (s.inertiaPropOffsets) r.inertiaOff = s.inertiaPropOffsets[e];
-        if (s.aX) a.ax = s.aX[e];
-        if (s.aY) a.ay = s.aY[e];
-        if (s.aZ) a.az = s.aZ[e];
-        if (s.alphaX) a.lx = s.alphaX[e];
-        if (s.alphaY) a.ly = s.alphaY[e];
-        if (s.alphaZ) a.lz = s.alphaZ[e];
         owners[o] = r;
         acc[o] = a;
     } else {
-        if (s.voxelID) s.voxelID[e] = r.voxelID;
-        if (s.locX) s.locX[e] = r.locX;
-        if (s.locY) s.locY[e] = r.locY;
-        if (s.locZ) s.locZ[e] = r.locZ;
-        if (s.oriQw) s.oriQw[e] = r.qw;
-        if (s.oriQx) s.oriQx[e] = r.qx;
-        if (s.oriQy) s.oriQy[e] = r.qy;
-        if (s.oriQz) s.oriQz[e] = r.qz;
-        if (s.vX) s.vX[e] = r.vx;
-        if (s.vY) s.vY[e] = r.vy;
-        if (s.vZ) s.vZ[e] = r.vz;
-        if (s.omgBarX) s.omgBarX[e] = r.wx;
-        if (s.omgBarY) s.omgBarY[e] = r.wy;
-        if (s.omgBarZ) s.omgBarZ[e] = r.wz;
+#define DEME_COL_R(abi, T, Rec, f) if (s.abi) s.abi[e] = r.f;
+#define DEME_COL_A(abi, T, Rec, f) if (s.abi) s.abi[e] = a.f;
+        DEME_OWNER_COLS(DEME_COL_R, DEME_COL_A, DEME_COL_NONE)
+#undef DEME_COL_R
+#undef DEME_COL_A
         if (s.familyID) s.familyID[e] = (uint8_t)r.family;
-        if (s.aX) s.aX[e] = a.ax;
-        if (s.aY) s.aY[e] = a.ay;
-        if (s.aZ) s.aZ[e] = a.az;
-        if (s.alphaX) s.alphaX[e] = a.lx;
-        if (s.alphaY) s.alphaY[e] = a.ly;
-        if (s.alphaZ) s.alphaZ[e] = a.lz;
     }
 }
 

@@ -4,10 +4,10 @@
 // A script that asks for the force on one plate, or for the neighbours of one clump, needs a few hundred rows of a list of
 // millions.  The kernels below run only when such a question is asked:
 //   k_query_mark    a mark scattered onto the caller's owner ids
-//   k_query_select  one thread per row of the current list: both owners looked up in the tables the force pass uses, translated to
-//                   the caller's ids, tested against the marks; the hit rows compacted per wavefront into a scratch buffer, with
-//                   the row's four 12-byte records when they are asked for
-//   k_query_select_slab  the same for one slab of a decomposed run: global ids from the device books, the merged list's
+//   k_query_select<false>  one thread per row of the current list: both owners looked up in the tables the force pass uses,
+//                   translated to the caller's ids, tested against the marks; the hit rows compacted per wavefront into a scratch
+//                   buffer, with the row's four 12-byte records when they are asked for
+//   k_query_select<true>  the same body for one slab of a decomposed run: global ids from the device books, the merged list's
 //                   report-once and flip rules (deme_multi_query_owner_contacts)
 //   k_query_owner_state  the 64-byte records of a few owners: a gather by slot, or one slab's share of a question in global ids
 //   k_scatter_owner_state  its counterpart: named fields of a few owners' records replaced, by slot or by global id on a slab
@@ -16,6 +16,7 @@
 #pragma once
 #include "deme_device.h"
 #include "deme_mesh.h"
+#include "deme_owner_cols.h"
 
 namespace deme_dev {
 
@@ -43,64 +44,6 @@ __global__ __launch_bounds__(256) void k_query_mark(uint32_t n, const uint32_t* 
         mark[ids[i]] = 1;  // (ids are in range and distinct: the host checks and de-duplicates them)
 }
 
-// rec[0..3] (force, torque-only force, cpA, cpB; 3 floats per row of the list) are copied bit for bit into recOut (12 floats per
-// hit) when recOut is not null.  cap: rows `hits` (and recOut) hold.
-__global__ __launch_bounds__(256) void k_query_select(uint32_t n, const uint64_t* __restrict__ keys, QueryTables t,
-                                                      const uint8_t* __restrict__ mark, const float* __restrict__ rec0,
-                                                      const float* __restrict__ rec1, const float* __restrict__ rec2,
-                                                      const float* __restrict__ rec3, QueryHit* __restrict__ hits,
-                                                      float* __restrict__ recOut, uint32_t cap, uint32_t* nHits) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    bool hit = false;
-    QueryHit h{};
-    if (i < n) {
-        const uint64_t k = keys[i];
-        const uint32_t cls = key_class(k), a = key_a(k), b = key_b(k);
-        uint32_t oA = 0xFFFFFFFFu, oB = 0xFFFFFFFFu;
-        if (a < t.nSpheres)
-            oA = load_sphere(t.spheres, a).owner;
-        if (cls == DEME_KEY_CLASS_SS) {
-            if (b < t.nSpheres)
-                oB = load_sphere(t.spheres, b).owner;
-        } else if (cls == DEME_KEY_CLASS_SM) {
-            if (b < t.nTri)
-                oB = t.tris[b].owner;
-        } else if (b < t.nAnal) {
-            oB = t.anal[b].owner;
-        }
-        if (oA < t.nOwners && oB < t.nOwners) {
-            if (t.o2e)
-                oA = t.o2e[oA], oB = t.o2e[oB];
-            const bool mA = oA < t.nOwners && mark[oA] != 0, mB = oB < t.nOwners && mark[oB] != 0;
-            hit = mA || mB;
-            h.key = t.s2e ? make_key(cls, t.s2e[a], cls == DEME_KEY_CLASS_SS ? t.s2e[b] : b) : k;
-            h.row = i, h.ownerA = oA, h.ownerB = oB, h.side = mA ? 0u : 1u;
-        }
-    }
-    // one reservation per wavefront (as k_resize_keys and k_sweep append)
-    const unsigned long long m = __ballot(hit);
-    if (!m)
-        return;
-    const uint32_t lane = __lane_id();
-    const uint32_t leader = (uint32_t)__ffsll((long long)m) - 1u;
-    uint32_t base = 0;
-    if (lane == leader)
-        base = atomicAdd(nHits, (uint32_t)__popcll(m));
-    base = __shfl(base, (int)leader);
-    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (!hit || at >= cap)  // the counter has counted the row; the host selects again with room for all of them
-        return;
-    hits[at] = h;
-    if (recOut) {
-        float* o = recOut + (size_t)at * 12;
-        const size_t r = (size_t)i * 3;
-        o[0] = rec0[r], o[1] = rec0[r + 1], o[2] = rec0[r + 2];
-        o[3] = rec1[r], o[4] = rec1[r + 1], o[5] = rec1[r + 2];
-        o[6] = rec2[r], o[7] = rec2[r + 1], o[8] = rec2[r + 2];
-        o[9] = rec3[r], o[10] = rec3[r + 1], o[11] = rec3[r + 2];
-    }
-}
-
 // ---- one slab of a decomposed run (deme_multi_query_owner_contacts) -------------------------------------------------------------
 // The slab lists its contacts in its own numbering; the question and the answer are in GLOBAL ids.  The books the migration keeps
 // on the device translate (SlabGeom::sphereGid / ownerGid, indexed by the slab scene's ids), so no host copy of them is needed.
@@ -119,8 +62,8 @@ __host__ __device__ inline uint64_t merged_key(uint64_t cls, uint32_t gA, uint32
 __host__ __device__ inline uint32_t merged_key_a(uint64_t k) { return (uint32_t)(k >> 34); }  // (the class sits where key_class reads it)
 __host__ __device__ inline uint32_t merged_key_b(uint64_t k) { return (uint32_t)(k & 0x7FFFFFFFull); }
 
-// The compaction of k_query_select for the kernels below: one reservation of the counter per wavefront; returns the slot of this
-// lane's hit, 0xFFFFFFFF for a lane without one.  Every lane of the wavefront calls it.
+// The compaction of the kernels below: one reservation of the counter per wavefront (as k_resize_keys and k_sweep append); returns
+// the slot of this lane's hit, 0xFFFFFFFF for a lane without one.  Every lane of the wavefront calls it.
 __device__ inline uint32_t query_append_slot(bool hit, uint32_t* nHits) {
     const unsigned long long m = __ballot(hit);
     if (!m)
@@ -134,16 +77,21 @@ __device__ inline uint32_t query_append_slot(bool hit, uint32_t* nHits) {
     return hit ? base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)) : 0xFFFFFFFFu;
 }
 
-// The rule of multi_contact_rows, row by row: a sphere-sphere pair is (smaller, larger) global sphere id; the row is reported only
-// by the slab that owns the clump of the (post-swap) sphere A; sphere-mesh and sphere-analytical rows go with sphere A's clump.  A
-// reported row is a hit when global owner A or B is marked.  Hits carry the merged key, the global owners, side (bit 0, in the
-// merged orientation) and the flipped bit (bit 1); the records of a flipped row as deme_multi_download_contact_records gives them:
-// force and torque-only force times -1.0f, cpA and cpB swapped.
-__global__ __launch_bounds__(256) void k_query_select_slab(uint32_t n, const uint64_t* __restrict__ keys, QueryTables t, SlabBooksDev bk,
-                                                           const uint8_t* __restrict__ mark, const float* __restrict__ rec0,
-                                                           const float* __restrict__ rec1, const float* __restrict__ rec2,
-                                                           const float* __restrict__ rec3, QueryHit* __restrict__ hits,
-                                                           float* __restrict__ recOut, uint32_t cap, uint32_t* nHits) {
+// rec[0..3] (force, torque-only force, cpA, cpB; 3 floats per row of the list) are copied into recOut (12 floats per hit) when
+// recOut is not null.  cap: rows `hits` (and recOut) hold.
+// SLAB false, a single context: a row is a hit when owner A or B (caller ids) is marked; the key is the caller's (order_key_out),
+// side 0 or 1, the records bit for bit; bk is not read.
+// SLAB true, the rule of multi_contact_rows row by row: a sphere-sphere pair is (smaller, larger) global sphere id; the row is
+// reported only by the slab that owns the clump of the (post-swap) sphere A; sphere-mesh and sphere-analytical rows go with sphere
+// A's clump.  A reported row is a hit when global owner A or B is marked.  Hits carry the merged key, the global owners, side (bit
+// 0, in the merged orientation) and the flipped bit (bit 1); the records of a flipped row as deme_multi_download_contact_records
+// gives them: force and torque-only force times -1.0f, cpA and cpB swapped.
+template <bool SLAB>
+__global__ __launch_bounds__(256) void k_query_select(uint32_t n, const uint64_t* __restrict__ keys, QueryTables t, SlabBooksDev bk,
+                                                      const uint8_t* __restrict__ mark, const float* __restrict__ rec0,
+                                                      const float* __restrict__ rec1, const float* __restrict__ rec2,
+                                                      const float* __restrict__ rec3, QueryHit* __restrict__ hits,
+                                                      float* __restrict__ recOut, uint32_t cap, uint32_t* nHits) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool hit = false, flipped = false;
     QueryHit h{};
@@ -163,23 +111,30 @@ __global__ __launch_bounds__(256) void k_query_select_slab(uint32_t n, const uin
             oB = t.anal[b].owner;
         }
         if (oA < t.nOwners && oB < t.nOwners) {
-            if (t.o2e)  // (a context with ghosts keeps the order it is uploaded in: null today)
+            if (t.o2e)  // (a context with ghosts keeps the order it is uploaded in: null on a slab today)
                 oA = t.o2e[oA], oB = t.o2e[oB];
-            uint32_t sA = t.s2e ? t.s2e[a] : a, sB = (t.s2e && cls == DEME_KEY_CLASS_SS) ? t.s2e[b] : b;
-            if (oA < t.nOwners && oB < t.nOwners && sA < t.nSpheres && (cls != DEME_KEY_CLASS_SS || sB < t.nSpheres)) {
-                uint32_t gA = bk.sphereGid[sA], gB = cls == DEME_KEY_CLASS_SS ? bk.sphereGid[sB] : sB;
-                if (cls == DEME_KEY_CLASS_SS && gA > gB) {
-                    uint32_t x = gA;
-                    gA = gB, gB = x;
-                    x = oA, oA = oB, oB = x;
-                    flipped = true;
-                }
-                if (oA < bk.nOwn) {  // the neighbour that owns that clump reports the pair otherwise
-                    const uint32_t goA = bk.ownerGid[oA], goB = bk.ownerGid[oB];
-                    const bool mA = goA < bk.nOwnersGlobal && mark[goA] != 0, mB = goB < bk.nOwnersGlobal && mark[goB] != 0;
-                    hit = mA || mB;
-                    h.key = merged_key(cls, gA, gB);
-                    h.row = i, h.ownerA = goA, h.ownerB = goB, h.side = (mA ? 0u : 1u) | (flipped ? DEME_QUERY_FLIPPED : 0u);
+            if constexpr (!SLAB) {
+                const bool mA = oA < t.nOwners && mark[oA] != 0, mB = oB < t.nOwners && mark[oB] != 0;
+                hit = mA || mB;
+                h.key = t.s2e ? make_key(cls, t.s2e[a], cls == DEME_KEY_CLASS_SS ? t.s2e[b] : b) : k;
+                h.row = i, h.ownerA = oA, h.ownerB = oB, h.side = mA ? 0u : 1u;
+            } else {
+                uint32_t sA = t.s2e ? t.s2e[a] : a, sB = (t.s2e && cls == DEME_KEY_CLASS_SS) ? t.s2e[b] : b;
+                if (oA < t.nOwners && oB < t.nOwners && sA < t.nSpheres && (cls != DEME_KEY_CLASS_SS || sB < t.nSpheres)) {
+                    uint32_t gA = bk.sphereGid[sA], gB = cls == DEME_KEY_CLASS_SS ? bk.sphereGid[sB] : sB;
+                    if (cls == DEME_KEY_CLASS_SS && gA > gB) {
+                        uint32_t x = gA;
+                        gA = gB, gB = x;
+                        x = oA, oA = oB, oB = x;
+                        flipped = true;
+                    }
+                    if (oA < bk.nOwn) {  // the neighbour that owns that clump reports the pair otherwise
+                        const uint32_t goA = bk.ownerGid[oA], goB = bk.ownerGid[oB];
+                        const bool mA = goA < bk.nOwnersGlobal && mark[goA] != 0, mB = goB < bk.nOwnersGlobal && mark[goB] != 0;
+                        hit = mA || mB;
+                        h.key = merged_key(cls, gA, gB);
+                        h.row = i, h.ownerA = goA, h.ownerB = goB, h.side = (mA ? 0u : 1u) | (flipped ? DEME_QUERY_FLIPPED : 0u);
+                    }
                 }
             }
         }
@@ -192,12 +147,14 @@ __global__ __launch_bounds__(256) void k_query_select_slab(uint32_t n, const uin
         float* o = recOut + (size_t)at * 12;
         const size_t r = (size_t)i * 3;
         const float sgn = flipped ? -1.0f : 1.0f;  // (the recorded force acts on A; a zero changes sign too, as on the host path)
-        const float* pa = flipped ? rec3 : rec2;
+        const float* pa = flipped ? rec3 : rec2;   // (flipped stays false on a single context)
         const float* pb = flipped ? rec2 : rec3;
-        o[0] = sgn * rec0[r], o[1] = sgn * rec0[r + 1], o[2] = sgn * rec0[r + 2];
-        o[3] = sgn * rec1[r], o[4] = sgn * rec1[r + 1], o[5] = sgn * rec1[r + 2];
-        o[6] = pa[r], o[7] = pa[r + 1], o[8] = pa[r + 2];
-        o[9] = pb[r], o[10] = pb[r + 1], o[11] = pb[r + 2];
+        for (int j = 0; j < 3; j++) {
+            o[j] = SLAB ? sgn * rec0[r + j] : rec0[r + j];
+            o[3 + j] = SLAB ? sgn * rec1[r + j] : rec1[r + j];
+            o[6 + j] = pa[r + j];
+            o[9 + j] = pb[r + j];
+        }
     }
 }
 
@@ -241,43 +198,16 @@ __global__ __launch_bounds__(256) void k_query_owner_state(uint32_t n, const Own
 
 // ---- writing pose, velocity and family of a few owners (deme_scatter_owner_state, deme_multi_scatter_owner_state) ------------------
 // The host sends one 64-byte record per id with the new values in their fields (the rest of it is not read) and a mask of the
-// columns the call gave: bit k is column k of DemeOwnerState in the order below.  What a write touches is what k_pack_owners
+// columns the call gave: DEME_SCATTER_BIT, bit k for pose column k of deme_owner_cols.h.  What a write touches is what k_pack_owners
 // touches with dir == 0: margin, inertiaOff and the flag bits of the family word keep their bits.
-#define DEME_SCATTER_VOXEL 0x0001u
-#define DEME_SCATTER_LOCX 0x0002u
-#define DEME_SCATTER_LOCY 0x0004u
-#define DEME_SCATTER_LOCZ 0x0008u
-#define DEME_SCATTER_QW 0x0010u
-#define DEME_SCATTER_QX 0x0020u
-#define DEME_SCATTER_QY 0x0040u
-#define DEME_SCATTER_QZ 0x0080u
-#define DEME_SCATTER_VX 0x0100u
-#define DEME_SCATTER_VY 0x0200u
-#define DEME_SCATTER_VZ 0x0400u
-#define DEME_SCATTER_WX 0x0800u
-#define DEME_SCATTER_WY 0x1000u
-#define DEME_SCATTER_WZ 0x2000u
-#define DEME_SCATTER_FAMILY 0x4000u
-
 __device__ inline void scatter_state_write(OwnerRec* __restrict__ owners, uint32_t slot, const OwnerRec* __restrict__ patch, uint32_t row,
                                            uint32_t mask) {
     OwnerRec r = owners[slot];
     const OwnerRec p = patch[row];
-    if (mask & DEME_SCATTER_VOXEL) r.voxelID = p.voxelID;
-    if (mask & DEME_SCATTER_LOCX) r.locX = p.locX;
-    if (mask & DEME_SCATTER_LOCY) r.locY = p.locY;
-    if (mask & DEME_SCATTER_LOCZ) r.locZ = p.locZ;
-    if (mask & DEME_SCATTER_QW) r.qw = p.qw;
-    if (mask & DEME_SCATTER_QX) r.qx = p.qx;
-    if (mask & DEME_SCATTER_QY) r.qy = p.qy;
-    if (mask & DEME_SCATTER_QZ) r.qz = p.qz;
-    if (mask & DEME_SCATTER_VX) r.vx = p.vx;
-    if (mask & DEME_SCATTER_VY) r.vy = p.vy;
-    if (mask & DEME_SCATTER_VZ) r.vz = p.vz;
-    if (mask & DEME_SCATTER_WX) r.wx = p.wx;
-    if (mask & DEME_SCATTER_WY) r.wy = p.wy;
-    if (mask & DEME_SCATTER_WZ) r.wz = p.wz;
-    if (mask & DEME_SCATTER_FAMILY) r.family = (r.family & OWNER_FLAG_BITS) | (p.family & 0xFFu);  // a ghost stays a ghost
+#define DEME_COL(abi, T, Rec, f) if (mask & DEME_SCATTER_BIT(abi)) r.f = p.f;
+    DEME_OWNER_COLS(DEME_COL, DEME_COL_NONE, DEME_COL_NONE)
+#undef DEME_COL
+    if (mask & DEME_SCATTER_BIT(familyID)) r.family = (r.family & OWNER_FLAG_BITS) | (p.family & 0xFFu);  // a ghost stays a ghost
     owners[slot] = r;
 }
 

@@ -97,6 +97,57 @@ constexpr unsigned int RESERVED_FAMILY_NUM = 255;
 const bool ENTITY_NORMAL_INWARD = false;
 const bool ENTITY_NORMAL_OUTWARD = true;
 
+/// Host room for the columns of DemeOwnerState.  view(groups, n) sizes the column groups asked for to n entries and returns a
+/// DemeOwnerState that names them; every other column stays null, which the library reads as "not asked" / "not written".
+struct OwnerCols {
+    enum : unsigned { POS = 1, ORI = 2, VEL = 4, ANGVEL = 8, ACC = 16, FAM = 32, POSE = POS | ORI | VEL | ANGVEL | FAM, ALL = POSE | ACC };
+    std::vector<uint64_t> vid;
+    std::vector<uint16_t> lx, ly, lz;
+    std::vector<float> f[16];  // oriQ w x y z, v, omgBar, a, alpha
+    std::vector<uint8_t> fam;
+    DemeOwnerState view(unsigned groups, size_t n) {
+        DemeOwnerState st{};
+        auto col = [&](int k) { return f[k].resize(n), f[k].data(); };
+        if (groups & POS) {
+            vid.resize(n), lx.resize(n), ly.resize(n), lz.resize(n);
+            st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
+        }
+        if (groups & ORI)
+            st.oriQw = col(0), st.oriQx = col(1), st.oriQy = col(2), st.oriQz = col(3);
+        if (groups & VEL)
+            st.vX = col(4), st.vY = col(5), st.vZ = col(6);
+        if (groups & ANGVEL)
+            st.omgBarX = col(7), st.omgBarY = col(8), st.omgBarZ = col(9);
+        if (groups & ACC)
+            st.aX = col(10), st.aY = col(11), st.aZ = col(12), st.alphaX = col(13), st.alphaY = col(14), st.alphaZ = col(15);
+        if (groups & FAM)
+            fam.resize(n), st.familyID = fam.data();
+        return st;
+    }
+    float4 q(size_t i) const { return {f[1][i], f[2][i], f[3][i], f[0][i]}; }
+    float3 vec(int first, size_t i) const { return {f[first][i], f[first + 1][i], f[first + 2][i]}; }  // 4: v, 7: omgBar, 10: a, 13: alpha
+    void set_q(size_t i, const float4& v) { f[0][i] = v.w, f[1][i] = v.x, f[2][i] = v.y, f[3][i] = v.z; }
+    void set_vec(int first, size_t i, const float3& v) { f[first][i] = v.x, f[first + 1][i] = v.y, f[first + 2][i] = v.z; }
+    void take_pose_row(size_t dst, const OwnerCols& from, size_t src) {  // the POSE columns of one owner
+        vid[dst] = from.vid[src], lx[dst] = from.lx[src], ly[dst] = from.ly[src], lz[dst] = from.lz[src], fam[dst] = from.fam[src];
+        for (int k = 0; k < 10; k++)
+            f[k][dst] = from.f[k][src];
+    }
+    /// the owner's centre from its position code, all fp32: voxelIDToPosition<float, ...> then + LBF (dT.cpp:1312-1320)
+    float3 com(size_t i, const DemeParams& p) const {
+        const uint64_t vx = vid[i] & ((1ull << p.nvXp2) - 1), vy = (vid[i] >> p.nvXp2) & ((1ull << p.nvYp2) - 1), vz = vid[i] >> (p.nvXp2 + p.nvYp2);
+        const float vs = (float)p.voxelSize, l = (float)p.l;
+        return make_float3(((float)vx * vs + (float)lx[i] * l) + p.LBFX, ((float)vy * vs + (float)ly[i] * l) + p.LBFY,
+                           ((float)vz * vs + (float)lz[i] * l) + p.LBFZ);
+    }
+    /// the same in double, rounded once at the end: voxelIDToPosition + LBF, DEMHelperKernels.cuh:116-134
+    float3 com_wide(size_t i, const DemeParams& p) const {
+        const uint64_t vx = vid[i] & ((1ull << p.nvXp2) - 1), vy = (vid[i] >> p.nvXp2) & ((1ull << p.nvYp2) - 1), vz = vid[i] >> (p.nvXp2 + p.nvYp2);
+        return {(float)((double)vx * p.voxelSize + (double)lx[i] * p.l + p.LBFX), (float)((double)vy * p.voxelSize + (double)ly[i] * p.l + p.LBFY),
+                (float)((double)vz * p.voxelSize + (double)lz[i] * p.l + p.LBFZ)};
+    }
+};
+
 struct DEMMaterial {
     std::unordered_map<std::string, float> mat_prop;
     unsigned int load_order = 0;
@@ -914,7 +965,7 @@ class DEMSolver {
     }
     float3 GetOwnerVelocity(unsigned int owner) {
         refresh_state();
-        return {m_st_v[0].at(owner), m_st_v[1].at(owner), m_st_v[2].at(owner)};
+        return {m_kin.f[4].at(owner), m_kin.f[5].at(owner), m_kin.f[6].at(owner)};
     }
     // DEMSolver::Get/SetOwner* (API.h:515-586): whole-state round trips through the ABI -- scripting calls, not for inner loops
     float3 GetOwnerAngVel(unsigned int owner) { return owner_column3(owner, 2); }
@@ -939,17 +990,17 @@ class DEMSolver {
             std::vector<bodyID_t> ids;
             for (size_t k = 0; k < n && owner + k < m_n_owners; k++)
                 ids.push_back((bodyID_t)(owner + k));
-            std::vector<uint8_t> f(ids.size(), (uint8_t)fam);
-            DemeOwnerState st{};
-            st.familyID = f.data();
+            OwnerCols s;
+            const DemeOwnerState st = s.view(OwnerCols::FAM, ids.size());
+            std::fill(s.fam.begin(), s.fam.end(), (uint8_t)fam);
             scatter_owner_state(ids, &st);
             return;
         }
-        std::vector<uint8_t> f = owner_families();
-        for (size_t k = 0; k < n && owner + k < f.size(); k++)
-            f[owner + k] = (uint8_t)fam;
-        DemeOwnerState st{};
-        st.familyID = f.data();
+        OwnerCols s;
+        DemeOwnerState st = s.view(OwnerCols::FAM, m_n_owners);
+        dl_state(&st);
+        for (size_t k = 0; k < n && owner + k < s.fam.size(); k++)
+            s.fam[owner + k] = (uint8_t)fam;
         ul_state(&st);
         state_changed();
     }
@@ -957,17 +1008,17 @@ class DEMSolver {
     size_t ChangeClumpFamily(unsigned int fam_num, const std::pair<double, double>& X = {-1e30, 1e30},
                              const std::pair<double, double>& Y = {-1e30, 1e30}, const std::pair<double, double>& Z = {-1e30, 1e30}) {
         refresh_state();
-        std::vector<uint8_t> f = owner_families();
+        OwnerCols s;
+        DemeOwnerState st = s.view(OwnerCols::FAM, m_n_owners);
+        dl_state(&st);
         size_t changed = 0;
         for (size_t i = 0; i < m_n_clumps; i++) {
             const float3 c = m_pos[i];
             if (c.x >= X.first && c.x <= X.second && c.y >= Y.first && c.y <= Y.second && c.z >= Z.first && c.z <= Z.second) {
-                f[i] = (uint8_t)fam_num;
+                s.fam[i] = (uint8_t)fam_num;
                 changed++;
             }
         }
-        DemeOwnerState st{};
-        st.familyID = f.data();
         ul_state(&st);
         return changed;
     }
@@ -975,7 +1026,10 @@ class DEMSolver {
         refresh_state();
         float m = 0;
         for (size_t i = 0; i < m_n_clumps; i++)
-            m = std::max(m, std::sqrt(m_st_v[0][i] * m_st_v[0][i] + m_st_v[1][i] * m_st_v[1][i] + m_st_v[2][i] * m_st_v[2][i]));
+            {
+            const float3 v = m_kin.vec(4, i);
+            m = std::max(m, std::sqrt(v.x * v.x + v.y * v.y + v.z * v.z));
+        }
         return m;
     }
     deme_ctx* GetContext() { return m_ctx; }
@@ -1039,18 +1093,8 @@ class DEMSolver {
     void UpdateClumps() {
         const size_t oldClumps = m_n_clumps, oldOwners = m_n_owners;
         // state of the old owners
-        std::vector<uint64_t> vid(oldOwners);
-        std::vector<uint16_t> lx(oldOwners), ly(oldOwners), lz(oldOwners);
-        std::vector<float> f[10];
-        for (auto& v : f)
-            v.resize(oldOwners);
-        std::vector<uint8_t> fam(oldOwners);
-        DemeOwnerState st{};
-        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
-        st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
-        st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
-        st.familyID = fam.data();
+        OwnerCols old;
+        DemeOwnerState st = old.view(OwnerCols::POSE, oldOwners);
         dl_state(&st);
         // contact list + wildcards
         const size_t nc = n_contacts();
@@ -1086,25 +1130,11 @@ class DEMSolver {
                                [](size_t i) { return i; });  // new spheres are appended
         // put the old owners' state back: old clumps keep their slots, the other owners moved behind the new clumps
         const size_t n = m_n_owners;
-        std::vector<uint64_t> vid2(n);
-        std::vector<uint16_t> lx2(n), ly2(n), lz2(n);
-        std::vector<float> g[10];
-        for (auto& v : g)
-            v.resize(n);
-        std::vector<uint8_t> fam2(n);
-        DemeOwnerState s2{};
-        s2.voxelID = vid2.data(), s2.locX = lx2.data(), s2.locY = ly2.data(), s2.locZ = lz2.data();
-        s2.oriQw = g[0].data(), s2.oriQx = g[1].data(), s2.oriQy = g[2].data(), s2.oriQz = g[3].data();
-        s2.vX = g[4].data(), s2.vY = g[5].data(), s2.vZ = g[6].data();
-        s2.omgBarX = g[7].data(), s2.omgBarY = g[8].data(), s2.omgBarZ = g[9].data();
-        s2.familyID = fam2.data();
+        OwnerCols now;
+        DemeOwnerState s2 = now.view(OwnerCols::POSE, n);
         dl_state(&s2);
-        for (size_t o = 0; o < oldOwners; o++) {
-            const size_t dst = o < oldClumps ? o : m_n_clumps + (o - oldClumps);
-            vid2[dst] = vid[o], lx2[dst] = lx[o], ly2[dst] = ly[o], lz2[dst] = lz[o], fam2[dst] = fam[o];
-            for (int k = 0; k < 10; k++)
-                g[k][dst] = f[k][o];
-        }
+        for (size_t o = 0; o < oldOwners; o++)
+            now.take_pose_row(o < oldClumps ? o : m_n_clumps + (o - oldClumps), old, o);
         ul_state(&s2);
         m_time = t;
         m_p.timeElapsed = t;
@@ -1173,18 +1203,8 @@ class DEMSolver {
         refresh_state();
         const size_t nC = m_n_clumps, nO = m_n_owners;
         // old state, contacts, history, marks
-        std::vector<uint64_t> vid(nO);
-        std::vector<uint16_t> lx(nO), ly(nO), lz(nO);
-        std::vector<float> f[10];
-        for (auto& v : f)
-            v.resize(nO);
-        std::vector<uint8_t> fam(nO);
-        DemeOwnerState st{};
-        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
-        st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
-        st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
-        st.familyID = fam.data();
+        OwnerCols old;
+        DemeOwnerState st = old.view(OwnerCols::POSE, nO);
         dl_state(&st);
         const size_t nc = n_contacts();
         const uint32_t nW = m_p.nContactWildcards;
@@ -1265,24 +1285,10 @@ class DEMSolver {
         m_reupload_dst = [&](size_t o, size_t) { return (size_t)new_of_old[o]; };
         initialize_impl();
         restore_user_wildcards(saved, [&](size_t o) { return (size_t)new_of_old[o]; }, [&](size_t i) { return (size_t)new_sphere((uint32_t)i); });
-        std::vector<uint64_t> vid2(nO);
-        std::vector<uint16_t> lx2(nO), ly2(nO), lz2(nO);
-        std::vector<float> g[10];
-        for (auto& v : g)
-            v.resize(nO);
-        std::vector<uint8_t> fam2(nO);
-        for (size_t o = 0; o < nO; o++) {
-            const size_t dst = new_of_old[o];
-            vid2[dst] = vid[o], lx2[dst] = lx[o], ly2[dst] = ly[o], lz2[dst] = lz[o], fam2[dst] = fam[o];
-            for (int k = 0; k < 10; k++)
-                g[k][dst] = f[k][o];
-        }
-        DemeOwnerState s2{};
-        s2.voxelID = vid2.data(), s2.locX = lx2.data(), s2.locY = ly2.data(), s2.locZ = lz2.data();
-        s2.oriQw = g[0].data(), s2.oriQx = g[1].data(), s2.oriQy = g[2].data(), s2.oriQz = g[3].data();
-        s2.vX = g[4].data(), s2.vY = g[5].data(), s2.vZ = g[6].data();
-        s2.omgBarX = g[7].data(), s2.omgBarY = g[8].data(), s2.omgBarZ = g[9].data();
-        s2.familyID = fam2.data();
+        OwnerCols now;
+        const DemeOwnerState s2 = now.view(OwnerCols::POSE, nO);
+        for (size_t o = 0; o < nO; o++)
+            now.take_pose_row(new_of_old[o], old, o);
         ul_state(&s2);
         m_time = t;
         m_p.timeElapsed = t;
@@ -1384,22 +1390,10 @@ class DEMSolver {
             who[i] = oc.side[i] == 0 ? oc.ownerA[i] : oc.ownerB[i];
         std::sort(who.begin(), who.end());
         who.erase(std::unique(who.begin(), who.end()), who.end());
-        const size_t n = who.size();
-        std::vector<uint64_t> vid(n);
-        std::vector<uint16_t> lx(n), ly(n), lz(n);
-        std::vector<float> qw(n), qx(n), qy(n), qz(n);
-        DemeOwnerState st{};
-        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        st.oriQw = qw.data(), st.oriQx = qx.data(), st.oriQy = qy.data(), st.oriQz = qz.data();
+        OwnerCols s;
+        DemeOwnerState st = s.view(OwnerCols::POS | OwnerCols::ORI, who.size());
         query_owner_state(who, &st);
         auto at = [&](bodyID_t o) { return (size_t)(std::lower_bound(who.begin(), who.end(), o) - who.begin()); };
-        const float vs = (float)m_p.voxelSize, l = (float)m_p.l;
-        auto com_of = [&](size_t i) {  // (as snapshot(): voxelIDToPosition<float, ...> then + LBF, all fp32)
-            const uint64_t vx = vid[i] & ((1ull << m_p.nvXp2) - 1), vy = (vid[i] >> m_p.nvXp2) & ((1ull << m_p.nvYp2) - 1),
-                           vz = vid[i] >> (m_p.nvXp2 + m_p.nvYp2);
-            return make_float3(((float)vx * vs + (float)lx[i] * l) + m_p.LBFX, ((float)vy * vs + (float)ly[i] * l) + m_p.LBFY,
-                               ((float)vz * vs + (float)lz[i] * l) + m_p.LBFZ);
-        };
         for (size_t i = 0; i < oc.n; i++) {
             const bool isA = oc.side[i] == 0;
             float3 force = {oc.F[3 * i], oc.F[3 * i + 1], oc.F[3 * i + 2]}, torque = {oc.T[3 * i], oc.T[3 * i + 1], oc.T[3 * i + 2]};
@@ -1413,7 +1407,7 @@ class DEMSolver {
                 force = force * -1.f;
                 torque = torque * -1.f;
             }
-            const float4 q = {qx[o], qy[o], qz[o], qw[o]};
+            const float4 q = s.q(o);
             if (torques) {  // the torque-only force becomes a torque about the contact point, in the owner's frame
                 rotate(torque, {-q.x, -q.y, -q.z, q.w});
                 torque = {pnt.y * torque.z - pnt.z * torque.y, pnt.z * torque.x - pnt.x * torque.z, pnt.x * torque.y - pnt.y * torque.x};
@@ -1422,7 +1416,7 @@ class DEMSolver {
                 torques->push_back(torque);
             }
             rotate(pnt, q);
-            points.push_back(pnt + com_of(o));
+            points.push_back(pnt + s.com(o, m_p));  // (as snapshot())
             forces.push_back(force);
         }
         return points.size();
@@ -2280,11 +2274,10 @@ class DEMSolver {
         return std::vector<float>(a.begin() + geoID, a.begin() + std::min(a.size(), (size_t)geoID + n));
     }
     std::vector<uint8_t> owner_families() {
-        std::vector<uint8_t> fam(m_n_owners);
-        DemeOwnerState st{};
-        st.familyID = fam.data();
+        OwnerCols s;
+        DemeOwnerState st = s.view(OwnerCols::FAM, m_n_owners);
         dl_state(&st);
-        return fam;
+        return std::move(s.fam);
     }
     // mode 0 all, 1 either owner's family == N1, 2 both, 3 the pair (N1, N2): APIPrivate.cpp's setFamilyContactWildcardValue_impl
     void set_contact_wc(int mode, unsigned int N1, unsigned int N2, const std::string& name, float val) {
@@ -2331,7 +2324,7 @@ class DEMSolver {
     uint64_t m_state_epoch = 0;  // counts the changes of the owners' state: what a tracker's gathered records are valid for
     void state_changed() { m_state_fresh = false, m_state_epoch++; }
     std::vector<float3> m_pos;
-    std::vector<float> m_st_v[3];
+    OwnerCols m_kin;  // position code and velocity of every owner as of refresh_state()
 
 
     struct Presc {
@@ -2505,34 +2498,17 @@ class DEMSolver {
     }
     Snapshot snapshot(bool contacts) {
         const size_t n = m_n_owners;
-        std::vector<uint64_t> vid(n);
-        std::vector<uint16_t> lx(n), ly(n), lz(n);
-        std::vector<float> f[16];
-        for (auto& v : f)
-            v.resize(n);
-        Snapshot sn;
-        sn.fam.resize(n);
-        DemeOwnerState st{};
-        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
-        st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
-        st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
-        st.aX = f[10].data(), st.aY = f[11].data(), st.aZ = f[12].data();
-        st.alphaX = f[13].data(), st.alphaY = f[14].data(), st.alphaZ = f[15].data();
-        st.familyID = sn.fam.data();
+        OwnerCols s;
+        DemeOwnerState st = s.view(OwnerCols::ALL, n);
         dl_state(&st);
+        Snapshot sn;
+        sn.fam = std::move(s.fam);
         sn.com.resize(n), sn.q.resize(n), sn.v.resize(n), sn.w.resize(n), sn.a.resize(n), sn.al.resize(n);
-        const float vs = (float)m_p.voxelSize, l = (float)m_p.l;
-        for (size_t i = 0; i < n; i++) {  // voxelIDToPosition<float, ...> then + LBF, all fp32 (dT.cpp:1312-1320)
-            const uint64_t vx = vid[i] & ((1ull << m_p.nvXp2) - 1), vy = (vid[i] >> m_p.nvXp2) & ((1ull << m_p.nvYp2) - 1),
-                           vz = vid[i] >> (m_p.nvXp2 + m_p.nvYp2);
-            sn.com[i] = {((float)vx * vs + (float)lx[i] * l) + m_p.LBFX, ((float)vy * vs + (float)ly[i] * l) + m_p.LBFY,
-                         ((float)vz * vs + (float)lz[i] * l) + m_p.LBFZ};
-            sn.q[i] = {f[1][i], f[2][i], f[3][i], f[0][i]};
-            sn.v[i] = {f[4][i], f[5][i], f[6][i]};
-            sn.w[i] = {f[7][i], f[8][i], f[9][i]};
-            sn.a[i] = {f[10][i], f[11][i], f[12][i]};
-            sn.al[i] = {f[13][i], f[14][i], f[15][i]};
+        for (size_t i = 0; i < n; i++) {
+            sn.com[i] = s.com(i, m_p);
+            sn.q[i] = s.q(i);
+            sn.v[i] = s.vec(4, i), sn.w[i] = s.vec(7, i);
+            sn.a[i] = s.vec(10, i), sn.al[i] = s.vec(13, i);
         }
         if (contacts) {
             const size_t nc = n_contacts();
@@ -2639,6 +2615,17 @@ class DEMSolver {
         vid = nn[0] + (nn[1] << m_p.nvXp2) + (nn[2] << (m_p.nvXp2 + m_p.nvYp2));
         lx = ss[0], ly = ss[1], lz = ss[2];
     }
+    // row k of the columns whose value is given (their groups are in the view)
+    void write_owner_row(OwnerCols& s, size_t k, const float3* pos, const float3* vel, const float3* angvel, const float4* q) const {
+        if (pos)
+            position_code(*pos, s.vid[k], s.lx[k], s.ly[k], s.lz[k]);
+        if (q)
+            s.set_q(k, *q);
+        if (vel)
+            s.set_vec(4, k, *vel);
+        if (angvel)
+            s.set_vec(7, k, *angvel);
+    }
     // tracker setters: one scatter of the given fields for the given owners (entry k of a non-null array goes to ids[k]);
     // DEME_TRACKER_HOST=1: a read-modify-write of the affected SoA columns over all owners, owner by owner
     void set_owners(const std::vector<bodyID_t>& ids, const float3* pos, const float3* vel, const float3* angvel, const float4* q) {
@@ -2648,56 +2635,21 @@ class DEMSolver {
             return;
         }
         const size_t n = ids.size();
-        std::vector<uint64_t> vid(n);
-        std::vector<uint16_t> lx(n), ly(n), lz(n);
-        std::vector<float> f[10];
-        for (auto& v : f)
-            v.resize(n);
-        DemeOwnerState st{};
-        for (size_t k = 0; k < n; k++) {
-            if (pos)
-                position_code(pos[k], vid[k], lx[k], ly[k], lz[k]);
-            if (q)
-                f[0][k] = q[k].w, f[1][k] = q[k].x, f[2][k] = q[k].y, f[3][k] = q[k].z;
-            if (vel)
-                f[4][k] = vel[k].x, f[5][k] = vel[k].y, f[6][k] = vel[k].z;
-            if (angvel)
-                f[7][k] = angvel[k].x, f[8][k] = angvel[k].y, f[9][k] = angvel[k].z;
-        }
-        if (pos)
-            st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        if (q)
-            st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
-        if (vel)
-            st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
-        if (angvel)
-            st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
+        OwnerCols s;
+        const DemeOwnerState st =
+            s.view((pos ? OwnerCols::POS : 0u) | (q ? OwnerCols::ORI : 0u) | (vel ? OwnerCols::VEL : 0u) | (angvel ? OwnerCols::ANGVEL : 0u), n);
+        for (size_t k = 0; k < n; k++)
+            write_owner_row(s, k, pos ? pos + k : nullptr, vel ? vel + k : nullptr, angvel ? angvel + k : nullptr, q ? q + k : nullptr);
         scatter_owner_state(ids, &st);
     }
     void set_owner(size_t o, const float3* pos, const float3* vel, const float3* angvel, const float4* q) {
         set_owners({(bodyID_t)o}, pos, vel, angvel, q);
     }
     void set_owner_whole_state(size_t o, const float3* pos, const float3* vel, const float3* angvel, const float4* q) {
-        const size_t n = m_n_owners;
-        std::vector<uint64_t> vid(n);
-        std::vector<uint16_t> lx(n), ly(n), lz(n);
-        std::vector<float> f[10];
-        for (auto& v : f)
-            v.resize(n);
-        DemeOwnerState st{};
-        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
-        st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
-        st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
+        OwnerCols s;
+        DemeOwnerState st = s.view(OwnerCols::POS | OwnerCols::ORI | OwnerCols::VEL | OwnerCols::ANGVEL, m_n_owners);
         dl_state(&st);
-        if (pos)
-            position_code(*pos, vid[o], lx[o], ly[o], lz[o]);
-        if (q)
-            f[0][o] = q->w, f[1][o] = q->x, f[2][o] = q->y, f[3][o] = q->z;
-        if (vel)
-            f[4][o] = vel->x, f[5][o] = vel->y, f[6][o] = vel->z;
-        if (angvel)
-            f[7][o] = angvel->x, f[8][o] = angvel->y, f[9][o] = angvel->z;
+        write_owner_row(s, o, pos, vel, angvel, q);
         ul_state(&st);
         state_changed();
     }
@@ -2722,22 +2674,11 @@ class DEMSolver {
     void refresh_state() {
         if (m_state_fresh)
             return;
-        std::vector<uint64_t> vid(m_n_owners);
-        std::vector<uint16_t> lx(m_n_owners), ly(m_n_owners), lz(m_n_owners);
-        for (auto& v : m_st_v)
-            v.resize(m_n_owners);
-        DemeOwnerState st{};
-        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        st.vX = m_st_v[0].data(), st.vY = m_st_v[1].data(), st.vZ = m_st_v[2].data();
+        DemeOwnerState st = m_kin.view(OwnerCols::POS | OwnerCols::VEL, m_n_owners);
         dl_state(&st);
         m_pos.resize(m_n_owners);
-        for (size_t i = 0; i < m_n_owners; i++) {  // voxelIDToPosition + LBF, DEMHelperKernels.cuh:116-134
-            const uint64_t vx = vid[i] & ((1ull << m_p.nvXp2) - 1), vy = (vid[i] >> m_p.nvXp2) & ((1ull << m_p.nvYp2) - 1),
-                           vz = vid[i] >> (m_p.nvXp2 + m_p.nvYp2);
-            m_pos[i] = {(float)((double)vx * m_p.voxelSize + (double)lx[i] * m_p.l + m_p.LBFX),
-                        (float)((double)vy * m_p.voxelSize + (double)ly[i] * m_p.l + m_p.LBFY),
-                        (float)((double)vz * m_p.voxelSize + (double)lz[i] * m_p.l + m_p.LBFZ)};
-        }
+        for (size_t i = 0; i < m_n_owners; i++)
+            m_pos[i] = m_kin.com_wide(i, m_p);
         m_state_fresh = true;
     }
 
@@ -3515,30 +3456,15 @@ class DEMTracker {
             return g;
         const std::vector<bodyID_t> ids = all_owner_ids();
         const size_t n = ids.size();
-        std::vector<uint64_t> vid(n);
-        std::vector<uint16_t> lx(n), ly(n), lz(n);
-        std::vector<float> f[10];
-        for (auto& v : f)
-            v.resize(n);
-        std::vector<uint8_t> fam(n);
-        DemeOwnerState st{};
-        st.voxelID = vid.data(), st.locX = lx.data(), st.locY = ly.data(), st.locZ = lz.data();
-        st.oriQw = f[0].data(), st.oriQx = f[1].data(), st.oriQy = f[2].data(), st.oriQz = f[3].data();
-        st.vX = f[4].data(), st.vY = f[5].data(), st.vZ = f[6].data();
-        st.omgBarX = f[7].data(), st.omgBarY = f[8].data(), st.omgBarZ = f[9].data();
-        st.familyID = fam.data();
+        OwnerCols s;
+        DemeOwnerState st = s.view(OwnerCols::POSE, n);
         m_sys->query_owner_state(ids, &st);
         g.pos.resize(n), g.vel.resize(n), g.w.resize(n), g.q.resize(n), g.fam.resize(n);
-        const DemeParams& p = m_sys->m_p;
-        for (size_t i = 0; i < n; i++) {  // the position as DEMSolver::refresh_state() computes it
-            const uint64_t vx = vid[i] & ((1ull << p.nvXp2) - 1), vy = (vid[i] >> p.nvXp2) & ((1ull << p.nvYp2) - 1),
-                           vz = vid[i] >> (p.nvXp2 + p.nvYp2);
-            g.pos[i] = {(float)((double)vx * p.voxelSize + (double)lx[i] * p.l + p.LBFX), (float)((double)vy * p.voxelSize + (double)ly[i] * p.l + p.LBFY),
-                        (float)((double)vz * p.voxelSize + (double)lz[i] * p.l + p.LBFZ)};
-            g.q[i] = {f[1][i], f[2][i], f[3][i], f[0][i]};
-            g.vel[i] = {f[4][i], f[5][i], f[6][i]};
-            g.w[i] = {f[7][i], f[8][i], f[9][i]};
-            g.fam[i] = fam[i];
+        for (size_t i = 0; i < n; i++) {
+            g.pos[i] = s.com_wide(i, m_sys->m_p);  // the position as DEMSolver::refresh_state() computes it
+            g.q[i] = s.q(i);
+            g.vel[i] = s.vec(4, i), g.w[i] = s.vec(7, i);
+            g.fam[i] = s.fam[i];
         }
         g.epoch = m_sys->m_state_epoch, g.valid = true;
         return g;

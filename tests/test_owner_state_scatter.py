@@ -309,3 +309,62 @@ def test_multi_scatter_sets_the_flags_on_every_slab(pkg, n_slabs):
     m.sync()
     assert per_slab() == [2] * n_slabs
     m.close()
+
+
+def _pattern(pkg, name, n, salt):
+    """n values of column `name` with a bit pattern of their own per owner and per salt (the family has 251 of them to give)"""
+    i = np.arange(n, dtype=np.uint64)
+    dt = pkg.abi.STATE_DTYPES[name]
+    if dt == np.float32:  # finite, positive, none of them a value a scene would hold
+        return (np.uint64(0x3C000000 + 0x10000 * salt + 1) + np.uint64(7) * i).astype(np.uint32).view(np.float32)
+    if dt == np.uint64:
+        return np.uint64(0x0000000100000003) * (i + np.uint64(1)) + np.uint64(salt)
+    if dt == np.uint16:
+        return (np.uint64(1000 * salt + 1) + np.uint64(5) * i).astype(np.uint16)
+    return ((np.uint64(7) * i + np.uint64(salt)) % np.uint64(251)).astype(np.uint8)
+
+
+@pytest.mark.parametrize("mode", ["fast", "exact"])
+def test_every_column_lands_in_its_own_field(pkg, mode):
+    """Column by column at the ABI, on 300 clumps in random order, a box and a mesh owner, with no step taken (a / alpha are plain
+    storage then): one column uploaded alone reads back bit for bit and leaves the other 20 as they were -- a column paired with
+    its neighbour's field would pass every twin test above.  Then the 15 pose columns through the scatter, on a few ids.  (300
+    clumps, not fewer: the engine keeps an order of its own only beyond two tiles of 128, and the fast leg is to go through it.)"""
+    b = pkg.model.packed_bed(300, seed=3, cd_freq=0, spacing_mult=2.8, order="random")
+    lo, hi = b.user_box_min, b.user_box_max
+    v, f = pkg.model.plate_mesh(4, 4, float(hi[0] - lo[0]) * 0.9, float(hi[1] - lo[1]) * 0.9, z=0.0, wavy=0.003)
+    m = b.AddMeshObject(v, f, 0)
+    m.SetInitPos(((lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2, 0.0195))
+    m.SetMass(0.5), m.SetMOI((1e-3, 1e-3, 2e-3))
+    p, sc = b.Initialize()
+    nO, nC = int(sc.nOwners), int(sc.nOwnerClumps)
+    assert nC == 300 and nO == nC + 2 and int(sc.nTri) > 0 and int(sc.nAnal) > 0
+    ctx = pkg.Context(0)
+    ctx.set_arith_mode(mode)
+    ctx.set_params(p), ctx.upload_scene(sc)
+    assert ctx.engine_order()[0] == (mode == "fast")
+    cols = list(pkg.abi.STATE_DTYPES)
+    assert len(cols) == 21
+    for salt, k in enumerate(cols):
+        before = ctx.download_state()
+        new = _pattern(pkg, k, nO, salt)
+        ctx.upload_state({k: new})
+        after = ctx.download_state()
+        assert np.array_equal(_bits(after[k]), _bits(new)), (mode, "upload", k)
+        for other in cols:
+            if other != k:
+                assert np.array_equal(_bits(after[other]), _bits(before[other])), (mode, "upload of", k, "moved", other)
+    ids = np.array([nO - 1, 7, nC, 130, nC - 1, 0], np.int64)  # unsorted: the mesh owner, the box, clumps of both tiles
+    rest = np.setdiff1d(np.arange(nO), ids)
+    assert pkg.abi.QUERY_STATE_COLUMNS == tuple(c for c in cols if not c.startswith(("a", "alpha")))
+    for salt, k in enumerate(pkg.abi.QUERY_STATE_COLUMNS, start=len(cols)):
+        before = ctx.download_state()
+        new = _pattern(pkg, k, len(ids), salt)
+        ctx.scatter_owner_state(ids, {k: new})
+        after = ctx.download_state()
+        assert np.array_equal(_bits(after[k][ids]), _bits(new)), (mode, "scatter", k)
+        assert np.array_equal(_bits(after[k][rest]), _bits(before[k][rest])), (mode, "scatter", k, "other owners")
+        for other in cols:
+            if other != k:
+                assert np.array_equal(_bits(after[other]), _bits(before[other])), (mode, "scatter of", k, "moved", other)
+    ctx.close()
