@@ -99,6 +99,10 @@ class DemeCounts(C.Structure):
                 ("maxSpheresInBin", C.c_uint32), ("lastStatus", C.c_uint32)]
 
 
+class DemeContactSums(C.Structure):
+    _fields_ = [("virial", C.c_double * 9), ("sides", C.c_uint64), ("clumps", C.c_uint64)]
+
+
 class DemeAdaptive(C.Structure):
     """include/deme_hip.h DemeAdaptive; the defaults are the reference's (DEM/Structs.h:204-216)"""
     _fields_ = [("autoBinSize", C.c_uint32), ("binObserveSteps", C.c_uint32), ("binMaxRate", C.c_float), ("binAcc", C.c_float),
@@ -212,6 +216,10 @@ def load_library():
         "deme_query_owner_contacts": [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                       C.POINTER(C.c_size_t)],
         "deme_query_host_bytes": [_P, C.POINTER(C.c_uint64)],
+        "deme_inspect_contacts": [_P, C.c_int, C.c_float, C.POINTER(DemeContactSums)],
+        "deme_inspect_contact_counts": [_P, C.c_int, C.c_float, _P, C.c_size_t],
+        "deme_multi_inspect_contacts": [_P, C.c_char_p, C.c_float, C.POINTER(DemeContactSums)],
+        "deme_multi_inspect_contact_counts": [_P, C.c_char_p, C.c_float, _P, C.c_size_t],
         "deme_query_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_scatter_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
@@ -697,6 +705,22 @@ class Multi:
         out.update(rec)
         return {k: v[:m].copy() for k, v in out.items()}
 
+    def inspect_contacts(self, region_code=None, force_threshold=1e-12):
+        """deme_multi_inspect_contacts: Context.inspect_contacts over every slab's own clumps, added in slab order.  region_code: a
+        region string (compiled once per slab), None everywhere."""
+        out = DemeContactSums()
+        code = None if region_code is None else region_code.encode()
+        self._ck(self.lib.deme_multi_inspect_contacts(self.h, code, float(force_threshold), C.byref(out)), "deme_multi_inspect_contacts")
+        return _contact_sums_dict(out)
+
+    def inspect_contact_counts(self, region_code=None, force_threshold=1e-12):
+        """deme_multi_inspect_contact_counts: the counted sides per owner by GLOBAL owner id (uint32)"""
+        out = np.zeros(self.n_owners, np.uint32)
+        code = None if region_code is None else region_code.encode()
+        self._ck(self.lib.deme_multi_inspect_contact_counts(self.h, code, float(force_threshold), _ptr(out), out.size),
+                 "deme_multi_inspect_contact_counts")
+        return out
+
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied from the devices to the host since the run was created"""
         v = C.c_uint64(0)
@@ -735,6 +759,10 @@ class Multi:
 
 QUERY_STATE_COLUMNS = ("voxelID", "locX", "locY", "locZ", "oriQw", "oriQx", "oriQy", "oriQz", "vX", "vY", "vZ", "omgBarX", "omgBarY",
                        "omgBarZ", "familyID")
+
+
+def _contact_sums_dict(s):
+    return {"virial": np.array(list(s.virial), np.float64).reshape(3, 3), "sides": int(s.sides), "clumps": int(s.clumps)}
 
 
 def _owner_state_request(owner_ids, columns):
@@ -1169,6 +1197,22 @@ class Context:
         self._query_rows = m
         out.update(rec)
         return {k: v[:m].copy() for k, v in out.items()}
+
+    def inspect_contacts(self, region=-1, force_threshold=1e-12):
+        """deme_inspect_contacts: the virial sum and the coordination counts of the current list, summed on the device.  A dict:
+        virial (3 x 3 float64, sum of arm (x) force over the counted sides; divide by the region's volume for the Love-Weber
+        stress), sides, clumps (mean coordination number = sides / clumps).  region: a handle of compile_region, -1 everywhere."""
+        out = DemeContactSums()
+        self._ck(self.lib.deme_inspect_contacts(self.h, int(region), float(force_threshold), C.byref(out)), "deme_inspect_contacts")
+        return _contact_sums_dict(out)
+
+    def inspect_contact_counts(self, region=-1, force_threshold=1e-12):
+        """deme_inspect_contact_counts: the counted sides per owner (uint32, the caller's numbering)"""
+        self.refresh_sizes()
+        out = np.zeros(self.n_owners, np.uint32)
+        self._ck(self.lib.deme_inspect_contact_counts(self.h, int(region), float(force_threshold), _ptr(out), out.size),
+                 "deme_inspect_contact_counts")
+        return out
 
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied to the host since the context was created (count read-backs, hit

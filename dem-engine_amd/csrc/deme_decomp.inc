@@ -1736,6 +1736,142 @@ int deme_multi_inspect_values(deme_multi* m, uint32_t q, float* out, size_t cap)
     return DEME_OK;
 }
 
+// ---- contact inspectors of a decomposed run (deme_contact_inspect.h) ------------------------------------------------------------------
+// Every slab runs the single context's passes over its own list; its mask holds its own clumps only (a ghost copy carries the ghost
+// bit), so a contact across a cut gives one side on each of its two slabs.  The host adds the slabs' answers in slab order.
+namespace {
+// the region of a slab context for a region string: compiled on first use, then found by its text; blank: -1
+int slab_region(deme_ctx* c, const char* code, int* id) {
+    const std::string src = code ? code : "";
+    *id = -1;
+    if (src.find_first_not_of(" \t\r\n") == std::string::npos)
+        return DEME_OK;
+    auto it = c->regionBySource.find(src);
+    if (it == c->regionBySource.end()) {
+        int rid = -1;
+        if (int rc = deme_compile_region(c, src.c_str(), &rid))
+            return rc;
+        it = c->regionBySource.emplace(src, rid).first;
+    }
+    *id = it->second;
+    return DEME_OK;
+}
+// what both calls refuse before any slab is asked, and the slabs' regions (in slab order)
+int multi_contact_inspect_begin(deme_multi* m, const char* who, const void* out, const char* regionCode, float thr, std::vector<int>& regions) {
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    if (!out)
+        return mfail(m, DEME_ERR_INVALID, "%s: null output", who);
+    if (!std::isfinite(thr) || thr < 0.f)
+        return mfail(m, DEME_ERR_INVALID, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    for (auto* g : m->groups)
+        if (g->pairsOnce)
+            return mfail(m, DEME_ERR_INVALID, "%s: the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab that "
+                         "does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    for (auto* g : m->groups)  // what deme_multi_download_contact_records would say, slab by slab
+        for (auto& s : g->slabs) {
+            deme_ctx* c = s.ctx;
+            if (!s.geo.set)
+                return mfail(m, DEME_ERR_INVALID, "%s: a slab has no books (deme_halo_group_set_slab / _build)", who);
+            if (!c->nContacts)
+                continue;
+            int rc = DEME_OK;  // (fail() writes c->err: called on its own, before the message is read)
+            if (!c->record)
+                rc = fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
+            else if (c->seeded)
+                rc = fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+            if (rc)
+                return mfail(m, rc, "%s", c->err.c_str());
+        }
+    regions.clear();
+    for (auto* g : m->groups) {
+        if (hipSetDevice(g->device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+        for (auto& s : g->slabs) {
+            int rid = -1;
+            if (int rc = slab_region(s.ctx, regionCode, &rid))
+                return mfail(m, rc, "%s", s.ctx->err.c_str());
+            regions.push_back(rid);
+        }
+    }
+    return DEME_OK;
+}
+// one slab's counted sides per owner slot (left in ciCounts by contact_inspect_launch) added at the global ids of h
+int slab_contact_counts(deme_ctx* c, const HaloSlab& s, uint32_t nOG, std::vector<uint32_t>& h) {
+    if (ensure(c, c->ciOut, std::max<size_t>(nOG, 1) * 4))
+        return c->lastStatus;
+    HIPCK(hipMemsetAsync(c->ciOut.p, 0, (size_t)nOG * 4, c->stream));
+    if (c->nOwners)
+        hipLaunchKernelGGL(k_contact_counts_out, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->nOwners, c->ciCounts.as<uint32_t>(),
+                           c->dp.o2e, (const uint32_t*)s.geo.ownerGid, c->ciOut.as<uint32_t>(), nOG);
+    h.resize(nOG);
+    HIPCK(hipMemcpyAsync(h.data(), c->ciOut.p, (size_t)nOG * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+int slab_contact_sums(deme_ctx* c, int region, float thr, DemeContactSums* h) {
+    ContactSums* res = nullptr;
+    if (int rc = contact_inspect_launch(c, region, thr, false, &res))
+        return rc;
+    HIPCK(hipMemcpyAsync(h, res, sizeof *h, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+}  // namespace
+
+int deme_multi_inspect_contacts(deme_multi* m, const char* regionCode, float thr, DemeContactSums* out) {
+    std::vector<int> regions;
+    if (int rc = multi_contact_inspect_begin(m, "deme_multi_inspect_contacts", out, regionCode, thr, regions))
+        return rc;
+    DemeContactSums sum{};
+    size_t slab = 0;
+    for (auto* g : m->groups) {
+        if (hipSetDevice(g->device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+        for (auto& s : g->slabs) {
+            DemeContactSums h{};
+            if (int rc = slab_contact_sums(s.ctx, regions[slab++], thr, &h))
+                return mfail(m, rc, "%s", s.ctx->err.c_str());
+            m->qHostBytes += sizeof h;
+            for (int j = 0; j < 9; j++)
+                sum.virial[j] += h.virial[j];
+            sum.sides += h.sides, sum.clumps += h.clumps;
+        }
+    }
+    *out = sum;
+    return DEME_OK;
+}
+
+int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, float thr, uint32_t* perOwnerGlobal, size_t cap) {
+    std::vector<int> regions;
+    if (m && m->plan && perOwnerGlobal && cap < m->plan->nOwnersGlobal)
+        return mfail(m, DEME_ERR_INVALID, "buffer too small: need %zu", (size_t)m->plan->nOwnersGlobal);
+    if (int rc = multi_contact_inspect_begin(m, "deme_multi_inspect_contact_counts", perOwnerGlobal, regionCode, thr, regions))
+        return rc;
+    const uint32_t nOG = m->plan->nOwnersGlobal;
+    std::vector<uint32_t> sum(nOG, 0u), h;
+    size_t slab = 0;
+    for (auto* g : m->groups) {
+        if (hipSetDevice(g->device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+        for (auto& s : g->slabs) {
+            deme_ctx* c = s.ctx;
+            if (int rc = contact_inspect_launch(c, regions[slab++], thr, true, nullptr))
+                return mfail(m, rc, "%s", c->err.c_str());
+            if (int rc = slab_contact_counts(c, s, nOG, h))
+                return mfail(m, rc, "%s", c->err.c_str());
+            m->qHostBytes += 4ull * nOG;
+            for (uint32_t i = 0; i < nOG; i++)
+                sum[i] += h[i];
+        }
+    }
+    if (nOG)
+        memcpy(perOwnerGlobal, sum.data(), (size_t)nOG * 4);
+    return DEME_OK;
+}
+
 // ---- moving the slab boundaries (load balance of a bed that drifts or piles up) --------------------------------------------------------
 // deme_halo_group_migrate keeps the boundaries where the plan put them.  deme_multi_rebalance recomputes them from the clumps'
 // CURRENT coordinates -- equal counts again, snapped to bin faces like the plan's -- and lets the same migration move the clumps that

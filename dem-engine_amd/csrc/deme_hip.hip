@@ -48,6 +48,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_mesh_kernels.h"
 #include "deme_resize.h"
 #include "deme_query.h"
+#include "deme_contact_inspect.h"
 #include "deme_sort.h"
 
 using namespace deme_dev;
@@ -130,6 +131,10 @@ struct deme_ctx {
     // the first query and kept, so that a script asking every frame selects once per call
     DevBuf qMark, qHits, qRecs, qCtr, qState;  // (qState: the owner records deme_query_owner_state gathers)
     uint64_t qHostBytes = 0;  // bytes the queries have copied to the host so far (deme_query_host_bytes)
+    // contact inspectors (deme_contact_inspect.h): the mask and the side counts per owner slot, the blocks' partials with the result
+    // behind them, the counts in the caller's (or global) ids; allocated by the first call and kept
+    DevBuf ciMask, ciCounts, ciPartial, ciOut;
+    std::map<std::string, int> regionBySource;  // deme_multi_inspect_contacts: a region string compiles once per slab context
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
     DevBuf geo, binLo, binN, counts, offsets, incKeys[2], incVals[2], keysRaw, keysMid, keysSorted[2], wc[2], ctr, segCtr,
@@ -1631,7 +1636,8 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->wc[0], &c->wc[1], &c->ctr,
                      &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
-                     &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr, &c->qState};
+                     &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr, &c->qState,
+                     &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -4672,6 +4678,107 @@ int deme_query_host_bytes(const deme_ctx* c, uint64_t* bytes) {
     if (!c || !bytes)
         return DEME_ERR_INVALID;
     *bytes = c->qHostBytes;
+    return DEME_OK;
+}
+
+// ---- contact inspectors: virial sum and counted sides of the current list (deme_contact_inspect.h) ----------------------------------
+namespace {
+// the refusals deme_inspect_contacts and deme_inspect_contact_counts share, in the order they make them (the last two are those of
+// deme_download_contact_records, with its words)
+int contact_inspect_refused(deme_ctx* c, const char* who, const void* out, int region, float thr) {
+    if (!out)
+        return fail(c, DEME_ERR_INVALID, "%s: null output", who);
+    if (region < -1 || region >= (int)c->regionFn.size())
+        return fail(c, DEME_ERR_INVALID, "unknown inspection region %d", region);
+    if (!std::isfinite(thr) || thr < 0.f)
+        return fail(c, DEME_ERR_INVALID, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    if (!c->record)
+        return fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
+    if (c->seeded)
+        return fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+    return DEME_OK;
+}
+// The passes of one context, enqueued on its stream.  perOwner false: the result is left in ciPartial behind the blocks' partials
+// (*res points at it).  perOwner true: the counted sides per owner SLOT are left in ciCounts.  Nothing the step reads is written.
+int contact_inspect_launch(deme_ctx* c, int region, float thr, bool perOwner, ContactSums** res) {
+    const size_t n = c->haveList ? (size_t)c->nContacts : 0, nO = c->nOwners;
+    const unsigned grid = grid_for(std::max<size_t>(std::max(n, nO), 1));
+    if (ensure(c, c->ciMask, std::max<size_t>(nO, 1) * 4) || ensure(c, c->ciPartial, ((size_t)grid + 1) * sizeof(ContactSums)) ||
+        (perOwner && ensure(c, c->ciCounts, std::max<size_t>(nO, 1) * 4)))
+        return c->lastStatus;
+    if (nO) {
+        hipLaunchKernelGGL(k_contact_owner_mask, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, c->owners.as<OwnerRec>(),
+                           (uint32_t)c->nOwnerClumps, c->dp.o2e, c->ciMask.as<float>());
+        if (region >= 0) {  // the owners' centres of mass, as deme_inspect_region tests them
+            DevParams dp = c->dp;
+            const OwnerRec* owners = c->owners.as<OwnerRec>();
+            const SphereRec* spheres = c->spheres.as<SphereRec>();
+            uint32_t nn = (uint32_t)nO, ps = 0u;
+            float identity = 0.f;
+            float* values = c->ciMask.as<float>();
+            void* args[] = {&dp, &owners, &spheres, &nn, &ps, &identity, &values};
+            HIPCK(hipModuleLaunchKernel(c->regionFn[region], grid_for(nO), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+        }
+    }
+    ContactSumArgs a{};
+    a.n = (uint32_t)n, a.nSlots = (uint32_t)nO, a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
+    a.t.spheres = c->spheres.as<SphereRec>(), a.t.tris = c->tris.as<TriRec>(), a.t.anal = c->anal.as<AnalObj>();
+    a.t.nSpheres = c->nSpheres, a.t.nTri = c->nTri, a.t.nAnal = c->nAnal, a.t.nOwners = c->nOwners;
+    a.owners = c->owners.as<OwnerRec>(), a.mask = c->ciMask.as<float>();
+    a.force = c->rec[0].as<float>(), a.cpA = c->rec[2].as<float>(), a.cpB = c->rec[3].as<float>();
+    a.thr2 = (double)thr * (double)thr;
+    a.partial = c->ciPartial.as<ContactSums>(), a.counts = c->ciCounts.as<uint32_t>();
+    if (perOwner) {
+        HIPCK(hipMemsetAsync(c->ciCounts.p, 0, std::max<size_t>(nO, 1) * 4, c->stream));
+        if (n)
+            hipLaunchKernelGGL(k_contact_sums<true>, dim3(grid_for(n)), dim3(256), 0, c->stream, a);
+        return DEME_OK;
+    }
+    hipLaunchKernelGGL(k_contact_sums<false>, dim3(grid), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_contact_sums_final, dim3(1), dim3(256), 0, c->stream, (uint32_t)grid, a.partial, a.partial + grid);
+    *res = a.partial + grid;
+    return DEME_OK;
+}
+}  // namespace
+
+int deme_inspect_contacts(deme_ctx* c, int region, float thr, DemeContactSums* out) {
+    static_assert(sizeof(DemeContactSums) == sizeof(ContactSums), "DemeContactSums is the device's ContactSums");
+    if (int rc = check_ready(c))
+        return rc;
+    if (int rc = contact_inspect_refused(c, "deme_inspect_contacts", out, region, thr))
+        return rc;
+    ContactSums* res = nullptr;
+    if (int rc = contact_inspect_launch(c, region, thr, false, &res))
+        return rc;
+    DemeContactSums h;
+    HIPCK(hipMemcpyAsync(&h, res, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->qHostBytes += sizeof h;
+    *out = h;
+    return DEME_OK;
+}
+
+int deme_inspect_contact_counts(deme_ctx* c, int region, float thr, uint32_t* perOwner, size_t cap) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (int rc = contact_inspect_refused(c, "deme_inspect_contact_counts", perOwner, region, thr))
+        return rc;
+    const size_t nO = c->nOwners;
+    if (cap < nO)
+        return fail(c, DEME_ERR_INVALID, "buffer too small: need %zu", nO);
+    if (!nO)
+        return DEME_OK;
+    if (ensure(c, c->ciOut, nO * 4))
+        return c->lastStatus;
+    if (int rc = contact_inspect_launch(c, region, thr, true, nullptr))
+        return rc;
+    hipLaunchKernelGGL(k_contact_counts_out, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, c->ciCounts.as<uint32_t>(), c->dp.o2e,
+                       (const uint32_t*)nullptr, c->ciOut.as<uint32_t>(), (uint32_t)nO);
+    std::vector<uint32_t> h(nO);
+    HIPCK(hipMemcpyAsync(h.data(), c->ciOut.p, nO * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->qHostBytes += 4ull * nO;
+    memcpy(perOwner, h.data(), nO * 4);
     return DEME_OK;
 }
 

@@ -3151,6 +3151,12 @@ class DEMSolver {
 /// clump_min_z, clump_max_absv, clump_mass, clump_volume, max_absv, clump_kinetic_energy, absv (AuxClasses.cpp:94-170);
 /// optionally limited to a region given as code (AuxClasses.cpp:205-223), compiled at the first GetValue like the
 /// reference's lazy Initialize.
+/// Two more look at the contact list (deme_inspect_contacts; not in the reference; they need the contact output content to
+/// include forces and contact points, which turns recording on):
+///   clump_virial        GetTensor(): 9 values, row-major -- the sum of arm (x) force over the force-carrying contact sides of the
+///                       clumps in the region; divided by the region's volume it is the Love-Weber stress (compression negative)
+///   clump_coordination  GetValue(): force-carrying contact sides per clump of the region (0 when it holds no clump);
+///                       GetValues(): the sides of every owner
 class DEMInspector {
   public:
     DEMInspector(DEMSolver* sys, const std::string& quantity, const std::string& region = "") : m_sys(sys), m_region_code(region) {
@@ -3161,15 +3167,23 @@ class DEMInspector {
                                                               {"max_absv", DEME_INSPECT_MAX_ABSV},
                                                               {"clump_kinetic_energy", DEME_INSPECT_CLUMP_KINETIC_ENERGY},
                                                               {"absv", DEME_INSPECT_ABSV},
-                                                              {"clump_volume", DEME_INSPECT_CLUMP_VOLUME}};
+                                                              {"clump_volume", DEME_INSPECT_CLUMP_VOLUME},
+                                                              {"clump_virial", CODE_VIRIAL},
+                                                              {"clump_coordination", CODE_COORDINATION}};
         auto it = codes.find(quantity);
         if (it == codes.end())
             throw std::runtime_error(quantity + " is not a known query type.");
         m_code = it->second;
     }
     float GetValue() {
+        if (m_code == CODE_VIRIAL)
+            throw std::runtime_error("DEMInspector(\"clump_virial\") is a tensor of 9 values: use GetTensor()");
         if (!m_sys->decomposed() && m_region < 0 && m_region_code.find_first_not_of(" \t\n") != std::string::npos)
             m_sys->check(deme_compile_region(m_sys->m_ctx, m_region_code.c_str(), &m_region));
+        if (m_code == CODE_COORDINATION) {
+            const DemeContactSums s = contact_sums();
+            return s.clumps ? (float)((double)s.sides / (double)s.clumps) : 0.f;
+        }
         float v = 0;
         if (m_sys->decomposed()) {  // every slab reduces over its OWN clumps (ghost copies are left out of inspections): max / min / sum of those
             const bool isMax = m_code == DEME_INSPECT_CLUMP_MAX_Z || m_code == DEME_INSPECT_CLUMP_MAX_ABSV || m_code == DEME_INSPECT_MAX_ABSV;
@@ -3194,7 +3208,28 @@ class DEMInspector {
         m_sys->check(deme_inspect_region(m_sys->m_ctx, m_code, m_region, &v));
         return v;
     }
+    /// the 9 values of "clump_virial", row-major
+    std::vector<double> GetTensor() {
+        if (m_code != CODE_VIRIAL)
+            throw std::runtime_error("GetTensor() is for the inspector \"clump_virial\": this one has a single value (GetValue()) or one per element (GetValues())");
+        if (!m_sys->decomposed() && m_region < 0 && m_region_code.find_first_not_of(" \t\n") != std::string::npos)
+            m_sys->check(deme_compile_region(m_sys->m_ctx, m_region_code.c_str(), &m_region));
+        const DemeContactSums s = contact_sums();
+        return std::vector<double>(s.virial, s.virial + 9);
+    }
     std::vector<float> GetValues() {
+        if (m_code == CODE_VIRIAL)
+            throw std::runtime_error("DEMInspector(\"clump_virial\") is a tensor of 9 values: use GetTensor()");
+        if (m_code == CODE_COORDINATION) {
+            if (!m_sys->decomposed() && m_region < 0 && m_region_code.find_first_not_of(" \t\n") != std::string::npos)
+                m_sys->check(deme_compile_region(m_sys->m_ctx, m_region_code.c_str(), &m_region));
+            std::vector<uint32_t> n(m_sys->m_n_owners);
+            if (m_sys->decomposed())
+                m_sys->mcheck(deme_multi_inspect_contact_counts(m_sys->m_multi, m_region_code.c_str(), DEME_TINY_FLOAT_HOST, n.data(), n.size()));
+            else
+                m_sys->check(deme_inspect_contact_counts(m_sys->m_ctx, m_region, DEME_TINY_FLOAT_HOST, n.data(), n.size()));
+            return std::vector<float>(n.begin(), n.end());
+        }
         std::vector<float> v(m_code <= DEME_INSPECT_CLUMP_MAX_ABSV ? m_sys->m_keep.sphOwner.size() : m_sys->m_n_owners);
         if (m_sys->decomposed())
             m_sys->mcheck(deme_multi_inspect_values(m_sys->m_multi, m_code, v.data(), v.size()));
@@ -3204,6 +3239,16 @@ class DEMInspector {
     }
 
   private:
+    static constexpr uint32_t CODE_VIRIAL = 100, CODE_COORDINATION = 101;  // the contact inspectors: no deme_inspect quantity
+    // (the region of a single context is compiled by the caller; a decomposed run hands the library its text)
+    DemeContactSums contact_sums() {
+        DemeContactSums s{};
+        if (m_sys->decomposed())
+            m_sys->mcheck(deme_multi_inspect_contacts(m_sys->m_multi, m_region_code.c_str(), DEME_TINY_FLOAT_HOST, &s));
+        else
+            m_sys->check(deme_inspect_contacts(m_sys->m_ctx, m_region, DEME_TINY_FLOAT_HOST, &s));
+        return s;
+    }
     DEMSolver* m_sys;
     uint32_t m_code = 0;
     std::string m_region_code;

@@ -486,6 +486,31 @@ int deme_compile_region(deme_ctx* ctx, const char* code, int* regionId);
 int deme_inspect_region(deme_ctx* ctx, uint32_t quantity, int regionId, float* out);
 /* Declared clump volumes, one per mass-property entry (reference: DEMClumpTemplate::volume, APIPrivate.cpp:730, 1849-1858). */
 int deme_upload_volumes(deme_ctx* ctx, const float* volumes, size_t n);
+/* Contact inspectors (no counterpart in the reference): the virial sum and the coordination of a bed, summed over the current
+ * contact list on the device.  The rows are those deme_download_contact_records gives.
+ *   A row is COUNTED when, in fp64, (double)fx^2 + (double)fy^2 + (double)fz^2 >= (double)forceThreshold^2, f the recorded force
+ *   (record 0; the torque-only force takes no part).
+ *   A SIDE of a counted row is counted when its owner is a clump owner of this context, is no ghost copy and lies in the region
+ *   -- the owner's centre of mass tested as deme_inspect_region tests it for the per-owner quantities; regionId -1: everywhere.
+ *   Mesh and analytical owners are never counted sides.  Side A carries +f and cpA, side B -f and cpB.
+ *   A counted side adds the outer product virial[3 * i + j] += r_i * f_j, r = R(q) cp, q the owner's stored quaternion as it stands
+ *   (not renormalised), R(q)v = v + 2w(u x v) + 2u x (u x v) with u = (qx, qy, qz); cp and q converted to fp64 first, everything
+ *   computed in fp64.  The Love-Weber stress of a region of volume V is virial / V (the caller divides); compression is negative.
+ * sides: the counted sides; clumps: the own, non-ghost clump owners in the region, with or without contacts -- the mean
+ * coordination number is sides / clumps.  The sum has a fixed order: two calls on the same state give the same bits.
+ * deme_inspect_contact_counts: the counted sides per owner in the caller's numbering (nOwners entries; 0 for owners that are no
+ * clumps or lie outside the region).
+ * Read-only: no reduction of the step is launched; the list, the prescriptions and the step's buffers stay as they are.  Only the
+ * result comes to the host: sizeof(DemeContactSums) = 88 bytes, or 4 bytes per owner; both are added to deme_query_host_bytes.
+ * Refused with DEME_ERR_INVALID and nothing written: a null output; an unknown region; cap < nOwners; a threshold that is negative
+ * or not finite; recording off or a seeded list (the messages of deme_download_contact_records). */
+typedef struct DemeContactSums {
+    double virial[9]; /* row-major */
+    uint64_t sides;
+    uint64_t clumps;
+} DemeContactSums;
+int deme_inspect_contacts(deme_ctx* ctx, int regionId, float forceThreshold, DemeContactSums* out);
+int deme_inspect_contact_counts(deme_ctx* ctx, int regionId, float forceThreshold, uint32_t* perOwner, size_t cap);
 
 /* timing of the kernels this library launched (HIP events on the context stream);
  * names: "calc_forces", "integrate", "detect"; returns avg ms per launch since last reset */
@@ -724,6 +749,18 @@ int deme_multi_download_wildcard_array(deme_multi* m, uint32_t kind, uint32_t in
 int deme_multi_upload_wildcard_array(deme_multi* m, uint32_t kind, uint32_t index, const float* in, size_t n);
 /* deme_inspect_values by GLOBAL id (per sphere for the sphere-wise quantities, per owner otherwise) */
 int deme_multi_inspect_values(deme_multi* m, uint32_t quantity, float* out, size_t cap);
+/* deme_inspect_contacts / deme_inspect_contact_counts for a decomposed run.  Every slab answers over its OWN clumps on its device
+ * (ghost sides are left out, as by every inspector): a contact across a cut gives its A side on one slab and its B side on the
+ * other, each from that slab's own record and the owner's current pose.  The host adds the slabs' results in slab order (fp64 for
+ * virial, integers for the rest); the per-owner counts are indexed by GLOBAL owner id (cap >= the global owner count) through the
+ * slabs' device books.  regionCode: a region string as deme_compile_region takes it, compiled once per slab context and kept by
+ * its text; NULL or blank: everywhere.  The call waits for the run (deme_multi_sync).  Refused as the single-context calls are --
+ * a slab without recording, or whose list is a seed as in the step after a migration, with the messages of
+ * deme_multi_download_contact_records -- and while the run evaluates every cross-cut contact once
+ * (deme_halo_group_set_cross_contacts): the slab that does not evaluate a pair holds no record of it.  Bytes, added to
+ * deme_multi_query_host_bytes: 88 per slab, or 4 per global owner and slab. */
+int deme_multi_inspect_contacts(deme_multi* m, const char* regionCode /* NULL or blank: everywhere */, float forceThreshold, DemeContactSums* out);
+int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, float forceThreshold, uint32_t* perOwnerGlobal, size_t cap);
 /* deme_add_owner_acc by GLOBAL owner id: a clump's entry goes to the slab that owns it, a replicated owner's to every slab */
 int deme_multi_add_owner_acc(deme_multi* m, uint32_t owner, uint32_t n, const float* acc, const float* angAcc);
 /* the visible HIP devices (0 and DEME_OK where there is none: what the constructors check ids against) */
