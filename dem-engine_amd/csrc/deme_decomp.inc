@@ -447,16 +447,28 @@ int deme_halo_group_build(deme_halo_group* g, const DemeParams* p, const deme_de
 }
 
 namespace {
-// rows of the slab's OWN clumps (and, on the first slab of the whole chain, of the replicated owners) between the slab's arrays and
-// the caller's arrays of the global scene
+// one slab as the host code of a decomposed run walks it
+struct SlabRef {
+    deme_halo_group* g;
+    HaloSlab* s;
+    deme_ctx* c;
+    uint32_t no;  // its number in the whole chain
+    bool first;   // the first slab of the chain: the one that answers for the replicated owners
+};
+inline SlabRef slab_ref(deme_halo_group* g, size_t k) { return {g, &g->slabs[k], g->slabs[k].ctx, g->firstSlab + (uint32_t)k, g->firstSlab + k == 0}; }
+// WHO REPORTS A ROW that is read by global id: an own clump's comes from its slab, a replicated owner's from the first slab of the
+// chain, a ghost copy's from nobody (its owner slab reports it).  k_query_owner_state (deme_query.h) applies the same rule on the device.
+inline bool slab_reports(const SlabRef& r, uint32_t ownerSlot) { return ownerSlot < r.s->geo.nOwn || (ownerSlot >= r.c->nOwnerClumps && r.first); }
+// WHO TAKES A ROW that is added once per owner (deme_multi_add_owner_acc): own clumps and replicated owners, on every slab.  (State
+// written by global id goes to every copy, ghosts included: rows_in, k_scatter_owner_state.)
+inline bool slab_takes(const SlabRef& r, uint32_t ownerSlot) { return ownerSlot < r.s->geo.nOwn || ownerSlot >= r.c->nOwnerClumps; }
+// the rows a slab reports, from the slab's arrays to the caller's arrays of the global scene
 template <class T>
-inline void rows_out(T* dst, const T* src, const std::vector<uint32_t>& gid, uint32_t nOwn, uint32_t nClumps, bool replicated) {
+inline void rows_out(T* dst, const T* src, const std::vector<uint32_t>& gid, const SlabRef& r) {
     if (!dst || !src)
         return;
-    for (uint32_t i = 0; i < nOwn; i++)
-        dst[gid[i]] = src[i];
-    if (replicated)
-        for (size_t i = nClumps; i < gid.size(); i++)
+    for (size_t i = 0; i < gid.size(); i++)
+        if (slab_reports(r, (uint32_t)i))
             dst[gid[i]] = src[i];
 }
 template <class T>
@@ -484,25 +496,23 @@ static int group_state_io(deme_halo_group* g, DemeOwnerState* glob, uint32_t nOw
         return DEME_ERR_INVALID;
     GHIP(hipSetDevice(g->device));
     for (size_t k = 0; k < g->slabs.size(); k++) {
-        HaloSlab& s = g->slabs[k];
-        deme_ctx* c = s.ctx;
+        const SlabRef r = slab_ref(g, k);
+        HaloSlab& s = *r.s;
+        deme_ctx* c = r.c;
         if (!s.geo.set)
             return gfail(g, DEME_ERR_INVALID, "state by global id: slab %zu has no books (deme_halo_group_set_slab / _build)", k);
         std::vector<uint32_t> gid(c->nOwners);
         GHIP(hipStreamSynchronize(c->stream));
-        if (c->nOwners)
-            GHIP(hipMemcpy(gid.data(), s.geo.ownerGid, (size_t)c->nOwners * 4, hipMemcpyDeviceToHost));
+        GHIP(slab_ids_host(s, gid.data(), nullptr, nullptr, nullptr));
         for (size_t i = 0; i < gid.size(); i++)
             if (gid[i] >= nOwnersGlobal)
                 return gfail(g, DEME_ERR_INVALID, "state by global id: owner id %u beyond the %u rows given (slab %zu, slot %zu of %u owners: %u own, %u + %u ghosts, %u clumps)",
                              gid[i], nOwnersGlobal, k, i, c->nOwners, s.geo.nOwn, s.geo.nGL, s.geo.nGR, c->nOwnerClumps);
         OwnerStateBuf b(std::max<size_t>(c->nOwners, 1));
-        const bool repl = g->firstSlab + k == 0;
-        const uint32_t nOwn = s.geo.nOwn, nCl = c->nOwnerClumps;
         if (down) {
             if (int rc = deme_download_owner_state(c, &b.st))
                 return gfail(g, rc, "state by global id (slab %zu): %s", k, c->err.c_str());
-#define DEME_COL(abi, T, Rec, f) rows_out(glob->abi, (const T*)b.st.abi, gid, nOwn, nCl, repl);
+#define DEME_COL(abi, T, Rec, f) rows_out(glob->abi, (const T*)b.st.abi, gid, r);
             DEME_OWNER_COLS(DEME_COL, DEME_COL, DEME_COL)
 #undef DEME_COL
         } else {
@@ -590,6 +600,7 @@ struct deme_multi {
     bool rowsValid = false;
     uint64_t qHostBytes = 0;  // bytes the by-owner queries have copied to the host (deme_multi_query_host_bytes)
     std::string err;
+    bool said = false;  // mfail has written err since multi_slabs last asked
 };
 
 int deme_scene_sizes(const deme_ctx* c, uint32_t out[4]) {
@@ -617,7 +628,7 @@ int mfail(deme_multi* m, int code, const char* fmt, ...) {
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     if (m)
-        m->err = buf;
+        m->err = buf, m->said = true;
     return code;
 }
 // the same call on every group: inline for one device, one host thread per device otherwise (each group's loop is written as the
@@ -648,6 +659,43 @@ int multi_each(deme_multi* m, F f) {
             return mfail(m, rc[i], "device %d: %s", m->devices[i], deme_halo_group_last_error(m->groups[i]));
     return DEME_OK;
 }
+// The host's walk over the slabs, one after the other in the order of the chain: f(const SlabRef&) -> int, each group's device
+// selected once.  A non-zero return ends the walk; unless f has said why through mfail, the message of the slab's context is the run's.
+template <class F>
+int multi_slabs(deme_multi* m, F f) {
+    for (auto* g : m->groups) {
+        if (hipSetDevice(g->device) != hipSuccess)
+            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+        for (size_t k = 0; k < g->slabs.size(); k++) {
+            const SlabRef r = slab_ref(g, k);
+            m->said = false;
+            if (int rc = f(r))
+                return m->said ? rc : mfail(m, rc, "%s", r.c->err.c_str());
+        }
+    }
+    return DEME_OK;
+}
+// slab number slabNo of the chain (c == null: the run holds no such slab); no device is selected
+SlabRef multi_slab(const deme_multi* m, uint32_t slabNo) {
+    const uint32_t per = m->plan->nSlabs / (uint32_t)m->groups.size();
+    deme_halo_group* g = slabNo < m->plan->nSlabs ? m->groups[slabNo / per] : nullptr;
+    return g && slabNo % per < g->slabs.size() ? slab_ref(g, slabNo % per) : SlabRef{g, nullptr, nullptr, slabNo, false};
+}
+// a slab's id books on the host (slab_ids_host), only the arrays `what` names, inside a walk of multi_slabs
+enum : unsigned { IDS_OWNER = 1, IDS_SPHERE = 2, IDS_SPHERE_OWNER = 4 };
+struct SlabIds {
+    std::vector<uint32_t> ownerGid, sphereGid, sphereOwner;  // owner slot -> global id, sphere -> global id, sphere -> owner slot
+};
+int slab_ids(deme_multi* m, const SlabRef& r, unsigned what, SlabIds& b) {
+    b.ownerGid.resize(what & IDS_OWNER ? r.c->nOwners : 0), b.sphereGid.resize(what & IDS_SPHERE ? r.c->nSpheres : 0);
+    b.sphereOwner.resize(what & IDS_SPHERE_OWNER ? r.c->nSpheres : 0);
+    if (slab_ids_host(*r.s, what & IDS_OWNER ? b.ownerGid.data() : nullptr, what & IDS_SPHERE ? b.sphereGid.data() : nullptr,
+                      what & IDS_SPHERE_OWNER ? b.sphereOwner.data() : nullptr, nullptr) != hipSuccess)
+        return mfail(m, DEME_ERR_HIP, "the slab's books could not be read");
+    return DEME_OK;
+}
+// what deme_multi_download_contact_records would say of a slab (a slab with an empty list is not asked)
+inline int slab_records_refused(const SlabRef& r) { return r.c->nContacts ? records_refused(r.c) : DEME_OK; }
 }  // namespace
 
 // one halo group per device of m->devices: a group of its own for one device, one communicator over several (every rank's
@@ -786,22 +834,18 @@ int deme_multi_num_slabs(const deme_multi* m, uint32_t* n) {
 }
 
 int deme_multi_slab_ctx(deme_multi* m, uint32_t slab, deme_ctx** ctx) {
-    if (!m || !ctx || !m->plan || slab >= m->plan->nSlabs)
-        return DEME_ERR_INVALID;
-    const uint32_t per = m->plan->nSlabs / (uint32_t)m->groups.size();
+    if (int rc = deme_multi_slab_ctx_peek(m, slab, const_cast<const deme_ctx**>(ctx)))
+        return rc;
     m->rowsValid = false;  // (the caller may change what the slab lists: the merged contact list is rebuilt on its next use)
-    return deme_halo_group_slab_ctx(m->groups[slab / per], slab % per, ctx, nullptr);
+    return DEME_OK;
 }
 
 // ... for questions that change nothing (kernel names, bin size, timers): the merged contact list stays valid
 int deme_multi_slab_ctx_peek(const deme_multi* m, uint32_t slab, const deme_ctx** ctx) {
-    if (!m || !ctx || !m->plan || slab >= m->plan->nSlabs)
+    if (!m || !ctx || !m->plan)
         return DEME_ERR_INVALID;
-    const uint32_t per = m->plan->nSlabs / (uint32_t)m->groups.size();
-    deme_ctx* c = nullptr;
-    const int rc = deme_halo_group_slab_ctx(m->groups[slab / per], slab % per, &c, nullptr);
-    *ctx = c;
-    return rc;
+    *ctx = multi_slab(m, slab).c;
+    return *ctx ? DEME_OK : DEME_ERR_INVALID;
 }
 
 int deme_multi_set_migration(deme_multi* m, uint32_t migrateEvery) {
@@ -876,19 +920,20 @@ int deme_multi_counts(deme_multi* m, DemeCounts* sum, uint64_t* clumpsMigrated) 
         return DEME_ERR_INVALID;
     if (sum) {
         *sum = DemeCounts{};
-        for (auto* g : m->groups)
-            for (auto& s : g->slabs) {
+        if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
                 DemeCounts c{};
-                if (int rc = deme_get_counts(s.ctx, &c))
-                    return mfail(m, rc, "%s", s.ctx->err.c_str());
+                if (int rc = deme_get_counts(r.c, &c))
+                    return rc;
                 sum->nContacts += c.nContacts, sum->nPrevContacts += c.nPrevContacts, sum->nBinSphereTouches += c.nBinSphereTouches;
                 sum->nActiveBins += c.nActiveBins;
                 sum->maxSpheresInBin = std::max(sum->maxSpheresInBin, c.maxSpheresInBin);
-                if (&s == &m->groups[0]->slabs[0])
+                if (r.first)
                     sum->nSteps = c.nSteps, sum->nDetections = c.nDetections;
                 if (c.lastStatus)
                     sum->lastStatus = c.lastStatus;
-            }
+                return DEME_OK;
+            }))
+            return rc;
     }
     if (clumpsMigrated)
         *clumpsMigrated = m->clumpsMigrated;
@@ -964,45 +1009,54 @@ int deme_copy_rate_probe(int device, size_t bytes, int reps, double* GBs) {
 // smaller sphere (sphere-analytical / sphere-mesh pairs go with sphere A's clump: decomp.py, _globalise_pairs) --, sphere-sphere
 // pairs as (smaller, larger) global id, rows in the canonical order of an undivided context (A, class, B).  A pair whose slab had it
 // the other way round is FLIPPED: its B -> A vector wildcards (flipMask) and its recorded force change sign, its contact points swap.
+namespace {
+// A pair in GLOBAL ids as the merged list names it: a sphere-sphere pair smaller id first (flipped: it was given the other way
+// round), the key in the list's order (A, class, B).  k_query_select (deme_query.h) builds the same on the device.
+struct GlobalPair {
+    uint64_t key;
+    uint32_t a, b;
+    bool flipped;
+};
+inline GlobalPair global_pair(uint32_t gA, uint32_t gB, uint8_t type) {
+    const bool flipped = type == DEME_SPHERE_SPHERE_CONTACT && gA > gB;
+    if (flipped)
+        std::swap(gA, gB);
+    return {merged_key(key_class_of_type(type), gA, gB), gA, gB, flipped};
+}
+// ... of a pair of a slab's list (its own sphere ids; analytical components and triangles are numbered alike on every slab)
+inline GlobalPair global_pair(const SlabIds& b, uint32_t la, uint32_t lb, uint8_t type) {
+    return global_pair(b.sphereGid[la], type == DEME_SPHERE_SPHERE_CONTACT ? b.sphereGid[lb] : lb, type);
+}
+// a slab's list in its own ids (empty vectors: an empty list)
+int slab_contacts(const SlabRef& r, std::vector<uint32_t>& a, std::vector<uint32_t>& b, std::vector<uint8_t>& t) {
+    DemeCounts cnt{};
+    if (int rc = deme_get_counts(r.c, &cnt))
+        return rc;
+    const size_t n = (size_t)cnt.nContacts;
+    a.resize(n), b.resize(n), t.resize(n);
+    return n ? deme_download_contacts(r.c, a.data(), b.data(), t.data(), nullptr, n) : DEME_OK;
+}
+}  // namespace
+
 static int multi_contact_rows(deme_multi* m, std::vector<MultiRow>& rows) {
     rows.clear();
-    uint32_t slabNo = 0;
-    for (size_t gi = 0; gi < m->groups.size(); gi++) {
-        deme_halo_group* g = m->groups[gi];
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            DemeCounts cnt{};
-            if (int rc = deme_get_counts(c, &cnt))
-                return mfail(m, rc, "%s", c->err.c_str());
-            const size_t n = (size_t)cnt.nContacts;
-            std::vector<uint32_t> a(n), b(n), sg(c->nSpheres), so(c->nSpheres);
-            std::vector<uint8_t> t(n);
-            if (n)
-                if (int rc = deme_download_contacts(c, a.data(), b.data(), t.data(), nullptr, n))
-                    return mfail(m, rc, "%s", c->err.c_str());
-            if (int rc = deme_halo_group_download_ids(g, c, nullptr, sg.data(), so.data(), nullptr))
-                return mfail(m, rc, "%s", deme_halo_group_last_error(g));
-            for (size_t i = 0; i < n; i++) {
-                MultiRow r;
-                r.slab = slabNo, r.row = (uint32_t)i, r.type = t[i], r.flipped = 0;
-                const bool ss = t[i] == DEME_SPHERE_SPHERE_CONTACT;
-                uint32_t gA = sg[a[i]], gB = ss ? sg[b[i]] : b[i];
-                uint32_t ownerOfA = so[a[i]];
-                if (ss && gA > gB) {
-                    std::swap(gA, gB);
-                    r.flipped = 1, ownerOfA = so[b[i]];
-                }
-                if (ownerOfA >= s.geo.nOwn)
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            std::vector<uint32_t> a, b;
+            std::vector<uint8_t> t;
+            SlabIds ids;
+            if (int rc = slab_contacts(r, a, b, t))
+                return rc;
+            if (int rc = slab_ids(m, r, IDS_SPHERE | IDS_SPHERE_OWNER, ids))
+                return rc;
+            for (size_t i = 0; i < t.size(); i++) {
+                const GlobalPair gp = global_pair(ids, a[i], b[i], t[i]);
+                if (ids.sphereOwner[gp.flipped ? b[i] : a[i]] >= r.s->geo.nOwn)
                     continue;  // the neighbour that owns that clump reports the pair
-                const uint64_t cls = ss ? DEME_KEY_CLASS_SS : (t[i] == DEME_SPHERE_MESH_CONTACT ? DEME_KEY_CLASS_SM : DEME_KEY_CLASS_SA);
-                r.key = ((uint64_t)gA << 34) | (cls << 31) | (uint64_t)gB;
-                rows.push_back(r);
+                rows.push_back({gp.key, r.no, (uint32_t)i, t[i], (uint8_t)gp.flipped});
             }
-            slabNo++;
-        }
-    }
+            return DEME_OK;
+        }))
+        return rc;
     std::sort(rows.begin(), rows.end(), [](const MultiRow& x, const MultiRow& y) { return x.key < y.key; });
     return DEME_OK;
 }
@@ -1018,14 +1072,6 @@ static int multi_rows_cached(deme_multi* m) {
     m->rowsAtStep = m->nSteps, m->rowsValid = true;
     return DEME_OK;
 }
-static deme_ctx* multi_ctx_of(deme_multi* m, uint32_t slab, deme_halo_group** gOut = nullptr) {
-    const uint32_t per = m->plan->nSlabs / (uint32_t)m->groups.size();
-    deme_halo_group* g = m->groups[slab / per];
-    if (gOut)
-        *gOut = g;
-    return g->slabs[slab % per].ctx;
-}
-
 int deme_multi_num_contacts(deme_multi* m, size_t* n) {
     if (!n)
         return DEME_ERR_INVALID;
@@ -1063,18 +1109,12 @@ int deme_multi_download_contact_wildcard(deme_multi* m, uint32_t w, float* out, 
         return mfail(m, DEME_ERR_INVALID, "buffer too small: need %zu", m->rows.size());
     std::vector<std::vector<float>> col(m->plan->nSlabs);
     std::vector<uint32_t> flipMask(m->plan->nSlabs, 0);
-    for (uint32_t s = 0; s < m->plan->nSlabs; s++) {
-        deme_halo_group* g = nullptr;
-        deme_ctx* c = multi_ctx_of(m, s, &g);
-        hipSetDevice(g->device);
-        col[s].resize(std::max<size_t>(c->nContacts, 1));
-        if (c->nContacts)
-            if (int rc = deme_download_contact_wildcard(c, w, col[s].data(), c->nContacts))
-                return mfail(m, rc, "%s", c->err.c_str());
-        for (auto& sl : g->slabs)
-            if (sl.ctx == c)
-                flipMask[s] = sl.geo.flipMask;
-    }
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            col[r.no].resize(std::max<size_t>(r.c->nContacts, 1));
+            flipMask[r.no] = r.s->geo.flipMask;
+            return r.c->nContacts ? deme_download_contact_wildcard(r.c, w, col[r.no].data(), r.c->nContacts) : DEME_OK;
+        }))
+        return rc;
     for (size_t i = 0; i < m->rows.size(); i++) {
         const MultiRow& r = m->rows[i];
         const float v = col[r.slab][r.row];
@@ -1095,80 +1135,60 @@ int deme_multi_upload_contact_wildcard(deme_multi* m, uint32_t w, const float* i
         return mfail(m, DEME_ERR_INVALID, "deme_multi_upload_contact_wildcard: null column for %zu rows", m->rows.size());
     if (n != m->rows.size())
         return mfail(m, DEME_ERR_INVALID, "contact wildcard column of %zu values for a merged list of %zu pairs", n, m->rows.size());
-    for (size_t gi = 0; gi < m->groups.size(); gi++) {
-        deme_halo_group* g = m->groups[gi];
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            DemeCounts cnt{};
-            if (int rc = deme_get_counts(c, &cnt))
-                return mfail(m, rc, "%s", c->err.c_str());
-            const size_t nc = (size_t)cnt.nContacts;
-            if (!nc)
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        std::vector<uint32_t> a, b;
+        std::vector<uint8_t> t;
+        SlabIds ids;
+        if (int rc = slab_contacts(r, a, b, t))
+            return rc;
+        const size_t nc = t.size();
+        if (!nc)
+            return DEME_OK;
+        std::vector<float> col(nc);
+        if (int rc = deme_download_contact_wildcard(r.c, w, col.data(), nc))
+            return rc;
+        if (int rc = slab_ids(m, r, IDS_SPHERE, ids))
+            return rc;
+        for (size_t i = 0; i < nc; i++) {
+            const GlobalPair gp = global_pair(ids, a[i], b[i], t[i]);
+            auto it = std::lower_bound(m->rows.begin(), m->rows.end(), gp.key, [](const MultiRow& x, uint64_t k) { return x.key < k; });
+            if (it == m->rows.end() || it->key != gp.key)
                 continue;
-            std::vector<uint32_t> a(nc), b(nc), sg(c->nSpheres);
-            std::vector<uint8_t> t(nc);
-            std::vector<float> col(nc);
-            if (int rc = deme_download_contacts(c, a.data(), b.data(), t.data(), nullptr, nc))
-                return mfail(m, rc, "%s", c->err.c_str());
-            if (int rc = deme_download_contact_wildcard(c, w, col.data(), nc))
-                return mfail(m, rc, "%s", c->err.c_str());
-            if (int rc = deme_halo_group_download_ids(g, c, nullptr, sg.data(), nullptr, nullptr))
-                return mfail(m, rc, "%s", deme_halo_group_last_error(g));
-            for (size_t i = 0; i < nc; i++) {
-                const bool ss = t[i] == DEME_SPHERE_SPHERE_CONTACT;
-                uint32_t gA = sg[a[i]], gB = ss ? sg[b[i]] : b[i];
-                bool flipped = false;
-                if (ss && gA > gB)
-                    std::swap(gA, gB), flipped = true;
-                const uint64_t cls = ss ? DEME_KEY_CLASS_SS : (t[i] == DEME_SPHERE_MESH_CONTACT ? DEME_KEY_CLASS_SM : DEME_KEY_CLASS_SA);
-                const uint64_t key = ((uint64_t)gA << 34) | (cls << 31) | (uint64_t)gB;
-                auto it = std::lower_bound(m->rows.begin(), m->rows.end(), key, [](const MultiRow& r, uint64_t k) { return r.key < k; });
-                if (it == m->rows.end() || it->key != key)
-                    continue;
-                const float v = in[it - m->rows.begin()];
-                col[i] = (flipped && ((s.geo.flipMask >> w) & 1u)) ? -v : v;
-            }
-            if (int rc = deme_upload_contact_wildcard(c, w, col.data(), nc))
-                return mfail(m, rc, "%s", c->err.c_str());
+            const float v = in[it - m->rows.begin()];
+            col[i] = (gp.flipped && ((r.s->geo.flipMask >> w) & 1u)) ? -v : v;
         }
-    }
-    return DEME_OK;
+        return deme_upload_contact_wildcard(r.c, w, col.data(), nc);
+    });
 }
 
 // ---- a saved list into a decomposed run (restart) and the marked (persistent) pairs, in GLOBAL ids ------------------------------------
 // A pair goes to every slab that holds both of its geometries and owns at least one of them, in the slab's own ids, smaller sphere
 // first, B -> A vector wildcards (the build's flipMask) with the slab's sign.
 namespace {
-struct SlabBooks {
-    std::vector<uint32_t> inv;    // global sphere id -> the slab's, or ~0
-    std::vector<uint32_t> owner;  // the slab's sphere -> its owner slot
-    std::vector<uint32_t> sg;     // the slab's sphere -> global id
+struct SlabSpheres : SlabIds {
+    std::vector<uint32_t> inv;  // global sphere id -> the slab's, or ~0
 };
-int slab_books(deme_multi* m, deme_halo_group* g, HaloSlab& s, SlabBooks& b) {
-    deme_ctx* c = s.ctx;
-    b.sg.assign(c->nSpheres, 0), b.owner.assign(c->nSpheres, 0);
-    if (int rc = deme_halo_group_download_ids(g, c, nullptr, b.sg.data(), b.owner.data(), nullptr))
-        return mfail(m, rc, "%s", deme_halo_group_last_error(g));
+int slab_spheres(deme_multi* m, const SlabRef& r, SlabSpheres& b) {
+    if (int rc = slab_ids(m, r, IDS_SPHERE | IDS_SPHERE_OWNER, b))
+        return rc;
     b.inv.assign(m->plan->nSpheresGlobal, 0xFFFFFFFFu);
-    for (uint32_t i = 0; i < c->nSpheres; i++)
-        if (b.sg[i] < b.inv.size())
-            b.inv[b.sg[i]] = i;
+    for (uint32_t i = 0; i < r.c->nSpheres; i++)
+        if (b.sphereGid[i] < b.inv.size())
+            b.inv[b.sphereGid[i]] = i;
     return DEME_OK;
 }
 // the slab's form of a global pair; false: the slab does not hold it
-inline bool slab_pair(const SlabBooks& b, const HaloSlab& s, uint32_t gA, uint32_t gB, uint8_t type, uint32_t& la, uint32_t& lb, bool& flipped) {
+inline bool slab_pair(const SlabSpheres& b, const HaloSlab& s, uint32_t gA, uint32_t gB, uint8_t type, uint32_t& la, uint32_t& lb, bool& flipped) {
     flipped = false;
     if (gA >= b.inv.size() || (la = b.inv[gA]) == 0xFFFFFFFFu)
         return false;
     if (type != DEME_SPHERE_SPHERE_CONTACT) {
         lb = gB;  // (analytical components and triangles are numbered alike on every slab)
-        return b.owner[la] < s.geo.nOwn;
+        return b.sphereOwner[la] < s.geo.nOwn;
     }
     if (gB >= b.inv.size() || (lb = b.inv[gB]) == 0xFFFFFFFFu)
         return false;
-    if (b.owner[la] >= s.geo.nOwn && b.owner[lb] >= s.geo.nOwn)
+    if (b.sphereOwner[la] >= s.geo.nOwn && b.sphereOwner[lb] >= s.geo.nOwn)
         return false;  // two ghosts: their owners' pair
     if (la > lb)
         std::swap(la, lb), flipped = true;
@@ -1182,39 +1202,30 @@ int deme_multi_seed_contacts(deme_multi* m, const uint32_t* idA, const uint32_t*
     if (int rc = deme_multi_sync(m))
         return rc;
     m->rowsValid = false;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            const uint32_t nW = c->hp.nContactWildcards;
-            if (n && nW && !wildcards)
-                return mfail(m, DEME_ERR_INVALID, "deme_multi_seed_contacts: the model keeps %u contact wildcards, none given", nW);
-            SlabBooks b;
-            if (int rc = slab_books(m, g, s, b))
-                return rc;
-            std::vector<uint32_t> a, bb;
-            std::vector<uint8_t> t;
-            std::vector<float> w;
-            for (size_t i = 0; i < n; i++) {
-                uint32_t la, lb;
-                bool flipped;
-                const uint32_t gA = (type[i] == DEME_SPHERE_SPHERE_CONTACT && idA[i] > idB[i]) ? idB[i] : idA[i];
-                const uint32_t gB = (type[i] == DEME_SPHERE_SPHERE_CONTACT && idA[i] > idB[i]) ? idA[i] : idB[i];
-                const bool given = gA != idA[i];  // (a pair given larger id first: its vector wildcards are of that order)
-                if (!slab_pair(b, s, gA, gB, type[i], la, lb, flipped))
-                    continue;
-                a.push_back(la), bb.push_back(lb), t.push_back(type[i]);
-                for (uint32_t k = 0; k < nW; k++) {
-                    const float v = wildcards[i * nW + k];
-                    w.push_back(((flipped != given) && ((s.geo.flipMask >> k) & 1u)) ? -v : v);
-                }
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        const uint32_t nW = r.c->hp.nContactWildcards;
+        if (n && nW && !wildcards)
+            return mfail(m, DEME_ERR_INVALID, "deme_multi_seed_contacts: the model keeps %u contact wildcards, none given", nW);
+        SlabSpheres b;
+        if (int rc = slab_spheres(m, r, b))
+            return rc;
+        std::vector<uint32_t> a, bb;
+        std::vector<uint8_t> t;
+        std::vector<float> w;
+        for (size_t i = 0; i < n; i++) {
+            uint32_t la, lb;
+            bool flipped;
+            const GlobalPair gp = global_pair(idA[i], idB[i], type[i]);  // (flipped: given larger id first, its vector wildcards are of that order)
+            if (!slab_pair(b, *r.s, gp.a, gp.b, type[i], la, lb, flipped))
+                continue;
+            a.push_back(la), bb.push_back(lb), t.push_back(type[i]);
+            for (uint32_t k = 0; k < nW; k++) {
+                const float v = wildcards[i * nW + k];
+                w.push_back(((flipped != gp.flipped) && ((r.s->geo.flipMask >> k) & 1u)) ? -v : v);
             }
-            if (int rc = deme_seed_contacts(c, a.data(), bb.data(), t.data(), nW ? w.data() : nullptr, a.size()))
-                return mfail(m, rc, "%s", c->err.c_str());
         }
-    }
-    return DEME_OK;
+        return deme_seed_contacts(r.c, a.data(), bb.data(), t.data(), nW ? w.data() : nullptr, a.size());
+    });
 }
 
 // the marked pairs of every slab, once each, in global ids (sphere-sphere pairs smaller id first), ascending
@@ -1222,30 +1233,26 @@ static int multi_persistent(deme_multi* m, std::vector<std::array<uint32_t, 3>>&
     out.clear();
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
             size_t nP = 0;
-            if (int rc = deme_num_persistent_contacts(c, &nP))
-                return mfail(m, rc, "%s", c->err.c_str());
+            if (int rc = deme_num_persistent_contacts(r.c, &nP))
+                return rc;
             if (!nP)
-                continue;
-            std::vector<uint32_t> a(nP), b(nP), sg(c->nSpheres);
+                return DEME_OK;
+            std::vector<uint32_t> a(nP), b(nP);
             std::vector<uint8_t> t(nP);
-            if (int rc = deme_download_persistent_contacts(c, a.data(), b.data(), t.data(), nP))
-                return mfail(m, rc, "%s", c->err.c_str());
-            if (int rc = deme_halo_group_download_ids(g, c, nullptr, sg.data(), nullptr, nullptr))
-                return mfail(m, rc, "%s", deme_halo_group_last_error(g));
+            SlabIds ids;
+            if (int rc = deme_download_persistent_contacts(r.c, a.data(), b.data(), t.data(), nP))
+                return rc;
+            if (int rc = slab_ids(m, r, IDS_SPHERE, ids))
+                return rc;
             for (size_t i = 0; i < nP; i++) {
-                uint32_t gA = sg[a[i]], gB = t[i] == DEME_SPHERE_SPHERE_CONTACT ? sg[b[i]] : b[i];
-                if (t[i] == DEME_SPHERE_SPHERE_CONTACT && gA > gB)
-                    std::swap(gA, gB);
-                out.push_back({gA, gB, (uint32_t)t[i]});
+                const GlobalPair gp = global_pair(ids, a[i], b[i], t[i]);
+                out.push_back({gp.a, gp.b, (uint32_t)t[i]});
             }
-        }
-    }
+            return DEME_OK;
+        }))
+        return rc;
     std::sort(out.begin(), out.end());
     out.erase(std::unique(out.begin(), out.end()), out.end());
     return DEME_OK;
@@ -1282,27 +1289,21 @@ int deme_multi_upload_persistent_contacts(deme_multi* m, const uint32_t* idA, co
         return DEME_ERR_INVALID;
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            SlabBooks b;
-            if (int rc = slab_books(m, g, s, b))
-                return rc;
-            std::vector<uint32_t> a, bb;
-            std::vector<uint8_t> t;
-            for (size_t i = 0; i < n; i++) {
-                uint32_t la, lb;
-                bool flipped;
-                const bool ss = type[i] == DEME_SPHERE_SPHERE_CONTACT;
-                if (slab_pair(b, s, ss ? std::min(idA[i], idB[i]) : idA[i], ss ? std::max(idA[i], idB[i]) : idB[i], type[i], la, lb, flipped))
-                    a.push_back(la), bb.push_back(lb), t.push_back(type[i]);
-            }
-            if (int rc = deme_upload_persistent_contacts(s.ctx, a.data(), bb.data(), t.data(), a.size()))
-                return mfail(m, rc, "%s", s.ctx->err.c_str());
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        SlabSpheres b;
+        if (int rc = slab_spheres(m, r, b))
+            return rc;
+        std::vector<uint32_t> a, bb;
+        std::vector<uint8_t> t;
+        for (size_t i = 0; i < n; i++) {
+            uint32_t la, lb;
+            bool flipped;
+            const GlobalPair gp = global_pair(idA[i], idB[i], type[i]);
+            if (slab_pair(b, *r.s, gp.a, gp.b, type[i], la, lb, flipped))
+                a.push_back(la), bb.push_back(lb), t.push_back(type[i]);
         }
-    }
-    return DEME_OK;
+        return deme_upload_persistent_contacts(r.c, a.data(), bb.data(), t.data(), a.size());
+    });
 }
 // deme_mark_persistent_contacts on every slab (the qualification is by families: the same rule everywhere)
 int deme_multi_mark_persistent_contacts(deme_multi* m, int mode, uint32_t N1, uint32_t N2, int mark) {
@@ -1310,14 +1311,7 @@ int deme_multi_mark_persistent_contacts(deme_multi* m, int mode, uint32_t N1, ui
         return DEME_ERR_INVALID;
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs)
-            if (int rc = deme_mark_persistent_contacts(s.ctx, mode, N1, N2, mark))
-                return mfail(m, rc, "%s", s.ctx->err.c_str());
-    }
-    return DEME_OK;
+    return multi_slabs(m, [&](const SlabRef& r) -> int { return deme_mark_persistent_contacts(r.c, mode, N1, N2, mark); });
 }
 
 int deme_multi_download_contact_records(deme_multi* m, float* force, float* torqueOnly, float* cpA, float* cpB, size_t cap) {
@@ -1326,16 +1320,12 @@ int deme_multi_download_contact_records(deme_multi* m, float* force, float* torq
     if (cap < m->rows.size())
         return mfail(m, DEME_ERR_INVALID, "buffer too small: need %zu", m->rows.size());
     std::vector<std::vector<float>> f(m->plan->nSlabs), t(m->plan->nSlabs), a(m->plan->nSlabs), b(m->plan->nSlabs);
-    for (uint32_t s = 0; s < m->plan->nSlabs; s++) {
-        deme_halo_group* g = nullptr;
-        deme_ctx* c = multi_ctx_of(m, s, &g);
-        hipSetDevice(g->device);
-        const size_t n = std::max<size_t>(c->nContacts, 1);
-        f[s].resize(3 * n), t[s].resize(3 * n), a[s].resize(3 * n), b[s].resize(3 * n);
-        if (c->nContacts)
-            if (int rc = deme_download_contact_records(c, f[s].data(), t[s].data(), a[s].data(), b[s].data(), c->nContacts))
-                return mfail(m, rc, "%s", c->err.c_str());
-    }
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            const size_t s = r.no, n = std::max<size_t>(r.c->nContacts, 1);
+            f[s].resize(3 * n), t[s].resize(3 * n), a[s].resize(3 * n), b[s].resize(3 * n);
+            return r.c->nContacts ? deme_download_contact_records(r.c, f[s].data(), t[s].data(), a[s].data(), b[s].data(), r.c->nContacts) : DEME_OK;
+        }))
+        return rc;
     for (size_t i = 0; i < m->rows.size(); i++) {
         const MultiRow& r = m->rows[i];
         const float sgn = r.flipped ? -1.f : 1.f;  // (the recorded force acts on A: the other body takes the opposite one)
@@ -1359,23 +1349,25 @@ int deme_multi_download_contact_records(deme_multi* m, float* force, float* torq
 // the host sorts the hits of all slabs by the merged key (a pair is reported once, so keys are unique).  The cached merged rows
 // are neither used nor invalidated.
 namespace {
-inline SlabBooksDev slab_books(const HaloSlab& s, uint32_t nOwnersGlobal) {
+inline SlabBooksDev slab_books_dev(const HaloSlab& s, uint32_t nOwnersGlobal) {
     SlabBooksDev bk{};
     bk.sphereGid = (const uint32_t*)s.geo.sphereGid, bk.ownerGid = (const uint32_t*)s.geo.ownerGid;
     bk.nOwn = s.geo.nOwn, bk.nOwnersGlobal = nOwnersGlobal;
     return bk;
 }
 // one slab's owners of a question: their records gathered into the context's scratch (at most ids.size() of them), the count in nHit
-int slab_query_state(deme_ctx* c, const HaloSlab& s, uint32_t nOwnersGlobal, bool takeReplicated, size_t nIds, uint32_t& nHit) {
+int slab_query_state(const SlabRef& r, uint32_t nOwnersGlobal, size_t nIds, uint32_t& nHit) {
+    deme_ctx* c = r.c;
     nHit = 0;
     if (!c->nOwners)
         return DEME_OK;
     if (ensure(c, c->qState, nIds * sizeof(OwnerRec)))
         return c->lastStatus;
-    const SlabBooksDev bk = slab_books(s, nOwnersGlobal);
+    const SlabBooksDev bk = slab_books_dev(*r.s, nOwnersGlobal);
     HIPCK(hipMemsetAsync(c->qCtr.p, 0, 4, c->stream));
+    // (takeReplicated = r.first: the kernel applies slab_reports to the slots it visits)
     hipLaunchKernelGGL(k_query_owner_state, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->nOwners, c->owners.as<OwnerRec>(),
-                       (const uint32_t*)nullptr, c->dp.o2e, bk, c->nOwnerClumps, takeReplicated ? 1u : 0u, c->qMark.as<uint8_t>(),
+                       (const uint32_t*)nullptr, c->dp.o2e, bk, c->nOwnerClumps, r.first ? 1u : 0u, c->qMark.as<uint8_t>(),
                        c->qState.as<OwnerRec>(), (uint32_t)std::min<size_t>(c->qState.bytes / sizeof(OwnerRec), 0xFFFFFFFFu),
                        c->qCtr.as<uint32_t>());
     HIPCK(hipMemcpyAsync(&nHit, c->qCtr.p, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1400,51 +1392,32 @@ int deme_multi_query_owner_contacts(deme_multi* m, const uint32_t* ownerIds, siz
         return mfail(m, rc, "%s", msg);
     if (int rc = deme_multi_sync(m))
         return rc;
-    if (withRecords)  // what deme_multi_download_contact_records would say, slab by slab
-        for (auto* g : m->groups)
-            for (auto& s : g->slabs) {
-                deme_ctx* c = s.ctx;
-                if (!c->nContacts)
-                    continue;
-                int rc = DEME_OK;  // (fail() writes c->err: called on its own, before the message is read)
-                if (!c->record)
-                    rc = fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
-                else if (c->seeded)
-                    rc = fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
-                if (rc)
-                    return mfail(m, rc, "%s", c->err.c_str());
-            }
+    if (withRecords)
+        if (int rc = multi_slabs(m, slab_records_refused))
+            return rc;
     std::vector<uint32_t> ids(ownerIds, ownerIds + nOwners);
     std::sort(ids.begin(), ids.end());
     ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    struct Part {
-        deme_halo_group* g;
-        deme_ctx* c;
-        uint32_t nHit;
-    };
-    std::vector<Part> parts;
+    std::vector<uint32_t> nHit(m->plan->nSlabs, 0);
     size_t total = 0;
     if (!ids.empty())
-        for (auto* g : m->groups) {
-            if (hipSetDevice(g->device) != hipSuccess)
-                return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-            for (auto& s : g->slabs) {
-                deme_ctx* c = s.ctx;
-                if (!s.geo.set)
+        if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+                deme_ctx* c = r.c;
+                if (!r.s->geo.set)
                     return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_contacts: a slab has no books (deme_halo_group_set_slab / _build)");
-                uint32_t nHit = 0, passes = 0;
+                uint32_t passes = 0;
                 if (c->haveList && c->nContacts) {
-                    const SlabBooksDev bk = slab_books(s, nOG);
+                    const SlabBooksDev bk = slab_books_dev(*r.s, nOG);
                     if (int rc = query_mark(c, ids, std::max<size_t>(nOG, 1)))
-                        return mfail(m, rc, "%s", c->err.c_str());
-                    if (int rc = query_select(c, &bk, "deme_multi_query_owner_contacts", withRecords, nHit, passes))
-                        return mfail(m, rc, "%s", c->err.c_str());
+                        return rc;
+                    if (int rc = query_select(c, &bk, "deme_multi_query_owner_contacts", withRecords, nHit[r.no], passes))
+                        return rc;
                 }
                 m->qHostBytes += 4ull * passes;  // (a slab with an empty list is not asked)
-                parts.push_back({g, c, nHit});
-                total += nHit;
-            }
-        }
+                total += nHit[r.no];
+                return DEME_OK;
+            }))
+            return rc;
     *nOut = total;
     if (cap < total)
         return mfail(m, DEME_ERR_INVALID, "buffer too small: need %zu", total);
@@ -1454,17 +1427,17 @@ int deme_multi_query_owner_contacts(deme_multi* m, const uint32_t* ownerIds, siz
     std::vector<float> r(withRecords ? total * 12 : 0);
     std::vector<const deme_ctx*> ctxOf(total);
     size_t at = 0;
-    for (const Part& p : parts) {
-        if (!p.nHit)
-            continue;
-        if (hipSetDevice(p.g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", p.g->device);
-        if (int rc = query_fetch(p.c, p.nHit, withRecords, h.data() + at, withRecords ? r.data() + 12 * at : nullptr))
-            return mfail(m, rc, "%s", p.c->err.c_str());
-        for (uint32_t i = 0; i < p.nHit; i++)
-            ctxOf[at + i] = p.c;
-        at += p.nHit;
-    }
+    if (int rc = multi_slabs(m, [&](const SlabRef& sl) -> int {
+            const uint32_t n = nHit[sl.no];
+            if (!n)
+                return DEME_OK;
+            if (int rc = query_fetch(sl.c, n, withRecords, h.data() + at, withRecords ? r.data() + 12 * at : nullptr))
+                return rc;
+            std::fill_n(ctxOf.begin() + at, n, sl.c);
+            at += n;
+            return DEME_OK;
+        }))
+        return rc;
     m->qHostBytes += (uint64_t)total * (sizeof(QueryHit) + (withRecords ? 48 : 0));
     query_emit(h, r, true, [&](uint32_t hit) { return ctxOf[hit]; }, QueryRows{idA, idB, type, ownerA, ownerB, side, {force, torqueOnly, cpA, cpB}});
     return DEME_OK;
@@ -1500,27 +1473,23 @@ int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_
             ids.push_back(pr.first);
     size_t found = 0;
     std::vector<OwnerRec> h;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (size_t k = 0; k < g->slabs.size(); k++) {
-            HaloSlab& s = g->slabs[k];
-            deme_ctx* c = s.ctx;
-            if (!s.geo.set)
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            deme_ctx* c = r.c;
+            if (!r.s->geo.set)
                 return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: a slab has no books (deme_halo_group_set_slab / _build)");
             uint32_t nHit = 0;
             if (int rc = query_mark(c, ids, std::max<size_t>(nOG, 1)))
-                return mfail(m, rc, "%s", c->err.c_str());
-            if (int rc = slab_query_state(c, s, nOG, g->firstSlab + k == 0, ids.size(), nHit))
-                return mfail(m, rc, "%s", c->err.c_str());
+                return rc;
+            if (int rc = slab_query_state(r, nOG, ids.size(), nHit))
+                return rc;
             m->qHostBytes += 4;
             if (nHit > ids.size())
                 return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: a slab holds %u owners for %zu ids", nHit, ids.size());
             if (!nHit)
-                continue;
+                return DEME_OK;
             h.resize(nHit);
             if (int rc = slab_query_fetch_state(c, nHit, h.data()))
-                return mfail(m, rc, "%s", c->err.c_str());
+                return rc;
             m->qHostBytes += (uint64_t)nHit * sizeof(OwnerRec);
             for (uint32_t i = 0; i < nHit; i++) {
                 uint32_t gid;
@@ -1530,8 +1499,9 @@ int deme_multi_query_owner_state(deme_multi* m, const uint32_t* globalIds, size_
                     owner_state_row(out, it->second, h[i]);
                 found++;
             }
-        }
-    }
+            return DEME_OK;
+        }))
+        return rc;
     if (found != ids.size())
         return mfail(m, DEME_ERR_INVALID, "deme_multi_query_owner_state: %zu of %zu owners were found on the slabs", found, ids.size());
     return DEME_OK;
@@ -1551,10 +1521,10 @@ int deme_multi_scatter_owner_state(deme_multi* m, const uint32_t* globalIds, siz
     const uint32_t mask = owner_state_mask(in);
     if (!n || !mask)
         return DEME_OK;
-    for (auto* g : m->groups)
-        for (auto& s : g->slabs)
-            if (!s.geo.set)
-                return mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: a slab has no books (deme_halo_group_set_slab / _build)");
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            return r.s->geo.set ? DEME_OK : mfail(m, DEME_ERR_INVALID, "deme_multi_scatter_owner_state: a slab has no books (deme_halo_group_set_slab / _build)");
+        }))
+        return rc;
     if (int rc = deme_multi_sync(m))
         return rc;
     std::vector<uint32_t> ids(n);
@@ -1564,19 +1534,14 @@ int deme_multi_scatter_owner_state(deme_multi* m, const uint32_t* globalIds, siz
         patch[i] = owner_state_patch(in, sorted[i].second);
     }
     m->rowsValid = false;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            if (int rc = check_ready(c))
-                return mfail(m, rc, "%s", c->err.c_str());
-            if (int rc = launch_owner_scatter(c, in, ids, patch, mask, true, (const uint32_t*)s.geo.ownerGid))
-                return mfail(m, rc, "%s", c->err.c_str());
-            m->qHostBytes += (uint64_t)n * (4 + sizeof(OwnerRec));
-        }
-    }
-    return DEME_OK;
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        if (int rc = check_ready(r.c))
+            return rc;
+        if (int rc = launch_owner_scatter(r.c, in, ids, patch, mask, true, (const uint32_t*)r.s->geo.ownerGid))
+            return rc;
+        m->qHostBytes += (uint64_t)n * (4 + sizeof(OwnerRec));
+        return DEME_OK;
+    });
 }
 
 // accelerations a script adds for the next step (deme_add_owner_acc), by GLOBAL owner id: a clump's go to the slab that owns it, a
@@ -1588,34 +1553,28 @@ int deme_multi_add_owner_acc(deme_multi* m, uint32_t owner, uint32_t n, const fl
         return mfail(m, DEME_ERR_INVALID, "deme_multi_add_owner_acc: owners [%u, %u) out of range", owner, owner + n);
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            std::vector<uint32_t> gid(c->nOwners);
-            if (c->nOwners && hipMemcpy(gid.data(), s.geo.ownerGid, (size_t)c->nOwners * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return mfail(m, DEME_ERR_HIP, "the slab's books could not be read");
-            auto wanted = [&](uint32_t i) {
-                const bool mine = i < s.geo.nOwn || i >= c->nOwnerClumps;  // own clumps and replicated owners; ghosts are their owner slab's
-                return mine && gid[i] >= owner && gid[i] < owner + n;
-            };
-            for (uint32_t i = 0; i < c->nOwners;) {  // runs of slots whose global ids run along: one call (one copy, one wait) per run
-                if (!wanted(i)) {
-                    i++;
-                    continue;
-                }
-                uint32_t j = i + 1;
-                while (j < c->nOwners && wanted(j) && gid[j] == gid[j - 1] + 1u)
-                    j++;
-                const uint32_t k = gid[i] - owner;
-                if (int rc = deme_add_owner_acc(c, i, j - i, acc ? acc + 3 * (size_t)k : nullptr, angAcc ? angAcc + 3 * (size_t)k : nullptr))
-                    return mfail(m, rc, "%s", c->err.c_str());
-                i = j;
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        deme_ctx* c = r.c;
+        SlabIds ids;
+        if (int rc = slab_ids(m, r, IDS_OWNER, ids))
+            return rc;
+        const std::vector<uint32_t>& gid = ids.ownerGid;
+        auto wanted = [&](uint32_t i) { return slab_takes(r, i) && gid[i] >= owner && gid[i] < owner + n; };  // (ghosts are their owner slab's)
+        for (uint32_t i = 0; i < c->nOwners;) {  // runs of slots whose global ids run along: one call (one copy, one wait) per run
+            if (!wanted(i)) {
+                i++;
+                continue;
             }
+            uint32_t j = i + 1;
+            while (j < c->nOwners && wanted(j) && gid[j] == gid[j - 1] + 1u)
+                j++;
+            const uint32_t k = gid[i] - owner;
+            if (int rc = deme_add_owner_acc(c, i, j - i, acc ? acc + 3 * (size_t)k : nullptr, angAcc ? angAcc + 3 * (size_t)k : nullptr))
+                return rc;
+            i = j;
         }
-    }
-    return DEME_OK;
+        return DEME_OK;
+    });
 }
 
 // a user model's wildcard arrays by GLOBAL id (kind 0: per owner, 1: per sphere): a row comes from the slab that owns the clump (a
@@ -1631,67 +1590,48 @@ static int multi_wc_io(deme_multi* m, uint32_t kind, uint32_t index, float* glob
         return mfail(m, DEME_ERR_INVALID, "wildcard array of kind %u of a decomposed run holds %zu values, %zu given", kind, want, n);
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (size_t gi = 0; gi < m->groups.size(); gi++) {
-        deme_halo_group* g = m->groups[gi];
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (size_t k = 0; k < g->slabs.size(); k++) {
-            HaloSlab& s = g->slabs[k];
-            deme_ctx* c = s.ctx;
-            if (kind >= 2) {  // replicated geometry: written everywhere; read from the first slab, and the others must agree with it
-                if (down && (gi || k)) {
-                    // A model that WRITES these arrays from its contacts (Models.h:345-360: triWildcards, analWildcards) leaves a
-                    // different part in every slab -- a triangle's contacts are evaluated by the slabs that own the spheres.  There is no
-                    // rule that merges parts of an arbitrary user quantity (a sum? a maximum? the last writer?), so a run whose slabs
-                    // disagree says so instead of handing back one slab's part as if it were the whole.
-                    std::vector<float> other(std::max<size_t>(n, 1));
-                    if (int rc = deme_download_wildcard_array(c, kind, index, other.data(), n))
-                        return mfail(m, rc, "%s", c->err.c_str());
-                    if (n && memcmp(other.data(), glob, n * sizeof(float)) != 0)
-                        return mfail(m, DEME_ERR_INVALID,
-                                     "%s wildcard array %u differs between the slabs of this decomposed run: the force model writes it, and each slab "
-                                     "holds the part of the contacts it evaluated (read the parts through deme_multi_slab_ctx + "
-                                     "deme_download_wildcard_array and combine them as the quantity asks)",
-                                     kind == 2 ? "triangle" : "analytical-geometry", index);
-                    continue;
-                }
-                if (int rc = down ? deme_download_wildcard_array(c, kind, index, glob, n) : deme_upload_wildcard_array(c, kind, index, glob, n))
-                    return mfail(m, rc, "%s", c->err.c_str());
-                continue;
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        deme_ctx* c = r.c;
+        if (kind >= 2) {  // replicated geometry: written everywhere; read from the first slab, and the others must agree with it
+            if (down && !r.first) {
+                // A model that WRITES these arrays from its contacts (Models.h:345-360: triWildcards, analWildcards) leaves a
+                // different part in every slab -- a triangle's contacts are evaluated by the slabs that own the spheres.  There is no
+                // rule that merges parts of an arbitrary user quantity (a sum? a maximum? the last writer?), so a run whose slabs
+                // disagree says so instead of handing back one slab's part as if it were the whole.
+                std::vector<float> other(std::max<size_t>(n, 1));
+                if (int rc = deme_download_wildcard_array(c, kind, index, other.data(), n))
+                    return rc;
+                if (n && memcmp(other.data(), glob, n * sizeof(float)) != 0)
+                    return mfail(m, DEME_ERR_INVALID,
+                                 "%s wildcard array %u differs between the slabs of this decomposed run: the force model writes it, and each slab "
+                                 "holds the part of the contacts it evaluated (read the parts through deme_multi_slab_ctx + "
+                                 "deme_download_wildcard_array and combine them as the quantity asks)",
+                                 kind == 2 ? "triangle" : "analytical-geometry", index);
+                return DEME_OK;
             }
-            const size_t nLoc = kind == 0 ? c->nOwners : c->nSpheres;
-            std::vector<uint32_t> gid(nLoc);
-            std::vector<float> loc(std::max<size_t>(nLoc, 1));
-            if (nLoc && hipMemcpy(gid.data(), kind == 0 ? s.geo.ownerGid : s.geo.sphereGid, nLoc * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return mfail(m, DEME_ERR_HIP, "the slab's books could not be read");
-            for (size_t i = 0; i < nLoc; i++)
-                if (gid[i] >= want)
-                    return mfail(m, DEME_ERR_INVALID, "wildcard array by global id: slab %zu slot %zu names id %u of %zu", g->firstSlab + k, i, gid[i], want);
-            if (!down) {
-                for (size_t i = 0; i < nLoc; i++)
-                    loc[i] = glob[gid[i]];
-                if (int rc = deme_upload_wildcard_array(c, kind, index, loc.data(), nLoc))
-                    return mfail(m, rc, "%s", c->err.c_str());
-                continue;
-            }
-            if (int rc = deme_download_wildcard_array(c, kind, index, loc.data(), nLoc))
-                return mfail(m, rc, "%s", c->err.c_str());
-            const bool first = g->firstSlab + k == 0;
-            if (kind == 0) {
-                for (size_t i = 0; i < nLoc; i++)
-                    if (i < s.geo.nOwn || (i >= c->nOwnerClumps && first))
-                        glob[gid[i]] = loc[i];
-            } else {
-                std::vector<SphereRec> sr(nLoc);
-                if (nLoc && hipMemcpy(sr.data(), c->spheres.p, nLoc * sizeof(SphereRec), hipMemcpyDeviceToHost) != hipSuccess)
-                    return mfail(m, DEME_ERR_HIP, "the slab's spheres could not be read");
-                for (size_t i = 0; i < nLoc; i++)
-                    if (sr[i].owner < s.geo.nOwn || (sr[i].owner >= c->nOwnerClumps && first))
-                        glob[gid[i]] = loc[i];
-            }
+            return down ? deme_download_wildcard_array(c, kind, index, glob, n) : deme_upload_wildcard_array(c, kind, index, glob, n);
         }
-    }
-    return DEME_OK;
+        const size_t nLoc = kind == 0 ? c->nOwners : c->nSpheres;
+        SlabIds ids;
+        if (int rc = slab_ids(m, r, kind == 0 ? IDS_OWNER : down ? IDS_SPHERE | IDS_SPHERE_OWNER : IDS_SPHERE, ids))
+            return rc;
+        const std::vector<uint32_t>& gid = kind == 0 ? ids.ownerGid : ids.sphereGid;
+        std::vector<float> loc(std::max<size_t>(nLoc, 1));
+        for (size_t i = 0; i < nLoc; i++)
+            if (gid[i] >= want)
+                return mfail(m, DEME_ERR_INVALID, "wildcard array by global id: slab %zu slot %zu names id %u of %zu", (size_t)r.no, i, gid[i], want);
+        if (!down) {
+            for (size_t i = 0; i < nLoc; i++)
+                loc[i] = glob[gid[i]];
+            return deme_upload_wildcard_array(c, kind, index, loc.data(), nLoc);
+        }
+        if (int rc = deme_download_wildcard_array(c, kind, index, loc.data(), nLoc))
+            return rc;
+        for (size_t i = 0; i < nLoc; i++)
+            if (slab_reports(r, kind == 0 ? (uint32_t)i : ids.sphereOwner[i]))
+                glob[gid[i]] = loc[i];
+        return DEME_OK;
+    });
 }
 int deme_multi_download_wildcard_array(deme_multi* m, uint32_t kind, uint32_t index, float* out, size_t cap) {
     return multi_wc_io(m, kind, index, out, cap, true);
@@ -1711,29 +1651,21 @@ int deme_multi_inspect_values(deme_multi* m, uint32_t q, float* out, size_t cap)
         return mfail(m, DEME_ERR_INVALID, "buffer too small: need %zu", want);
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (size_t k = 0; k < g->slabs.size(); k++) {
-            HaloSlab& s = g->slabs[k];
-            deme_ctx* c = s.ctx;
-            const size_t nLoc = perSphere ? c->nSpheres : c->nOwners;
-            std::vector<float> loc(std::max<size_t>(nLoc, 1));
-            if (int rc = deme_inspect_values(c, q, loc.data(), nLoc))
-                return mfail(m, rc, "%s", c->err.c_str());
-            std::vector<uint32_t> og(c->nOwners), sg(c->nSpheres), so(c->nSpheres);
-            if (int rc = deme_halo_group_download_ids(g, c, og.data(), sg.data(), so.data(), nullptr))
-                return mfail(m, rc, "%s", deme_halo_group_last_error(g));
-            const bool first = g->firstSlab + k == 0;
-            for (size_t i = 0; i < nLoc; i++) {
-                const uint32_t o = perSphere ? so[i] : (uint32_t)i;
-                const uint32_t gid = perSphere ? sg[i] : og[i];
-                if ((o < s.geo.nOwn || (o >= c->nOwnerClumps && first)) && gid < want)
-                    out[gid] = loc[i];
-            }
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        const size_t nLoc = perSphere ? r.c->nSpheres : r.c->nOwners;
+        std::vector<float> loc(std::max<size_t>(nLoc, 1));
+        if (int rc = deme_inspect_values(r.c, q, loc.data(), nLoc))
+            return rc;
+        SlabIds ids;
+        if (int rc = slab_ids(m, r, perSphere ? IDS_SPHERE | IDS_SPHERE_OWNER : IDS_OWNER, ids))
+            return rc;
+        for (size_t i = 0; i < nLoc; i++) {
+            const uint32_t gid = perSphere ? ids.sphereGid[i] : ids.ownerGid[i];
+            if (slab_reports(r, perSphere ? ids.sphereOwner[i] : (uint32_t)i) && gid < want)
+                out[gid] = loc[i];
         }
-    }
-    return DEME_OK;
+        return DEME_OK;
+    });
 }
 
 // ---- contact inspectors of a decomposed run (deme_contact_inspect.h) ------------------------------------------------------------------
@@ -1770,33 +1702,20 @@ int multi_contact_inspect_begin(deme_multi* m, const char* who, const void* out,
                          "does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (auto* g : m->groups)  // what deme_multi_download_contact_records would say, slab by slab
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            if (!s.geo.set)
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            if (!r.s->geo.set)
                 return mfail(m, DEME_ERR_INVALID, "%s: a slab has no books (deme_halo_group_set_slab / _build)", who);
-            if (!c->nContacts)
-                continue;
-            int rc = DEME_OK;  // (fail() writes c->err: called on its own, before the message is read)
-            if (!c->record)
-                rc = fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
-            else if (c->seeded)
-                rc = fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
-            if (rc)
-                return mfail(m, rc, "%s", c->err.c_str());
-        }
+            return slab_records_refused(r);
+        }))
+        return rc;
     regions.clear();
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            int rid = -1;
-            if (int rc = slab_region(s.ctx, regionCode, &rid))
-                return mfail(m, rc, "%s", s.ctx->err.c_str());
-            regions.push_back(rid);
-        }
-    }
-    return DEME_OK;
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        int rid = -1;
+        if (int rc = slab_region(r.c, regionCode, &rid))
+            return rc;
+        regions.push_back(rid);
+        return DEME_OK;
+    });
 }
 // one slab's counted sides per owner slot (left in ciCounts by contact_inspect_launch) added at the global ids of h
 int slab_contact_counts(deme_ctx* c, const HaloSlab& s, uint32_t nOG, std::vector<uint32_t>& h) {
@@ -1826,20 +1745,17 @@ int deme_multi_inspect_contacts(deme_multi* m, const char* regionCode, float thr
     if (int rc = multi_contact_inspect_begin(m, "deme_multi_inspect_contacts", out, regionCode, thr, regions))
         return rc;
     DemeContactSums sum{};
-    size_t slab = 0;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
             DemeContactSums h{};
-            if (int rc = slab_contact_sums(s.ctx, regions[slab++], thr, &h))
-                return mfail(m, rc, "%s", s.ctx->err.c_str());
+            if (int rc = slab_contact_sums(r.c, regions[r.no], thr, &h))
+                return rc;
             m->qHostBytes += sizeof h;
             for (int j = 0; j < 9; j++)
                 sum.virial[j] += h.virial[j];
             sum.sides += h.sides, sum.clumps += h.clumps;
-        }
-    }
+            return DEME_OK;
+        }))
+        return rc;
     *out = sum;
     return DEME_OK;
 }
@@ -1852,21 +1768,17 @@ int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, flo
         return rc;
     const uint32_t nOG = m->plan->nOwnersGlobal;
     std::vector<uint32_t> sum(nOG, 0u), h;
-    size_t slab = 0;
-    for (auto* g : m->groups) {
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            if (int rc = contact_inspect_launch(c, regions[slab++], thr, true, nullptr))
-                return mfail(m, rc, "%s", c->err.c_str());
-            if (int rc = slab_contact_counts(c, s, nOG, h))
-                return mfail(m, rc, "%s", c->err.c_str());
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            if (int rc = contact_inspect_launch(r.c, regions[r.no], thr, true, nullptr))
+                return rc;
+            if (int rc = slab_contact_counts(r.c, *r.s, nOG, h))
+                return rc;
             m->qHostBytes += 4ull * nOG;
             for (uint32_t i = 0; i < nOG; i++)
                 sum[i] += h[i];
-        }
-    }
+            return DEME_OK;
+        }))
+        return rc;
     if (nOG)
         memcpy(perOwnerGlobal, sum.data(), (size_t)nOG * 4);
     return DEME_OK;
@@ -1890,26 +1802,23 @@ int deme_multi_rebalance(deme_multi* m, uint32_t* clumpsMoved, double* newEdges)
         return rc;
     // the coordinate of every own clump along the cut axis, and the boundaries in force
     const int axis = m->plan->axis;
-    const uint32_t per = nSlabs / (uint32_t)m->groups.size();
     std::vector<double> x;
     std::vector<double> edges(nSlabs + 1);
     DemeParams hp{};
-    for (uint32_t s = 0; s < nSlabs; s++) {
-        deme_halo_group* g = m->groups[s / per];
-        HaloSlab& sl = g->slabs[s % per];
-        deme_ctx* c = sl.ctx;
-        if (hipSetDevice(g->device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-        if (!sl.geo.set)
-            return mfail(m, DEME_ERR_INVALID, "rebalance: slab %u has no books", s);
-        hp = c->hp;
-        edges[s] = sl.geo.xLo, edges[s + 1] = sl.geo.xHi;
-        std::vector<OwnerRec> rec(sl.geo.nOwn);
-        if (sl.geo.nOwn && hipMemcpy(rec.data(), c->owners.p, (size_t)sl.geo.nOwn * sizeof(OwnerRec), hipMemcpyDeviceToHost) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "rebalance: the owners of slab %u could not be read", s);
-        for (auto& r : rec)
-            x.push_back(decomp_coord(hp, r.voxelID, r.locX, r.locY, r.locZ, axis));
-    }
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            const SlabGeom& q = r.s->geo;
+            if (!q.set)
+                return mfail(m, DEME_ERR_INVALID, "rebalance: slab %u has no books", r.no);
+            hp = r.c->hp;
+            edges[r.no] = q.xLo, edges[r.no + 1] = q.xHi;
+            std::vector<OwnerRec> rec(q.nOwn);
+            if (q.nOwn && hipMemcpy(rec.data(), r.c->owners.p, (size_t)q.nOwn * sizeof(OwnerRec), hipMemcpyDeviceToHost) != hipSuccess)
+                return mfail(m, DEME_ERR_HIP, "rebalance: the owners of slab %u could not be read", r.no);
+            for (auto& o : rec)
+                x.push_back(decomp_coord(hp, o.voxelID, o.locX, o.locY, o.locZ, axis));
+            return DEME_OK;
+        }))
+        return rc;
     if (x.empty())
         return DEME_OK;
     std::sort(x.begin(), x.end());
@@ -1938,10 +1847,9 @@ int deme_multi_rebalance(deme_multi* m, uint32_t* clumpsMoved, double* newEdges)
     for (uint32_t i = 1; i + 1 < nSlabs; i++)  // (an interior slab keeps at least a halo of width: where two boundaries would come
         if (next[i + 1] - next[i] < halo)      // closer than that, both stay where they are this time)
             next[i] = edges[i], next[i + 1] = edges[i + 1];
-    for (uint32_t s = 0; s < nSlabs; s++) {
-        HaloSlab& sl = m->groups[s / per]->slabs[s % per];
-        sl.geo.xLo = next[s], sl.geo.xHi = next[s + 1];
-    }
+    for (uint32_t s = 0; s < nSlabs; s++)
+        if (HaloSlab* sl = multi_slab(m, s).s)
+            sl->geo.xLo = next[s], sl->geo.xHi = next[s + 1];
     for (uint32_t i = 0; i <= nSlabs; i++)
         m->plan->edges[i] = next[i];
     if (newEdges)
@@ -1963,12 +1871,12 @@ int deme_multi_rebalance(deme_multi* m, uint32_t* clumpsMoved, double* newEdges)
 int deme_multi_slab_counts(deme_multi* m, uint32_t slab, uint32_t counts[6], double range[2]) {
     if (!m || !m->plan || slab >= m->plan->nSlabs)
         return DEME_ERR_INVALID;
-    const uint32_t per = m->plan->nSlabs / (uint32_t)m->groups.size();
-    deme_halo_group* g = m->groups[slab / per];
-    HaloSlab& sl = g->slabs[slab % per];
+    const SlabRef r = multi_slab(m, slab);
+    if (!r.s)
+        return DEME_ERR_INVALID;
     if (range)
-        range[0] = sl.geo.xLo, range[1] = sl.geo.xHi;
-    return counts ? deme_halo_group_slab_counts(g, sl.ctx, counts) : DEME_OK;
+        range[0] = r.s->geo.xLo, range[1] = r.s->geo.xHi;
+    return counts ? deme_halo_group_slab_counts(r.g, r.c, counts) : DEME_OK;
 }
 
 // deme_change_owner_sizes on a decomposed run, by GLOBAL owner id: every slab resizes its own clumps and its ghost copies of them
@@ -1989,19 +1897,11 @@ int deme_multi_change_owner_sizes(deme_multi* m, const uint32_t* globalIds, cons
     std::vector<uint32_t> byGid(m->plan->nOwnersGlobal, 0);
     for (size_t i = 0; i < n; i++)
         byGid[globalIds[i]] = fb[i];
-    struct Part {
-        deme_ctx* c;
-        int device;
-    };
-    std::vector<Part> parts;
     std::map<uint64_t, uint32_t> merged;  // key -> spheres that carry it, over every slab (own clumps and ghost copies)
     std::vector<uint32_t> usesAll;
     const deme_ctx* first = nullptr;
-    for (auto* g : m->groups)
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            if (hipSetDevice(g->device) != hipSuccess)
-                return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            deme_ctx* c = r.c;
             if (!first) {
                 first = c;
                 usesAll.assign(c->nComp, 0);
@@ -2009,22 +1909,26 @@ int deme_multi_change_owner_sizes(deme_multi* m, const uint32_t* globalIds, cons
                        memcmp(c->hComp.data(), first->hComp.data(), (size_t)c->nComp * sizeof(float4)) != 0) {
                 return mfail(m, DEME_ERR_INVALID, "deme_multi_change_owner_sizes: the slabs' component tables differ");
             }
-            std::vector<uint32_t> gid(c->nOwnerClumps), ids, bits;
-            if (c->nOwnerClumps && hipMemcpy(gid.data(), s.geo.ownerGid, (size_t)c->nOwnerClumps * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return mfail(m, DEME_ERR_HIP, "the slab's books could not be read");
-            for (uint32_t i = 0; i < c->nOwnerClumps; i++)  // own clumps [0, nOwn) and ghost copies [nOwn, nOwnerClumps)
-                if (gid[i] < byGid.size() && byGid[gid[i]])
-                    ids.push_back(i), bits.push_back(byGid[gid[i]]);
+            SlabIds book;
+            std::vector<uint32_t> ids, bits;
+            if (int rc = slab_ids(m, r, IDS_OWNER, book))
+                return rc;
+            for (uint32_t i = 0; i < c->nOwnerClumps; i++) {  // own clumps [0, nOwn) and ghost copies [nOwn, nOwnerClumps)
+                const uint32_t gid = book.ownerGid[i];
+                if (gid < byGid.size() && byGid[gid])
+                    ids.push_back(i), bits.push_back(byGid[gid]);
+            }
             std::vector<uint64_t> keys;
             std::vector<uint32_t> runs, uses;
             if (int rc = resize_collect(c, ids.data(), bits.data(), ids.size(), keys, runs, uses))
-                return mfail(m, rc, "%s", c->err.c_str());
+                return rc;
             for (size_t u = 0; u < keys.size(); u++)
                 merged[keys[u]] += runs[u];
             for (size_t k = 0; k < uses.size(); k++)
                 usesAll[k] += uses[k];
-            parts.push_back({c, g->device});
-        }
+            return DEME_OK;
+        }))
+        return rc;
     if (merged.empty() || !first)
         return DEME_OK;
     std::vector<uint64_t> keys;
@@ -2040,12 +1944,8 @@ int deme_multi_change_owner_sizes(deme_multi* m, const uint32_t* globalIds, cons
         return mfail(m, DEME_ERR_HALO, "deme_multi_change_owner_sizes: the largest clump would reach %g m from its centre, but the slabs were "
                      "cut with a halo of %g m, which must hold two such reaches; build the run again with a halo of at least %g m",
                      pl.reach, m->plan->halo, 2.0 * pl.reach);
-    for (auto& pt : parts) {
-        if (hipSetDevice(pt.device) != hipSuccess)
-            return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", pt.device);
-        if (int rc = resize_apply(pt.c, keys, pl))
-            return mfail(m, rc, "%s", pt.c->err.c_str());
-    }
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int { return resize_apply(r.c, keys, pl); }))
+        return rc;
     m->rowsValid = false;
     return DEME_OK;
 }
@@ -2058,20 +1958,16 @@ int deme_multi_download_sphere_components(deme_multi* m, uint16_t* comp, size_t 
         return mfail(m, DEME_ERR_INVALID, "buffer too small: need %u", m->plan->nSpheresGlobal);
     if (int rc = deme_multi_sync(m))
         return rc;
-    for (auto* g : m->groups)
-        for (auto& s : g->slabs) {
-            deme_ctx* c = s.ctx;
-            if (hipSetDevice(g->device) != hipSuccess)
-                return mfail(m, DEME_ERR_HIP, "device %d cannot be selected", g->device);
-            std::vector<uint32_t> gid(c->nSpheres);
-            std::vector<uint16_t> loc(c->nSpheres);
-            if (c->nSpheres && hipMemcpy(gid.data(), s.geo.sphereGid, (size_t)c->nSpheres * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return mfail(m, DEME_ERR_HIP, "the slab's books could not be read");
-            if (int rc = deme_download_sphere_components(c, loc.data(), loc.size()))
-                return mfail(m, rc, "%s", c->err.c_str());
-            for (uint32_t i = 0; i < c->nSpheres; i++)
-                if (gid[i] < m->plan->nSpheresGlobal)
-                    comp[gid[i]] = loc[i];
-        }
-    return DEME_OK;
+    return multi_slabs(m, [&](const SlabRef& r) -> int {
+        SlabIds ids;
+        std::vector<uint16_t> loc(r.c->nSpheres);
+        if (int rc = slab_ids(m, r, IDS_SPHERE, ids))
+            return rc;
+        if (int rc = deme_download_sphere_components(r.c, loc.data(), loc.size()))
+            return rc;
+        for (uint32_t i = 0; i < r.c->nSpheres; i++)
+            if (ids.sphereGid[i] < m->plan->nSpheresGlobal)
+                comp[ids.sphereGid[i]] = loc[i];
+        return DEME_OK;
+    });
 }

@@ -295,6 +295,21 @@ int fail(deme_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
+// the class field of a contact key for a contact type of the C-ABI (every analytical type is one class)
+inline uint64_t key_class_of_type(uint8_t type) {
+    return type == DEME_SPHERE_SPHERE_CONTACT ? DEME_KEY_CLASS_SS : type == DEME_SPHERE_MESH_CONTACT ? DEME_KEY_CLASS_SM : DEME_KEY_CLASS_SA;
+}
+
+// What every reader of the contact records (deme_download_contact_records, the by-owner query with records, the contact inspectors,
+// and their forms of a decomposed run, slab by slab) refuses of a list without them: the code, with the text left in c->err.
+int records_refused(deme_ctx* c) {
+    if (!c->record)
+        return fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
+    if (c->seeded)
+        return fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+    return DEME_OK;
+}
+
 #define HIPCK(call)                                                                                   \
     do {                                                                                              \
         hipError_t _e = (call);                                                                       \
@@ -3566,7 +3581,7 @@ int deme_seed_contacts(deme_ctx* c, const uint32_t* idA, const uint32_t* idB, co
     std::vector<uint64_t> keys(n);
     std::vector<uint8_t> flip(n, 0);
     for (size_t i = 0; i < n; i++) {
-        const uint64_t cls = (type[i] == 1) ? DEME_KEY_CLASS_SS : (type[i] == 2) ? DEME_KEY_CLASS_SM : DEME_KEY_CLASS_SA;
+        const uint64_t cls = key_class_of_type(type[i]);
         const uint32_t nB = (cls == DEME_KEY_CLASS_SS) ? c->dp.nSpheres : (cls == DEME_KEY_CLASS_SM) ? c->dp.nTri : c->dp.nAnal;
         if (idA[i] >= c->dp.nSpheres || idB[i] >= nB)
             return fail(c, DEME_ERR_INVALID, "deme_seed_contacts: pair %zu (%u, %u, type %u) is out of range", i, idA[i], idB[i],
@@ -3639,10 +3654,8 @@ int deme_set_record_contacts(deme_ctx* c, int enable) {
 int deme_download_contact_records(deme_ctx* c, float* force, float* torqueOnly, float* cpA, float* cpB, size_t cap) {
     if (int rc = check_ready(c))
         return rc;
-    if (!c->record)
-        return fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
-    if (c->seeded)
-        return fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+    if (int rc = records_refused(c))
+        return rc;
     const size_t n = c->nContacts;
     if (cap < n)
         return fail(c, DEME_ERR_INVALID, "buffer too small: need %zu", n);
@@ -3972,7 +3985,7 @@ int deme_upload_persistent_contacts(deme_ctx* c, const uint32_t* idA, const uint
         return fail(c, DEME_ERR_INVALID, "persistent contacts cannot be marked with a history-less force model");
     std::vector<uint64_t> keys(n);
     for (size_t i = 0; i < n; i++) {
-        const uint64_t cls = (type[i] == 1) ? DEME_KEY_CLASS_SS : (type[i] == 2) ? DEME_KEY_CLASS_SM : DEME_KEY_CLASS_SA;
+        const uint64_t cls = key_class_of_type(type[i]);
         const uint32_t nB = (cls == DEME_KEY_CLASS_SS) ? c->dp.nSpheres : (cls == DEME_KEY_CLASS_SM) ? c->dp.nTri : c->dp.nAnal;
         if (idA[i] >= c->dp.nSpheres || idB[i] >= nB)
             return fail(c, DEME_ERR_INVALID, "deme_upload_persistent_contacts: pair %zu (%u, %u, type %u) is out of range", i, idA[i],
@@ -4644,10 +4657,9 @@ int deme_query_owner_contacts(deme_ctx* c, const uint32_t* ownerIds, size_t nOwn
     char msg[320];
     if (int rc = owner_ids_refused(msg, "deme_query_owner_contacts", nOut, "nOut", ownerIds, nOwners, c->nOwners))
         return fail(c, rc, "%s", msg);
-    if (withRecords && !c->record)
-        return fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
-    if (withRecords && c->seeded)
-        return fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+    if (withRecords)
+        if (int rc = records_refused(c))
+            return rc;
     std::vector<uint32_t> ids(ownerIds, ownerIds + nOwners);
     std::sort(ids.begin(), ids.end());
     ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
@@ -4683,8 +4695,8 @@ int deme_query_host_bytes(const deme_ctx* c, uint64_t* bytes) {
 
 // ---- contact inspectors: virial sum and counted sides of the current list (deme_contact_inspect.h) ----------------------------------
 namespace {
-// the refusals deme_inspect_contacts and deme_inspect_contact_counts share, in the order they make them (the last two are those of
-// deme_download_contact_records, with its words)
+// the refusals deme_inspect_contacts and deme_inspect_contact_counts share, in the order they make them (the last are those of
+// deme_download_contact_records: records_refused)
 int contact_inspect_refused(deme_ctx* c, const char* who, const void* out, int region, float thr) {
     if (!out)
         return fail(c, DEME_ERR_INVALID, "%s: null output", who);
@@ -4692,10 +4704,8 @@ int contact_inspect_refused(deme_ctx* c, const char* who, const void* out, int r
         return fail(c, DEME_ERR_INVALID, "unknown inspection region %d", region);
     if (!std::isfinite(thr) || thr < 0.f)
         return fail(c, DEME_ERR_INVALID, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
-    if (!c->record)
-        return fail(c, DEME_ERR_INVALID, "contact recording is off (deme_set_record_contacts)");
-    if (c->seeded)
-        return fail(c, DEME_ERR_INVALID, "the list is a seed (deme_seed_contacts, or the engine's order was just renewed): its contacts have not been evaluated yet -- step or detect first");
+    if (int rc = records_refused(c))
+        return rc;
     return DEME_OK;
 }
 // The passes of one context, enqueued on its stream.  perOwner false: the result is left in ciPartial behind the blocks' partials

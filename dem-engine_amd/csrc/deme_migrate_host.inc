@@ -330,6 +330,31 @@ int deme_halo_group_slab_counts(const deme_halo_group* g, const deme_ctx* c, uin
     return DEME_ERR_INVALID;
 }
 
+namespace {
+// A slab's id books on the host -- the global id of every owner slot and of every sphere, every sphere's owner slot and component --,
+// only the arrays that are asked for (null: not read).  The ONE host reader of the books: the caller has selected the slab's device
+// and waited for whatever writes them (a migration).
+hipError_t slab_ids_host(const HaloSlab& s, uint32_t* ownerGlobal, uint32_t* sphereGlobal, uint32_t* sphereOwner, uint16_t* sphereComp) {
+    const deme_ctx* c = s.ctx;
+    hipError_t e = hipSuccess;
+    if (ownerGlobal && c->nOwners)
+        e = hipMemcpy(ownerGlobal, s.geo.ownerGid, (size_t)c->nOwners * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && sphereGlobal && c->nSpheres)
+        e = hipMemcpy(sphereGlobal, s.geo.sphereGid, (size_t)c->nSpheres * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (sphereOwner || sphereComp) && c->nSpheres) {
+        std::vector<SphereRec> h(c->nSpheres);
+        e = hipMemcpy(h.data(), c->spheres.p, (size_t)c->nSpheres * sizeof(SphereRec), hipMemcpyDeviceToHost);
+        for (uint32_t i = 0; e == hipSuccess && i < c->nSpheres; i++) {
+            if (sphereOwner)
+                sphereOwner[i] = h[i].owner;
+            if (sphereComp)
+                sphereComp[i] = h[i].comp;
+        }
+    }
+    return e;
+}
+}  // namespace
+
 int deme_halo_group_download_ids(deme_halo_group* g, deme_ctx* c, uint32_t* ownerGlobal, uint32_t* sphereGlobal, uint32_t* sphereOwner,
                                  uint16_t* sphereComp) {
     if (!g || !c)
@@ -338,20 +363,7 @@ int deme_halo_group_download_ids(deme_halo_group* g, deme_ctx* c, uint32_t* owne
     for (auto& s : g->slabs)
         if (s.ctx == c && s.geo.set) {
             GHIP(hipStreamSynchronize(c->stream));
-            if (ownerGlobal)
-                GHIP(hipMemcpy(ownerGlobal, s.geo.ownerGid, (size_t)c->nOwners * 4, hipMemcpyDeviceToHost));
-            if (sphereGlobal)
-                GHIP(hipMemcpy(sphereGlobal, s.geo.sphereGid, (size_t)c->nSpheres * 4, hipMemcpyDeviceToHost));
-            if (sphereOwner || sphereComp) {
-                std::vector<SphereRec> h(c->nSpheres);
-                GHIP(hipMemcpy(h.data(), c->spheres.p, (size_t)c->nSpheres * sizeof(SphereRec), hipMemcpyDeviceToHost));
-                for (uint32_t i = 0; i < c->nSpheres; i++) {
-                    if (sphereOwner)
-                        sphereOwner[i] = h[i].owner;
-                    if (sphereComp)
-                        sphereComp[i] = h[i].comp;
-                }
-            }
+            GHIP(slab_ids_host(s, ownerGlobal, sphereGlobal, sphereOwner, sphereComp));
             return DEME_OK;
         }
     return gfail(g, DEME_ERR_INVALID, "download_ids: the context has no slab geometry (deme_halo_group_set_slab)");

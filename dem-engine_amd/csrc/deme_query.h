@@ -170,8 +170,8 @@ __device__ inline void query_state_write(OwnerRec* __restrict__ out, uint32_t at
 
 // bk.ownerGid == null: a gather by slot -- thread i copies owner slots[i] (the host translated the caller's ids) to out[i]; nHits unused.
 // Otherwise one thread per owner slot of the slab: the owner's global id looked up, tested against the marks, and taken under the
-// rule of group_state_io -- own clumps from the slab that owns them, replicated owners (slots from nOwnerClumps on) from the first
-// slab of the chain (takeReplicated) --, hits compacted per wavefront as in k_query_select.
+// rule of the host's slab_reports (deme_decomp.inc) -- own clumps from the slab that owns them, replicated owners (slots from
+// nOwnerClumps on) from the first slab of the chain (takeReplicated) --, hits compacted per wavefront as in k_query_select.
 __global__ __launch_bounds__(256) void k_query_owner_state(uint32_t n, const OwnerRec* __restrict__ owners, const uint32_t* __restrict__ slots,
                                                            const uint32_t* __restrict__ o2e, SlabBooksDev bk, uint32_t nOwnerClumps, uint32_t takeReplicated,
                                                            const uint8_t* __restrict__ mark, OwnerRec* __restrict__ out, uint32_t cap,

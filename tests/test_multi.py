@@ -94,6 +94,54 @@ def test_multi_adds_accelerations_by_global_owner_id(pkg, orc):
     m.close()
 
 
+def test_multi_adds_accelerations_to_a_range_of_owners_that_starts_mid_scene(pkg, orc):
+    """deme_multi_add_owner_acc for owners [nc // 3, nc // 3 + 200): row k of the caller's array belongs to global owner first + k
+    on whichever slab owns it, and no owner outside the range moves differently from the oracle's"""
+    b, p, sc = _bed(pkg, cd_freq=7)
+    nc = int(sc.nOwnerClumps)
+    first, n = nc // 3, 200
+    m = pkg.abi.Multi(devices=(0,))
+    m.build(p, sc, slabs_per_device=3, axis=0, halo=0.03, arith="exact")
+    sim = orc.make_sim(pkg, p, sc)
+    v0 = sim.download_state()["vX"][:nc].copy()
+    acc = np.zeros((n, 3), np.float32)
+    acc[:, 0] = np.linspace(-2.0e3, 2.0e3, n, dtype=np.float32)
+    m.add_owner_acc(first, acc), sim.add_owner_acc(first, acc)
+    m.step(2), sim.step(2)
+    m.sync()
+    g, o = m.download_state(), sim.download_state()
+    assert np.abs(g["vX"][:nc] - o["vX"][:nc]).max() < 1e-5 and np.abs(o["vX"][:nc] - v0).max() > 5e-3
+    outside = np.r_[0:first, first + n:nc]
+    assert np.abs(g["vX"][outside] - o["vX"][outside]).max() < 1e-5
+    m.close()
+
+
+def test_multi_writes_a_contact_wildcard_column_with_every_slabs_own_sign(pkg):
+    """deme_multi_upload_contact_wildcard: a column of the merged list written to a B -> A vector wildcard (0, flipped under the
+    default flip mask 7) and to a scalar one (3) reads back bit for bit; on the slabs the two columns agree up to sign, both signs
+    occur (some slab lists a pair the other way round than the merged list), and every row holds a value of the column"""
+    b, p, sc = _bed(pkg)
+    m = pkg.abi.Multi(devices=(0,))
+    m.build(p, sc, slabs_per_device=3, axis=0, halo=0.03, arith="exact")
+    m.step(20)
+    m.sync()
+    n = m.num_contacts()
+    assert 500 < n < 2 ** 24
+    v = np.arange(1, n + 1, dtype=np.float32)
+    m.set_contact_wildcard(0, v), m.set_contact_wildcard(3, v)
+    assert np.array_equal(m.wildcard(0), v) and np.array_equal(m.wildcard(3), v)
+    plus = minus = 0
+    for s in range(3):
+        c = m.slab_ctx(s)
+        c0, c3 = c.wildcard(0), c.wildcard(3)
+        assert len(c0) > 0 and np.array_equal(np.abs(c0), np.abs(c3)), s
+        assert np.isin(np.abs(c0), v).all() and np.isin(np.abs(c3), v).all(), s
+        plus, minus = plus + int((c0 > 0).sum()), minus + int((c0 < 0).sum())
+    print(f"{n} merged rows; on the slabs {plus} rows in the merged list's pair order, {minus} the other way round")
+    assert plus > 0 and minus > 0
+    m.close()
+
+
 def test_multi_migrates_a_drifting_bed(pkg, orc):
     """a sheared bed in three library-made slabs with deme_multi_set_migration(50): clumps change slabs inside deme_multi_step, the
     gather by global id follows them (the books come from the library), and the run stays on the oracle's single-domain trajectory
