@@ -137,7 +137,7 @@ struct deme_ctx {
     std::map<std::string, int> regionBySource;  // deme_multi_inspect_contacts: a region string compiles once per slab context
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
-    DevBuf geo, binLo, binN, counts, offsets, incKeys[2], incVals[2], keysRaw, keysMid, keysSorted[2], wc[2], ctr, segCtr,
+    DevBuf geo, binLo, binN, binPartial, incKeys[2], incVals[2], keysRaw, keysMid, keysSorted[2], wc[2], ctr,
         scanTmp, sortTmp, rec[4], stage;
     // The contact list the steps read (list[cur]) and the one an asynchronous detection builds beside them (list[cur ^ 1]).
     // Shared by both, on purpose: the key and history double buffers with their selectors (keysSorted, wc, keysCur, wcCur ...),
@@ -628,7 +628,7 @@ int status_to_error(deme_ctx* c, uint32_t st) {
 }
 
 int do_margins(deme_ctx* c, uint32_t drift) {
-    HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectCounters), c->stream));
+    HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->stream));
     c->ctrFresh = true;
     hipLaunchKernelGGL(k_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp, c->owners.as<OwnerRec>(),
                        drift, c->ctr.as<DetectCounters>());
@@ -644,17 +644,17 @@ int do_migrate(deme_ctx* c);
 int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t* nCout) {
     const uint32_t nS = c->nSpheres;
     DetectCounters hc{};
-    // The margins kernel zeroes the counters and may leave status bits (velocity limit, non-finite state): when it has just run the
-    // block is not zeroed again and its status comes back with the first sizing read-back below (no read-back of its own).
+    // The margins kernel's launch zeroes the counters (the whole DetectBlock, the segment counters with it: one fill) and may leave
+    // status bits (velocity limit, non-finite state): when it has just run the block is not zeroed again and its status comes back
+    // with the first sizing read-back below (no read-back of its own).
     const bool countersFresh = c->ctrFresh;
     c->ctrFresh = false;
     bool statusSeen = false;
 
-    if (int rc = ensure(c, c->segCtr, DEME_KEY_SEGS * DEME_KEY_SEG_STRIDE * 8))
-        return rc;
+    DetectBlock* blk = c->ctr.as<DetectBlock>();
     for (int attempt = 0; attempt < 4; attempt++) {
         if (attempt > 0 || !countersFresh)
-            HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectCounters), st));
+            HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), st));
         // the raw key arena: 64 segments with a counter each once it is large enough for every segment to hold a fair share of any
         // list (see KeyArena); one segment, counted in DetectCounters::nContactsRaw, below that
         const bool segmented = c->keySegMin && c->cntCap >= c->keySegMin && c->cntCap >= DEME_KEY_SEGS * 64u;
@@ -662,24 +662,22 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
         ar.keys = c->keysRaw.as<uint64_t>();
         ar.segMask = segmented ? DEME_KEY_SEGS - 1u : 0u;
         ar.segCap = segmented ? (uint64_t)c->cntCap / DEME_KEY_SEGS : (uint64_t)c->cntCap;
-        ar.ctr = segmented ? c->segCtr.as<unsigned long long>() : &c->ctr.as<DetectCounters>()->nContactsRaw;
-        if (segmented)
-            HIPCK(hipMemsetAsync(c->segCtr.p, 0, DEME_KEY_SEGS * DEME_KEY_SEG_STRIDE * 8, st));
+        ar.ctr = segmented ? blk->segCtr : &blk->c.nContactsRaw;
         if (nS) {
             c->geoStale = false;
             hipLaunchKernelGGL(k_sphere_prep, dim3(grid_for(nS)), dim3(256), 0, st, c->dp,
                                ow, c->spheres.as<SphereRec>(), c->geo.as<GeoRec>(),
-                               c->binLo.as<uint4>(), c->binN.as<uint2>(), c->counts.as<uint32_t>(),
+                               c->binLo.as<uint4>(), c->binN.as<uint2>(), c->binPartial.as<uint32_t>(),
                                ar, c->ctr.as<DetectCounters>(), c->sphFam.as<uint16_t>());
-            size_t tmp = c->scanTmp.bytes;
-            HIPCK(rocprim::exclusive_scan(c->scanTmp.p, tmp, c->counts.as<uint32_t>(), c->offsets.as<uint32_t>(), 0u,
-                                          (size_t)nS + 1, rocprim::plus<uint32_t>(), st));
+            // (one workgroup: the prefix of one sum per workgroup above, and the total for the read-back below)
+            hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, st, c->binPartial.as<uint32_t>(), c->binPartial.as<uint32_t>(),
+                               grid_for(nS), &blk->c.nIncidence);
         }
         uint32_t P = 0;
         bool filled = false;
         auto fill_incidence = [&]() {
             hipLaunchKernelGGL(k_fill_incidence, dim3(grid_for(nS)), dim3(256), 0, st, c->dp,
-                               c->binLo.as<uint4>(), c->binN.as<uint2>(), c->offsets.as<uint32_t>(),
+                               c->binLo.as<uint4>(), c->binN.as<uint2>(), c->binPartial.as<uint32_t>(),
                                c->incKeys[0].as<uint32_t>(), c->incVals[0].as<uint32_t>(), (uint64_t)c->incCap);
             filled = true;
         };
@@ -688,10 +686,9 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
         if (nS) {
             // (read-backs land in pinned memory: a copy into pageable memory goes through the runtime's staging buffer and costs
             // tens of microseconds of host time before the wait even starts)
-            HIPCK(hipMemcpyAsync(pin_at<uint32_t>(c, 0), c->offsets.as<uint32_t>() + nS, 4, hipMemcpyDeviceToHost, st));
-            HIPCK(hipMemcpyAsync(pin_at<DetectCounters>(c, 64), c->ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(pin_at<DetectCounters>(c, 1024), c->ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
             HIPCK(sync_readback(c, st, !async));
-            P = *pin_at<uint32_t>(c, 0), hc = *pin_at<DetectCounters>(c, 64);
+            hc = *pin_at<DetectCounters>(c, 1024);
             if (!statusSeen) {
                 statusSeen = true;
                 if (int rc = status_to_error(c, hc.status & ~DEME_ST_INCIDENCE))
@@ -701,23 +698,10 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
                 return fail(c, DEME_ERR_OVERFLOW,
                             "a sphere touches more than %u bins (margin far larger than the bin size): the incidence list cannot be built",
                             DEME_MAX_BINS_PER_SPHERE);
-            if ((uint64_t)hc.maxCount * nS > 0xFFFFFFFFull) {  // the 32-bit offsets may have wrapped: exact total in 64 bits
-                auto in64 = rocprim::make_transform_iterator(c->counts.as<uint32_t>(),
-                                                             [] __host__ __device__(uint32_t v) { return (unsigned long long)v; });
-                unsigned long long* tot = &c->ctr.as<DetectCounters>()->nContactsRaw;  // borrowed: saved and restored around the reduction (k_sphere_prep has already counted its sphere-analytical contacts here)
-                unsigned long long keep = 0, total = 0;
-                HIPCK(hipMemcpyAsync(&keep, tot, 8, hipMemcpyDeviceToHost, st));
-                if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                        return rocprim::reduce(tmp, bytes, in64, tot, 0ull, (size_t)nS, rocprim::plus<unsigned long long>(), st);
-                    }))
-                    return rc;
-                HIPCK(hipMemcpyAsync(&total, tot, 8, hipMemcpyDeviceToHost, st));
-                HIPCK(hipStreamSynchronize(st));
-                HIPCK(hipMemcpyAsync(tot, &keep, 8, hipMemcpyHostToDevice, st));
-                HIPCK(hipStreamSynchronize(st));
-                if (total > 0xFFFFFFFFull)
-                    return fail(c, DEME_ERR_OVERFLOW, "%llu bin-sphere incidences do not fit the 32-bit list offsets (use larger bins)", total);
-            }
+            if (hc.nIncidence > 0xFFFFFFFFull)  // (the total is exact in 64 bits; the offsets the kernels work with have wrapped)
+                return fail(c, DEME_ERR_OVERFLOW, "%llu bin-sphere incidences do not fit the 32-bit list offsets (use larger bins)",
+                            hc.nIncidence);
+            P = (uint32_t)hc.nIncidence;
         }
         if (P > c->incCap) {
             if (int rc = grow_incidence_arena(c, (size_t)P + P / 4 + 1024))
@@ -725,6 +709,7 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             filled = false;
         }
         c->nInc = P;
+        uint32_t nStats = 0;  // records of k_sweep's windows that are still to be added up
         const unsigned bits = bits_for((uint64_t)c->hp.nbX * c->hp.nbY * c->hp.nbZ, 32);  // of a bin id
         if (P) {
             if (!filled)
@@ -747,8 +732,11 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             hipLaunchKernelGGL(k_sweep, dim3(nWin), dim3(SW_T), 0, st, c->dp,
                                c->incKeys[1].as<uint32_t>(), c->incVals[1].as<uint32_t>(), P, c->geo.as<GeoRec>(),
                                c->sphFam.as<uint16_t>(), ar, c->binStat.as<uint2>());
-            hipLaunchKernelGGL(k_bin_stats_final, dim3((nWin + 2047u) / 2048u), dim3(256), 0, st, c->binStat.as<uint2>(), nWin,
-                               c->ctr.as<DetectCounters>());
+            if (segmented)  // (the workgroups of k_compact_keys add the windows' statistics up)
+                nStats = nWin;
+            else
+                hipLaunchKernelGGL(k_bin_stats_final, dim3((nWin + 2047u) / 2048u), dim3(256), 0, st, c->binStat.as<uint2>(), nWin,
+                                   c->ctr.as<DetectCounters>());
         }
         // ---- sphere-triangle contacts (only when a mesh is loaded and some sphere is registered in a bin)
         c->nTriInc = 0;
@@ -794,14 +782,13 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
         if (segmented) {
             compactBlocks = (uint32_t)std::min<uint64_t>(grid_for(std::max<uint64_t>(c->lastSegMax + c->lastSegMax / 8 + 1024, 1)), grid_for(ar.segCap));
             hipLaunchKernelGGL(k_compact_keys, dim3(compactBlocks, DEME_KEY_SEGS), dim3(256), 0, st, c->keysRaw.as<uint64_t>(), ar.segCap,
-                               c->segCtr.as<unsigned long long>(), 0u, c->keysSorted[nextEarly].as<uint64_t>());
+                               blk, 0u, c->keysSorted[nextEarly].as<uint64_t>(), c->binStat.as<uint2>(), nStats);
         }
-        HIPCK(hipMemcpyAsync(pin_at<DetectCounters>(c, 64), c->ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
-        const unsigned long long* hseg = pin_at<unsigned long long>(c, 1024);
-        if (segmented)
-            HIPCK(hipMemcpyAsync(pin_at<unsigned long long>(c, 1024), c->segCtr.p, DEME_KEY_SEGS * DEME_KEY_SEG_STRIDE * 8, hipMemcpyDeviceToHost, st));
+        // one copy: the counters and, with the segmented arena, the 64 counts k_compact_keys has put beside them
+        const DetectHead* hh = pin_at<DetectHead>(c, 1024);
+        HIPCK(hipMemcpyAsync(pin_at<DetectHead>(c, 1024), c->ctr.p, segmented ? sizeof(DetectHead) : sizeof(DetectCounters), hipMemcpyDeviceToHost, st));
         HIPCK(sync_readback(c, st, !async));
-        hc = *pin_at<DetectCounters>(c, 64);
+        hc = hh->c;
         if (!statusSeen) {
             statusSeen = true;
             if (int rc = status_to_error(c, hc.status & ~DEME_ST_INCIDENCE))
@@ -811,8 +798,8 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
         if (segmented) {
             hc.nContactsRaw = 0;
             for (uint32_t g = 0; g < DEME_KEY_SEGS; g++) {
-                hc.nContactsRaw += hseg[g * DEME_KEY_SEG_STRIDE];
-                segMax = std::max(segMax, hseg[g * DEME_KEY_SEG_STRIDE]);
+                hc.nContactsRaw += hh->segCount[g];
+                segMax = std::max(segMax, hh->segCount[g]);
             }
         }
         if (hc.nContactsRaw > c->cntCap || segMax > ar.segCap) {  // arena (or one segment of it) too small: grow and redo the emitting kernels
@@ -847,8 +834,8 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             c->lastSegMax = segMax;
             if (grid_for(segMax) > compactBlocks)
                 hipLaunchKernelGGL(k_compact_keys, dim3((unsigned)grid_for(segMax) - compactBlocks, DEME_KEY_SEGS), dim3(256), 0, st,
-                                   c->keysRaw.as<uint64_t>(), ar.segCap, c->segCtr.as<unsigned long long>(), compactBlocks,
-                                   c->keysSorted[next].as<uint64_t>());
+                                   c->keysRaw.as<uint64_t>(), ar.segCap, blk, compactBlocks, c->keysSorted[next].as<uint64_t>(),
+                                   (const uint2*)nullptr, 0u);
             if (hc.nContactsRaw)
                 rawKeys = c->keysSorted[next].as<uint64_t>();
         }
@@ -870,7 +857,7 @@ int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t
             hipLaunchKernelGGL(k_segment_rank_sort, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, mid,
                                c->keysSorted[next].as<uint64_t>());
             if (nPersist) {  // a marked contact the sweep found as well appears once (markDuplicateContacts)
-                unsigned long long* cnt = &c->ctr.as<DetectCounters>()->nContactsRaw;
+                unsigned long long* cnt = &blk->c.nContactsRaw;
                 if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
                         return rocprim::unique(tmp, bytes, c->keysSorted[next].as<uint64_t>(), c->keysRaw.as<uint64_t>(), cnt, (size_t)nC,
                                                rocprim::equal_to<uint64_t>(), st);
@@ -967,17 +954,18 @@ bool tile_eligible(const deme_ctx* c, uint64_t nC) {
 int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st, uint64_t nC) {
     const int next = c->keysCur ^ 1;
     L.invalidate();  // (a pending read-back of this list's last build is superseded)
+    const bool tileEligible = tile_eligible(c, nC);
+    const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
     if (nC) {
         const uint64_t nPrev = c->haveList ? c->nContacts : 0;
         hipLaunchKernelGGL(k_history, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, c->keysSorted[next].as<uint64_t>(),
-                           (uint32_t)nPrev, c->keysSorted[c->keysCur].as<uint64_t>(), L.mapping.as<uint32_t>());
+                           (uint32_t)nPrev, c->keysSorted[c->keysCur].as<uint64_t>(), L.mapping.as<uint32_t>(),
+                           L.rangeCtr.as<uint32_t>(), (uint32_t)(sizeof(RangeCounters) / 4), L.tileRem.as<uint32_t>(),
+                           tileEligible ? nTiles + 1 : 0u);
+    } else {  // (k_history zeroes the list builders' counters on the side; no list, no tiles)
+        HIPCK(hipMemsetAsync(L.rangeCtr.p, 0, sizeof(RangeCounters), st));
     }
     // per-owner gather lists for the atomics-free accumulation
-    HIPCK(hipMemsetAsync(L.rangeCtr.p, 0, sizeof(RangeCounters), st));
-    const bool tileEligible = tile_eligible(c, nC);
-    const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
-    if (tileEligible)
-        HIPCK(hipMemsetAsync(L.tileRem.p, 0, ((size_t)nTiles + 1) * 4, st));
     if (nC) {
         hipLaunchKernelGGL(k_contact_owners, dim3(grid_for(nC)), dim3(256), 0, st, c->dp, (uint32_t)nC,
                            c->keysSorted[next].as<uint64_t>(), c->spheres.as<SphereRec>(), L.ownerA.as<uint32_t>(),
@@ -1001,11 +989,8 @@ int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st
     bool tiled = false;
     RangeCounters hr{};
     if (tileEligible) {  // owner tiles (deme_tile.h): the builders of the list structures k_tile_forces and the integrator read
-        if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
-                return rocprim::exclusive_scan(tmp, bytes, L.tileRem.as<uint32_t>(), L.tileBase.as<uint32_t>(), 0u, (size_t)nTiles + 1,
-                                               rocprim::plus<uint32_t>(), st);
-            }))
-            return rc;
+        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, st, L.tileRem.as<uint32_t>(), L.tileBase.as<uint32_t>(), nTiles + 1,
+                           &L.rangeCtr.as<RangeCounters>()->nRemote);
         hipLaunchKernelGGL(k_tile_build, dim3(nTiles), dim3(256), 0, st, c->dp, c->nOwners, L.info.as<uint4>(),
                            L.ownerB[0].as<uint32_t>(), L.aStart.as<uint32_t>(), ow, L.tileBase.as<uint32_t>(), L.tInfo.as<uint2>(),
                            L.hList.as<uint32_t>(), L.hCount.as<uint32_t>(),
@@ -1016,11 +1001,11 @@ int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st
         hipLaunchKernelGGL(k_tile_stats, dim3((nTiles + 1023u) / 1024u), dim3(256), 0, st, nTiles, L.hCount.as<uint32_t>(),
                            L.lCount.as<uint32_t>(), L.rangeCtr.as<RangeCounters>());
         uint32_t nR = 0;  // crossing contacts = records = entries of the sort below: the one size the host has to know
-        HIPCK(hipMemcpyAsync(pin_at<uint32_t>(c, 8), L.tileBase.as<uint32_t>() + nTiles, 4, hipMemcpyDeviceToHost, st));
         HIPCK(hipMemcpyAsync(pin_at<RangeCounters>(c, 128), L.rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, st));
         HIPCK(sync_readback(c, st, true));  // (part 2 is short, also beside the steps)
-        nR = *pin_at<uint32_t>(c, 8), hr = *pin_at<RangeCounters>(c, 128);
-        nR += hr.nExtra;  // the records of the tiles that do not fit (k_tile_forces_big): every contact of such a tile has one
+        hr = *pin_at<RangeCounters>(c, 128);
+        // (nExtra: the records of the tiles that do not fit (k_tile_forces_big): every contact of such a tile has one)
+        nR = (uint32_t)hr.nRemote + hr.nExtra;
         L.nBigTiles = hr.nBig;
         const unsigned obits = bits_for(c->nOwners, 32);
         if (nR) {
@@ -1581,11 +1566,11 @@ int deme_ctx_create(int device, deme_ctx** out) {
         delete c;
         return DEME_ERR_HIP;
     }
-    if (ensure(c, c->ctr, sizeof(DetectCounters)) || ensure(c, c->scanTmp, 1 << 20)) {
+    if (ensure(c, c->ctr, sizeof(DetectBlock)) || ensure(c, c->scanTmp, 1 << 20)) {
         delete c;
         return DEME_ERR_HIP;
     }
-    hipMemsetAsync(c->ctr.p, 0, sizeof(DetectCounters), c->stream);
+    hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->stream);
     if (hipHostMalloc((void**)&c->pin, 16384, hipHostMallocDefault) != hipSuccess) {
         deme_ctx_destroy(c);
         return DEME_ERR_HIP;
@@ -1642,12 +1627,12 @@ void deme_ctx_destroy(deme_ctx* c) {
         hipStreamDestroy(c->detStream);
     }
     DevBuf* all[] = {&c->hCountIn, &c->ownersNext, &c->recContact, &c->inCnt, &c->inStart, &c->tInfoIn, &c->inContact,
-                     &c->sphFam, &c->dO2E, &c->dS2E, &c->segCtr, &c->rec32, &c->revSlot, &c->nextAcc, &c->binStat, &c->volumes,
+                     &c->sphFam, &c->dO2E, &c->dS2E, &c->rec32, &c->revSlot, &c->nextAcc, &c->binStat, &c->volumes,
                      &c->persistKeys, &c->owners, &c->spheres, &c->acc, &c->conA4, &c->conA2, &c->conB4, &c->conB2, &c->aSum,
                      &c->prescList, &c->prescSlot, &c->prescRec, &c->tris, &c->triWorld, &c->triLo, &c->triHi, &c->triCounts,
                      &c->triOffsets, &c->triKeys[0], &c->triKeys[1], &c->triVals[0], &c->triVals[1], &c->comp, &c->massProps,
                      &c->anal, &c->matPair, &c->E, &c->nu, &c->CoR, &c->mu, &c->Crr, &c->famMasks, &c->famExtra, &c->famFlags,
-                     &c->geo, &c->binLo, &c->binN, &c->counts, &c->offsets, &c->incKeys[0], &c->incKeys[1], &c->incVals[0],
+                     &c->geo, &c->binLo, &c->binN, &c->binPartial, &c->incKeys[0], &c->incKeys[1], &c->incVals[0],
                      &c->incVals[1], &c->keysRaw, &c->keysSorted[0], &c->keysSorted[1], &c->wc[0], &c->wc[1], &c->ctr,
                      &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
@@ -1850,12 +1835,10 @@ static int owner_scratch_for_counts(deme_ctx* c, size_t nO) {
 }
 static int sphere_scratch_for_counts(deme_ctx* c, size_t nS) {
     if (ensure(c, c->sphFam, std::max<size_t>(nS, 1) * 2) || ensure(c, c->geo, std::max<size_t>(nS, 1) * sizeof(GeoRec)) ||
-        ensure(c, c->binLo, std::max<size_t>(nS, 1) * 16) || ensure(c, c->binN, std::max<size_t>(nS, 1) * 8) || ensure(c, c->counts, (nS + 1) * 4) ||
-        ensure(c, c->offsets, (nS + 1) * 4))
+        ensure(c, c->binLo, std::max<size_t>(nS, 1) * 16) || ensure(c, c->binN, std::max<size_t>(nS, 1) * 8) ||
+        ensure(c, c->binPartial, (size_t)grid_for(std::max<size_t>(nS, 1)) * 4))  // one sum per workgroup of k_sphere_prep
         return c->lastStatus;
-    size_t need = 0;
-    HIPCK(rocprim::exclusive_scan(nullptr, need, c->counts.as<uint32_t>(), c->offsets.as<uint32_t>(), 0u, nS + 1, rocprim::plus<uint32_t>(), c->stream));
-    return ensure(c, c->scanTmp, need);
+    return DEME_OK;
 }
 
 int deme_upload_scene(deme_ctx* c, const DemeScene* s) {
@@ -2423,7 +2406,7 @@ static int async_part1(deme_ctx* c, uint64_t* nC) {
     const uint32_t K = c->hp.cdUpdateFreq, D = c->asyncLead;
     HIPCK(hipStreamWaitEvent(c->detStream, c->evSnap, 0));
     ScopedTimer tm(c, "detect_async_part1", true, c->detStream);
-    HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectCounters), c->detStream));
+    HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->detStream));
     hipLaunchKernelGGL(k_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, c->detStream, c->dp, c->ownersSnap.as<OwnerRec>(),
                        K + D, c->ctr.as<DetectCounters>());
     c->ctrFresh = true;

@@ -3,8 +3,8 @@
 // Pipeline of one contact-detection update (replaces algorithms/DEMCubContactDetection.cu:38-1123,
 // which runs ~7 radix sorts, 6 scans, 3 run-length encodes and >=10 host syncs):
 //   k_sphere_prep   sphere world geometry + bin span + sphere-analytical contacts   (1 pass)
-//   exclusive scan  of per-sphere bin counts                                         (rocPRIM)
-//   k_fill_incidence (bin, sphere) pairs in sphere order
+//   k_scan_small    exclusive prefix of the workgroups' sums of per-sphere bin counts, and their total
+//   k_fill_incidence (bin, sphere) pairs in sphere order (each count again from the bin span, scanned in the workgroup)
 //   radix sort      pairs by bin (only ceil(log2(nBins)) key bits)                   (rocPRIM)
 //   k_sweep         LDS-staged chunks of the bin-sorted list, all pairs inside a bin,
 //                   contact-point-in-this-bin de-duplication, wavefront ballot/prefix
@@ -29,8 +29,9 @@ struct DetectCounters {  // one 64-byte block of device counters, zeroed per det
     unsigned int nActiveBins;
     unsigned int maxInBin;
     unsigned int status;
-    unsigned int maxCount;  // largest number of bins one sphere touches (sizing check of the 32-bit incidence offsets)
-    unsigned int pad[10];
+    unsigned int pad0;
+    unsigned long long nIncidence;  // (bin, sphere) pairs of all spheres, exact in 64 bits (k_scan_small); the list's offsets are 32-bit
+    unsigned int pad[8];
 };
 
 // Where the emitting kernels (k_sphere_prep, k_sweep, k_tri_sweep) append their raw contact keys.  A reservation is an atomic add
@@ -41,6 +42,17 @@ struct DetectCounters {  // one 64-byte block of device counters, zeroed per det
 // gaps afterwards (the host has read the counters by then: it needs the total anyway).  Small arenas keep one segment.
 #define DEME_KEY_SEGS 64u
 #define DEME_KEY_SEG_STRIDE 16u  // in counters (8 bytes each)
+// The detection's counters as one allocation, cleared by one fill: the block above, the segments' counts as k_compact_keys leaves
+// them for the host (densely: one read-back brings the head of this struct), and the segment counters themselves.
+struct DetectBlock {
+    DetectCounters c;
+    unsigned long long segCount[DEME_KEY_SEGS];
+    unsigned long long segCtr[DEME_KEY_SEGS * DEME_KEY_SEG_STRIDE];
+};
+struct DetectHead {  // what the host reads back
+    DetectCounters c;
+    unsigned long long segCount[DEME_KEY_SEGS];
+};
 struct KeyArena {
     uint64_t* keys;
     unsigned long long* ctr;  // segment g counts at ctr[g * DEME_KEY_SEG_STRIDE]
@@ -61,14 +73,19 @@ __device__ inline void arena_store(const KeyArena& a, uint32_t seg, unsigned lon
 // on the device (every workgroup adds up the 64 of them for its segment's start), so the kernel can be enqueued BEFORE the host
 // reads them: the GPU works through that read-back.  xOff: first slot-block this launch covers (the host launches the rest of a
 // segment that turned out longer than its estimate).
-__global__ __launch_bounds__(256) void k_compact_keys(const uint64_t* __restrict__ in, uint64_t segCap,
-                                                      const unsigned long long* __restrict__ segCtr, uint32_t xOff,
-                                                      uint64_t* __restrict__ out) {
+// The first launch of a detection (stats != nullptr) does two small jobs on the side, in the workgroups of segment 0: the counts
+// go to DetectBlock::segCount for the host, and k_sweep's per-window statistics are added up (bin_stats_block).
+__device__ void bin_stats_block(const uint2* __restrict__ perBlock, uint32_t nBlocks, uint32_t block, DetectCounters* ctr);
+__global__ __launch_bounds__(256) void k_compact_keys(const uint64_t* __restrict__ in, uint64_t segCap, DetectBlock* blk, uint32_t xOff,
+                                                      uint64_t* __restrict__ out, const uint2* __restrict__ stats, uint32_t nStats) {
     __shared__ unsigned long long sStart, sCount;
     const uint32_t seg = blockIdx.y;
     if (threadIdx.x < 64) {
         static_assert(DEME_KEY_SEGS == 64, "one lane per segment");
-        const unsigned long long cnt = min(segCtr[threadIdx.x * DEME_KEY_SEG_STRIDE], (unsigned long long)segCap);
+        const unsigned long long raw = blk->segCtr[threadIdx.x * DEME_KEY_SEG_STRIDE];
+        if (stats && seg == 0 && blockIdx.x == 0)
+            blk->segCount[threadIdx.x] = raw;
+        const unsigned long long cnt = min(raw, (unsigned long long)segCap);
         unsigned long long inc = cnt;
         for (int d = 1; d < 64; d <<= 1) {
             const unsigned long long u = __shfl_up(inc, d);
@@ -82,6 +99,9 @@ __global__ __launch_bounds__(256) void k_compact_keys(const uint64_t* __restrict
     const uint64_t i = ((uint64_t)xOff + blockIdx.x) * blockDim.x + threadIdx.x;
     if (i < sCount)
         out[sStart + i] = in[(uint64_t)seg * segCap + i];
+    if (stats && seg == 0)  // (uniform in the workgroup)
+        for (uint32_t b = blockIdx.x; b * 2048u < nStats; b += gridDim.x)
+            bin_stats_block(stats, nStats, b, &blk->c);
 }
 
 // ---------------------------------------------------------------------------
@@ -127,9 +147,10 @@ struct ObjWorld {
 __global__ __launch_bounds__(256) void k_sphere_prep(const DevParams p, const OwnerRec* __restrict__ owners,
                                                      const SphereRec* __restrict__ spheres, GeoRec* __restrict__ geo,
                                                      uint4* __restrict__ binLo, uint2* __restrict__ binN,
-                                                     uint32_t* __restrict__ counts, const KeyArena ar, DetectCounters* ctr,
+                                                     uint32_t* __restrict__ partial, const KeyArena ar, DetectCounters* ctr,
                                                      uint16_t* __restrict__ sphFam) {
     __shared__ ObjWorld sObj[64];
+    __shared__ uint32_t sWaveSum[4];
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = s < p.nSpheres;
     d3 pos{0, 0, 0};
@@ -168,14 +189,19 @@ __global__ __launch_bounds__(256) void k_sphere_prep(const DevParams p, const Ow
         if (n64 > DEME_MAX_BINS_PER_SPHERE)
             atomicOr(&ctr->status, DEME_ST_INCIDENCE);
         myCount = (n64 > DEME_MAX_BINS_PER_SPHERE) ? 0u : (uint32_t)n64;
-        counts[s] = myCount;
     }
-    // largest per-sphere count, recorded only when it is large enough for nSpheres such counts to overflow the 32-bit offsets
-    // of the scan (never in a sanely binned scene: no atomic, no extra load on the normal path); the host then checks the total
-    if (myCount > 0xFFFFFFFFu / max(p.nSpheres, 1u))
-        atomicMax(&ctr->maxCount, myCount);
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        counts[p.nSpheres] = 0;  // scan sentinel: offsets[nSpheres] = total
+    // first level of the scan of the counts: this workgroup's sum (256 counts of at most 2^24 - 1 fit 32 bits exactly);
+    // k_scan_small takes the prefix of the sums, k_fill_incidence has each count again from the bin span
+    {
+        uint32_t sum = myCount;
+        for (int off = 32; off > 0; off >>= 1)
+            sum += (uint32_t)__shfl_xor((int)sum, off);
+        if ((threadIdx.x & 63u) == 0)
+            sWaveSum[threadIdx.x >> 6] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partial[blockIdx.x] = sWaveSum[0] + sWaveSum[1] + sWaveSum[2] + sWaveSum[3];
+    }
 
     for (uint32_t ob0 = 0; ob0 < p.nAnal; ob0 += 64) {
         __syncthreads();
@@ -234,20 +260,91 @@ __global__ __launch_bounds__(256) void k_sphere_prep(const DevParams p, const Ow
     }
 }
 
+// The exclusive prefix of a short array by ONE workgroup (out may be in), and its total: a look-back scan of the library is two
+// dispatches and a read-back of out[n] a third, where a few thousand values are a few rounds of one workgroup.  Two users:
+//   the second level of the scan of the per-sphere bin counts -- the sums that the workgroups of k_sphere_prep left (one per 256
+//     spheres: 11 719 at 3e6 spheres) become their prefix in place, 32-bit like the list's offsets, and the exact total goes to
+//     DetectCounters::nIncidence for the host, which sizes the arena from it and refuses a list past 2^32 entries;
+//   the tiles' counts of crossing contacts (deme_tile.h), total to RangeCounters::nRemote.
+#define DEME_SCAN_T 1024u
+#define DEME_SCAN_IPT 4u
+__global__ __launch_bounds__(DEME_SCAN_T) void k_scan_small(const uint32_t* in, uint32_t* out, uint32_t n, unsigned long long* totalOut) {
+    __shared__ unsigned long long sWave[DEME_SCAN_T / 64];
+    __shared__ unsigned long long sCarry;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (threadIdx.x == 0)
+        sCarry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < n; base += DEME_SCAN_T * DEME_SCAN_IPT) {
+        const uint32_t first = base + threadIdx.x * DEME_SCAN_IPT;
+        uint32_t v[DEME_SCAN_IPT];
+        unsigned long long sum = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < DEME_SCAN_IPT; i++) {
+            v[i] = first + i < n ? in[first + i] : 0u;
+            sum += v[i];
+        }
+        unsigned long long inc = sum;
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long u = __shfl_up(inc, d);
+            if ((int)lane >= d)
+                inc += u;
+        }
+        if (lane == 63)
+            sWave[w] = inc;
+        __syncthreads();
+        unsigned long long run = sCarry + inc - sum, total = 0;
+        for (uint32_t j = 0; j < DEME_SCAN_T / 64; j++) {
+            const unsigned long long t = sWave[j];
+            run += j < w ? t : 0ull;
+            total += t;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < DEME_SCAN_IPT; i++) {
+            if (first + i < n)
+                out[first + i] = (uint32_t)run;
+            run += v[i];
+        }
+        __syncthreads();  // (every thread has read sCarry and sWave)
+        if (threadIdx.x == 0)
+            sCarry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        *totalOut = sCarry;
+}
+
 // kernel/DEMBinSphereKernels.cu:181-211: z-y-x loop nest, sphere-major output
 __global__ __launch_bounds__(256) void k_fill_incidence(const DevParams p, const uint4* __restrict__ binLo,
                                                         const uint2* __restrict__ binN,
-                                                        const uint32_t* __restrict__ offsets,
+                                                        const uint32_t* __restrict__ partialPrefix,
                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                         uint64_t cap) {
+    __shared__ uint32_t sWaveSum[4];
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= p.nSpheres)
+    const bool valid = s < p.nSpheres;
+    const uint4 lo = valid ? binLo[s] : make_uint4(0u, 0u, 0u, 0u);
+    const uint2 n = valid ? binN[s] : make_uint2(0u, 0u);
+    // (a sphere past the limit was counted as zero and flagged by k_sphere_prep; the host stops the detection when it reads the flag)
+    const uint64_t n64 = (uint64_t)lo.w * n.x * n.y;
+    const uint32_t cnt = n64 > DEME_MAX_BINS_PER_SPHERE ? 0u : (uint32_t)n64;
+    // this sphere's first entry: the prefix of the workgroups before + the counts before it in this workgroup
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t inc = cnt;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)inc, d);
+        if ((int)lane >= d)
+            inc += u;
+    }
+    if (lane == 63)
+        sWaveSum[w] = inc;
+    __syncthreads();
+    uint32_t before = partialPrefix[blockIdx.x] + inc - cnt;
+    for (uint32_t j = 0; j < 3; j++)
+        before += j < w ? sWaveSum[j] : 0u;
+    if (!cnt)
         return;
-    const uint4 lo = binLo[s];
-    const uint2 n = binN[s];
-    if ((uint64_t)lo.w * n.x * n.y > DEME_MAX_BINS_PER_SPHERE)
-        return;  // (counted as zero and flagged by k_sphere_prep; the host stops the detection when it reads the flag)
-    uint64_t off = offsets[s];
+    uint64_t off = before;
     for (uint32_t k = lo.z; k < lo.z + n.y; k++)
         for (uint32_t j = lo.y; j < lo.y + n.x; j++)
             for (uint32_t i = lo.x; i < lo.x + lo.w; i++) {
@@ -688,13 +785,14 @@ __global__ __launch_bounds__(SW_T) void k_sweep(const DevParams p, const uint32_
 
 // Active-bin count and the largest bin population (numSpheresBinTouches statistics of DEMCubContactDetection.cu:195-230; the
 // population check feeds errOutBinSphNum): k_sweep leaves one (bins, largest population) record per window, added up here.
-__global__ __launch_bounds__(256) void k_bin_stats_final(const uint2* __restrict__ perBlock, uint32_t nBlocks, DetectCounters* ctr) {
+// (with the segmented arena the workgroups of k_compact_keys do this on the side; the kernel is the small arena's)
+__device__ void bin_stats_block(const uint2* __restrict__ perBlock, uint32_t nBlocks, uint32_t block, DetectCounters* ctr) {
     __shared__ uint32_t sHeads[4], sPop[4];
     uint32_t heads = 0, pop = 0;
     // a workgroup per 2048 records, eight independent loads in flight per thread; one pair of atomics per workgroup (a few dozen
     // in all: same-address atomics serialise at ~12 ns each)
     {
-        const uint32_t i0 = blockIdx.x * 2048u;
+        const uint32_t i0 = block * 2048u;
         uint2 v[8];
 #pragma unroll
         for (uint32_t k = 0; k < 8; k++) {
@@ -722,6 +820,10 @@ __global__ __launch_bounds__(256) void k_bin_stats_final(const uint2* __restrict
         if (m > 1)
             atomicMax(&ctr->maxInBin, m);
     }
+    __syncthreads();  // (a workgroup may come again for another block)
+}
+__global__ __launch_bounds__(256) void k_bin_stats_final(const uint2* __restrict__ perBlock, uint32_t nBlocks, DetectCounters* ctr) {
+    bin_stats_block(perBlock, nBlocks, blockIdx.x, ctr);
 }
 
 // Second half of the contact-key sort.  The radix sort orders the keys by their upper part only (sphere A, type class: the
@@ -756,9 +858,17 @@ __global__ __launch_bounds__(256) void k_segment_rank_sort(uint32_t n, const uin
 // (rearrangeContactWildcards); the per-sphere linear search becomes a binary search because both
 // lists are key-sorted.
 // ---------------------------------------------------------------------------
+// On the side it zeroes what the list builders enqueued after it on the same stream count into (`zero`: nZero words, any length:
+// the workgroups stride over them) -- two or three fills of a few dozen bytes to a few dozen KB cost 5 us each as dispatches.
 __global__ __launch_bounds__(256) void k_history(uint32_t nNew, const uint64_t* __restrict__ newKeys, uint32_t nPrev,
-                                                 const uint64_t* __restrict__ prevKeys, uint32_t* __restrict__ mapping) {
+                                                 const uint64_t* __restrict__ prevKeys, uint32_t* __restrict__ mapping,
+                                                 uint32_t* __restrict__ zeroA, uint32_t nZeroA, uint32_t* __restrict__ zeroB,
+                                                 uint32_t nZeroB) {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint32_t i = c; i < nZeroA; i += gridDim.x * blockDim.x)
+        zeroA[i] = 0u;
+    for (uint32_t i = c; i < nZeroB; i += gridDim.x * blockDim.x)
+        zeroB[i] = 0u;
     if (c >= nNew)
         return;
     const uint64_t k = newKeys[c];
@@ -1216,7 +1326,8 @@ struct RangeCounters {
     unsigned int tileHaloSum;  // foreign owners staged by all fitting tiles together (the engine watches its mean: deme_order.inc)
     unsigned int nBigIn;         // closed tiles (deme_tile_step.h) whose halo, extended by their incoming contacts' owners, does not fit
     unsigned int tileMaxHaloIn;  // the largest closed tile's foreign owners
-    unsigned int pad[4];
+    unsigned long long nRemote;  // crossing contacts of all tiles = records of the tiles that fit (k_scan_small over tileRem)
+    unsigned int pad[2];
 };
 
 // start[o] = first index i with owner[i] >= o, for o = 0 .. nOwners (owner[] ascending): every element fills the owners that

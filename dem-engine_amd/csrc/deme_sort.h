@@ -53,21 +53,33 @@ __device__ inline unsigned digit_of(K k, unsigned shift, unsigned mask) {
 template <typename K>
 __global__ __launch_bounds__(THREADS) void k_count(const K* __restrict__ keys, uint32_t n, uint32_t nTiles, unsigned shift, unsigned nbits,
                                                    uint32_t* __restrict__ table) {
-    __shared__ uint32_t hist[RADIX];
+    // COPIES counters per digit, side by side, a lane adding to copy (lane % COPIES): equal digits of neighbouring lanes -- the rule in
+    // a pass over a list that is nearly in order -- do not meet on one address.  tools/sortbench, profiles/r08/sort_ab.txt: 3 to 7 us
+    // a sort ahead of one copy and level with a copy per wavefront; one add per group of equal digits found by ballots is far behind.
+    // (The tile's keys are loaded before the first add: eight loads in flight, none waiting behind an atomic.)
+    constexpr unsigned COPIES = 4;
+    __shared__ uint32_t hist[COPIES * RADIX];
     const unsigned tid = threadIdx.x, tile = blockIdx.x, mask = (1u << nbits) - 1u;
-    if (tid < RADIX)
-        hist[tid] = 0;
+    for (unsigned d = tid; d < COPIES * RADIX; d += THREADS)
+        hist[d] = 0;
     __syncthreads();
     const uint32_t base = tile * TILE + tid;
+    K k[KPT];
 #pragma unroll
-    for (unsigned i = 0; i < KPT; i++) {
-        const uint32_t idx = base + i * THREADS;
-        if (idx < n)
-            atomicAdd(&hist[digit_of(keys[idx], shift, mask)], 1u);
-    }
+    for (unsigned i = 0; i < KPT; i++)
+        k[i] = base + i * THREADS < n ? keys[base + i * THREADS] : K(0);
+#pragma unroll
+    for (unsigned i = 0; i < KPT; i++)
+        if (base + i * THREADS < n)
+            atomicAdd(&hist[digit_of(k[i], shift, mask) * COPIES + tid % COPIES], 1u);
     __syncthreads();
-    if (tid <= mask)
-        table[(size_t)tid * nTiles + tile] = hist[tid];
+    if (tid <= mask) {
+        uint32_t c = 0;
+#pragma unroll
+        for (unsigned j = 0; j < COPIES; j++)
+            c += hist[tid * COPIES + j];
+        table[(size_t)tid * nTiles + tile] = c;
+    }
 }
 
 // row d of the table becomes its exclusive prefix; totals[d] the row's sum
