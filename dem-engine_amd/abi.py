@@ -220,6 +220,8 @@ def load_library():
         "deme_inspect_contact_counts": [_P, C.c_int, C.c_float, _P, C.c_size_t],
         "deme_multi_inspect_contacts": [_P, C.c_char_p, C.c_float, C.POINTER(DemeContactSums)],
         "deme_multi_inspect_contact_counts": [_P, C.c_char_p, C.c_float, _P, C.c_size_t],
+        "deme_inspect_tri_loads": [_P, C.c_float, C.c_uint32, C.c_uint32, _P, _P],
+        "deme_multi_inspect_tri_loads": [_P, C.c_float, C.c_uint32, C.c_uint32, _P, _P],
         "deme_query_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_scatter_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
@@ -243,6 +245,8 @@ def load_library():
         fn.restype = C.c_int
     lib.deme_sort_tile_keys.argtypes = []
     lib.deme_sort_tile_keys.restype = C.c_uint
+    lib.deme_tri_loads_block_rows.argtypes = []
+    lib.deme_tri_loads_block_rows.restype = C.c_uint
     lib.deme_halo_unique_id.argtypes = [_P]
     lib.deme_halo_unique_id.restype = C.c_int
     lib.deme_halo_group_create.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]
@@ -514,6 +518,7 @@ class Multi:
         self._ck(self.lib.deme_multi_build(self.h, C.byref(params), C.byref(scene), int(slabs_per_device), int(axis), float(halo),
                                            (1 if shared_free else 0) | (8 if caller_order else 0), int(a), int(flip_mask)), "deme_multi_build")
         self.n_owners = int(scene.nOwners)
+        self.n_tri = int(scene.nTri)
 
     def num_slabs(self):
         n = C.c_uint32(0)
@@ -721,6 +726,10 @@ class Multi:
                  "deme_multi_inspect_contact_counts")
         return out
 
+    def inspect_tri_loads(self, force_threshold=1e-12, first=0, count=None):
+        """deme_multi_inspect_tri_loads: Context.inspect_tri_loads of every slab's own list, the slabs' arrays added in slab order"""
+        return _inspect_tri_loads(self, self.lib.deme_multi_inspect_tri_loads, "deme_multi_inspect_tri_loads", force_threshold, first, count)
+
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied from the devices to the host since the run was created"""
         v = C.c_uint64(0)
@@ -812,6 +821,23 @@ def _ptr(a):
 def sort_tile_keys():
     """keys one workgroup of the project's radix sort takes (the sizes around which its tests place their cases)"""
     return int(load_library().deme_sort_tile_keys())
+
+
+def tri_loads_block_rows():
+    """sorted rows one workgroup of the per-triangle sum takes (inspect_tri_loads): a longer run is summed by several"""
+    return int(load_library().deme_tri_loads_block_rows())
+
+
+def _inspect_tri_loads(self, fn, name, force_threshold, first, count):
+    """the call both Context.inspect_tri_loads and Multi.inspect_tri_loads make"""
+    if count is None:
+        if getattr(self, "n_tri", None) is None:
+            raise ValueError(f"{name}: count is needed (this object has not seen the scene's triangle count)")
+        count = self.n_tri - int(first)
+    force = np.zeros((max(int(count), 0), 3), np.float64)
+    contacts = np.zeros(max(int(count), 0), np.uint32)
+    self._ck(fn(self.h, float(force_threshold), int(first), int(count), _ptr(force), _ptr(contacts)), name)
+    return force, contacts
 
 
 def sort_pairs_u32(keys, vals, begin_bit, end_bit, force_own=True, device=0):
@@ -922,6 +948,7 @@ class Context:
 
     def upload_scene(self, sc):
         self.n_owners, self.n_spheres = int(sc.nOwners), int(sc.nSpheres)
+        self.n_tri = int(sc.nTri)
         self._ck(self.lib.deme_upload_scene(self.h, C.byref(sc)), "deme_upload_scene")
 
     def upload_state(self, arrays):
@@ -1213,6 +1240,12 @@ class Context:
         self._ck(self.lib.deme_inspect_contact_counts(self.h, int(region), float(force_threshold), _ptr(out), out.size),
                  "deme_inspect_contact_counts")
         return out
+
+    def inspect_tri_loads(self, force_threshold=1e-12, first=0, count=None):
+        """deme_inspect_tri_loads: the contact load of the mesh triangles [first, first + count) (count None: to the last one),
+        summed over the current list on the device.  (force[n, 3] float64 -- the force ON each triangle, world frame --,
+        contacts[n] uint32: the counted sphere-mesh rows of each)"""
+        return _inspect_tri_loads(self, self.lib.deme_inspect_tri_loads, "deme_inspect_tri_loads", force_threshold, first, count)
 
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied to the host since the context was created (count read-backs, hit

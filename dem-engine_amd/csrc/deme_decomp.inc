@@ -1784,6 +1784,55 @@ int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, flo
     return DEME_OK;
 }
 
+// ---- contact loads per mesh triangle of a decomposed run (deme_tri_loads.h) -------------------------------------------------------------
+// Triangles carry the same ids on every slab, and a row whose sphere belongs to a ghost copy is not counted: every sphere-triangle
+// pair is counted by the one slab that owns the sphere's clump.  All slabs' passes are enqueued first, each on its device, then the
+// host takes the asked range slab by slab and adds the arrays in slab order.  (The pairsOnce refusal mirrors the contact
+// inspectors'; nothing sets pairsOnce on a deme_multi's groups today, so the branch is not reached.)
+int deme_multi_inspect_tri_loads(deme_multi* m, float thr, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts) {
+    const char* who = "deme_multi_inspect_tri_loads";
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    const SlabRef head = multi_slab(m, 0);
+    char msg[320];
+    if (int rc = tri_loads_args_refused(msg, who, thr, firstTri, nTris, head.c ? head.c->nTri : 0u, force, contacts))
+        return mfail(m, rc, "%s", msg);
+    if (!nTris)
+        return DEME_OK;
+    for (auto* g : m->groups)
+        if (g->pairsOnce)
+            return mfail(m, DEME_ERR_INVALID, "%s: the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab that "
+                         "does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            if (slab_records_refused(r))
+                return mfail(m, DEME_ERR_INVALID, "%s: %s", who, r.c->err.c_str());
+            return DEME_OK;
+        }))
+        return rc;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int { return tri_loads_launch(r.c, thr); }))
+        return rc;
+    std::vector<double> sumF(force ? (size_t)nTris * 3 : 0, 0.0), hf(sumF.size());
+    std::vector<uint32_t> sumN(contacts ? nTris : 0, 0u), hn(sumN.size());
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            if (int rc = tri_loads_fetch(r.c, firstTri, nTris, force ? hf.data() : nullptr, contacts ? hn.data() : nullptr))
+                return rc;
+            m->qHostBytes += (uint64_t)nTris * ((force ? 24 : 0) + (contacts ? 4 : 0));
+            for (size_t i = 0; i < sumF.size(); i++)
+                sumF[i] += hf[i];
+            for (size_t i = 0; i < sumN.size(); i++)
+                sumN[i] += hn[i];
+            return DEME_OK;
+        }))
+        return rc;
+    if (force)
+        memcpy(force, sumF.data(), sumF.size() * 8);
+    if (contacts)
+        memcpy(contacts, sumN.data(), sumN.size() * 4);
+    return DEME_OK;
+}
+
 // ---- moving the slab boundaries (load balance of a bed that drifts or piles up) --------------------------------------------------------
 // deme_halo_group_migrate keeps the boundaries where the plan put them.  deme_multi_rebalance recomputes them from the clumps'
 // CURRENT coordinates -- equal counts again, snapped to bin faces like the plan's -- and lets the same migration move the clumps that

@@ -49,6 +49,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_resize.h"
 #include "deme_query.h"
 #include "deme_contact_inspect.h"
+#include "deme_tri_loads.h"
 #include "deme_sort.h"
 
 using namespace deme_dev;
@@ -134,6 +135,9 @@ struct deme_ctx {
     // contact inspectors (deme_contact_inspect.h): the mask and the side counts per owner slot, the blocks' partials with the result
     // behind them, the counts in the caller's (or global) ids; allocated by the first call and kept
     DevBuf ciMask, ciCounts, ciPartial, ciOut;
+    // triangle loads (deme_tri_loads.h): the (triangle, row) pairs before and after the sort, the sort's own scratch (never the
+    // detection's: an asynchronous detection may be sorting), the blocks' partials, the sums and counts per triangle; kept likewise
+    DevBuf tlTri[2], tlRow[2], tlTmp, tlPartial, tlForce, tlCount;
     std::map<std::string, int> regionBySource;  // deme_multi_inspect_contacts: a region string compiles once per slab context
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
@@ -1637,7 +1641,8 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
                      &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr, &c->qState,
-                     &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut};
+                     &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut, &c->tlTri[0], &c->tlTri[1], &c->tlRow[0], &c->tlRow[1],
+                     &c->tlTmp, &c->tlPartial, &c->tlForce, &c->tlCount};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -4772,6 +4777,105 @@ int deme_inspect_contact_counts(deme_ctx* c, int region, float thr, uint32_t* pe
     HIPCK(hipStreamSynchronize(c->stream));
     c->qHostBytes += 4ull * nO;
     memcpy(perOwner, h.data(), nO * 4);
+    return DEME_OK;
+}
+
+// ---- contact loads per mesh triangle (deme_tri_loads.h) -----------------------------------------------------------------------------
+namespace {
+// what deme_inspect_tri_loads refuses of its arguments, in the order it does (c null: a decomposed run asking before any slab is;
+// the text goes to msg)
+int tri_loads_args_refused(char (&msg)[320], const char* who, float thr, uint32_t firstTri, uint32_t nTris, uint32_t nTri, const void* force,
+                           const void* contacts) {
+    msg[0] = 0;
+    if (!std::isfinite(thr) || thr < 0.f)
+        snprintf(msg, sizeof msg, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    else if ((uint64_t)firstTri + nTris > nTri)
+        snprintf(msg, sizeof msg, "%s: triangles [%u, %llu) were asked for; the scene has %u", who, firstTri,
+                 (unsigned long long)firstTri + nTris, nTri);
+    else if (nTris && !force && !contacts)
+        snprintf(msg, sizeof msg, "%s: null output (force and contacts)", who);
+    return msg[0] ? DEME_ERR_INVALID : DEME_OK;
+}
+// The passes of one context, enqueued on its stream: the sums of every triangle are left in tlForce (3 doubles a triangle) and
+// tlCount.  Nothing the step reads is written.
+int tri_loads_launch(deme_ctx* c, float thr) {
+    const size_t n = c->haveList ? (size_t)c->nContacts : 0, nT = c->nTri;
+    const unsigned grid = grid_for(std::max<size_t>(n, 1), TRI_LOADS_BLOCK_ROWS);
+    if (ensure(c, c->tlForce, nT * 24) || ensure(c, c->tlCount, nT * 4))
+        return c->lastStatus;
+    HIPCK(hipMemsetAsync(c->tlForce.p, 0, nT * 24, c->stream));
+    HIPCK(hipMemsetAsync(c->tlCount.p, 0, nT * 4, c->stream));
+    if (!n)
+        return DEME_OK;
+    for (int k = 0; k < 2; k++)
+        if (ensure(c, c->tlTri[k], n * 4) || ensure(c, c->tlRow[k], n * 4))
+            return c->lastStatus;
+    if (ensure(c, c->tlPartial, (size_t)grid * 2 * sizeof(TriPartial)))
+        return c->lastStatus;
+    TriSelectArgs a{};
+    a.n = (uint32_t)n, a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
+    a.spheres = c->spheres.as<SphereRec>(), a.owners = c->owners.as<OwnerRec>();
+    a.nSpheres = c->nSpheres, a.nOwners = c->nOwners, a.nTri = c->nTri;
+    a.force = c->rec[0].as<float>(), a.thr2 = (double)thr * (double)thr;
+    a.tri = c->tlTri[0].as<uint32_t>(), a.row = c->tlRow[0].as<uint32_t>();
+    {
+        ScopedTimer t(c, "tri_loads_select", true);
+        hipLaunchKernelGGL(k_tri_select, dim3(grid_for(n)), dim3(256), 0, c->stream, a);
+    }
+    // (the key nTri of the uncounted rows takes part: one value more than the triangles)
+    const unsigned bits = bits_for((uint64_t)nT + 1, 32);
+    {
+        ScopedTimer t(c, "tri_loads_sort", true);
+        if (int rc = with_temp(c, c->tlTmp, [&](void* tmp, size_t& bytes) {
+                return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->tlTri[0].as<uint32_t>(), c->tlTri[1].as<uint32_t>(),
+                                                              c->tlRow[0].as<uint32_t>(), c->tlRow[1].as<uint32_t>(), n, n, 0, bits,
+                                                              DEME_SORT_OWN_FROM_RECORDS, c->stream);
+            }))
+            return rc;
+    }
+    ScopedTimer t(c, "tri_loads_sums", true);
+    hipLaunchKernelGGL(k_tri_seg_sums, dim3(grid), dim3(256), 0, c->stream, (uint32_t)n, (uint32_t)nT, c->tlTri[1].as<uint32_t>(),
+                       c->tlRow[1].as<uint32_t>(), c->rec[0].as<float>(), c->tlForce.as<double>(), c->tlCount.as<uint32_t>(),
+                       c->tlPartial.as<TriPartial>());
+    hipLaunchKernelGGL(k_tri_seg_final, dim3(1), dim3(256), 0, c->stream, 2u * grid, (uint32_t)nT, c->tlPartial.as<TriPartial>(),
+                       c->tlForce.as<double>(), c->tlCount.as<uint32_t>());
+    HIPCK(hipGetLastError());
+    return DEME_OK;
+}
+// the asked range of the sums tri_loads_launch left, to host arrays (either may be null); waits for the stream
+int tri_loads_fetch(deme_ctx* c, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts) {
+    if (force)
+        HIPCK(hipMemcpyAsync(force, c->tlForce.as<double>() + 3 * (size_t)firstTri, (size_t)nTris * 24, hipMemcpyDeviceToHost, c->stream));
+    if (contacts)
+        HIPCK(hipMemcpyAsync(contacts, c->tlCount.as<uint32_t>() + firstTri, (size_t)nTris * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+}  // namespace
+
+unsigned deme_tri_loads_block_rows(void) { return TRI_LOADS_BLOCK_ROWS; }
+
+int deme_inspect_tri_loads(deme_ctx* c, float thr, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts) {
+    if (int rc = check_ready(c))
+        return rc;
+    char msg[320];
+    if (int rc = tri_loads_args_refused(msg, "deme_inspect_tri_loads", thr, firstTri, nTris, c->nTri, force, contacts))
+        return fail(c, rc, "%s", msg);
+    if (!nTris)
+        return DEME_OK;
+    if (records_refused(c))
+        return fail(c, DEME_ERR_INVALID, "deme_inspect_tri_loads: %s", std::string(c->err).c_str());
+    if (int rc = tri_loads_launch(c, thr))
+        return rc;
+    std::vector<double> hf(force ? (size_t)nTris * 3 : 0);  // (the caller's arrays are written once the call cannot fail any more)
+    std::vector<uint32_t> hn(contacts ? nTris : 0);
+    if (int rc = tri_loads_fetch(c, firstTri, nTris, force ? hf.data() : nullptr, contacts ? hn.data() : nullptr))
+        return rc;
+    c->qHostBytes += (uint64_t)nTris * ((force ? 24 : 0) + (contacts ? 4 : 0));
+    if (force)
+        memcpy(force, hf.data(), hf.size() * 8);
+    if (contacts)
+        memcpy(contacts, hn.data(), hn.size() * 4);
     return DEME_OK;
 }
 

@@ -1086,7 +1086,60 @@ class DEMSolver {
         o << "\n\nCELL_TYPES " << total_f << std::endl;
         for (size_t j = 0; j < total_f; j++)
             o << "5 " << std::endl;
+        if (m_mesh_face_loads) {  // EnableMeshFaceLoadOutput: the contact load of every face behind the grid
+            std::vector<double> force(3 * total_f);
+            std::vector<uint32_t> count(total_f);
+            tri_loads(0, (uint32_t)total_f, force.data(), count.data());
+            o << "\n\nCELL_DATA " << total_f << "\nVECTORS contact_force float" << std::endl;
+            for (size_t j = 0; j < total_f; j++)
+                o << (float)force[3 * j] << " " << (float)force[3 * j + 1] << " " << (float)force[3 * j + 2] << std::endl;
+            o << "\nSCALARS contact_pressure float 1\nLOOKUP_TABLE default" << std::endl;
+            size_t j = 0;
+            for (size_t i = 0; i < m_meshes.size(); i++) {
+                const size_t owner = m_n_owners - m_meshes.size() + i;
+                std::vector<float3> nodes = m_meshes[i]->vertices;
+                for (float3& v : nodes) {
+                    rotate(v, sn.q[owner]);
+                    v = v + sn.com[owner];
+                }
+                for (auto& f : m_meshes[i]->faces) {
+                    o << face_pressure(nodes[(size_t)f[0]], nodes[(size_t)f[1]], nodes[(size_t)f[2]], &force[3 * j]) << std::endl;
+                    j++;
+                }
+            }
+            o << "\nSCALARS contact_count int 1\nLOOKUP_TABLE default" << std::endl;
+            for (size_t k = 0; k < total_f; k++)
+                o << count[k] << std::endl;
+        }
         flush(outfilename, o);
+    }
+    /// Not in the reference: WriteMeshFile appends CELL_DATA with the contact force on every face (world frame), the contact
+    /// pressure |F . n| / A and the number of contacts (deme_inspect_tri_loads, summed on the device).  Call before Initialize():
+    /// it turns contact recording on.  Off by default, and the file is then what it always was.
+    void EnableMeshFaceLoadOutput(bool on = true) { m_mesh_face_loads = on; }
+    /// |F . n| / A of a face with world nodes a, b, c under the force F (3 doubles); 0 for a degenerate face
+    static float face_pressure(const float3& a, const float3& b, const float3& c, const double* F) {
+        const double ux = (double)b.x - a.x, uy = (double)b.y - a.y, uz = (double)b.z - a.z;
+        const double vx = (double)c.x - a.x, vy = (double)c.y - a.y, vz = (double)c.z - a.z;
+        const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+        const double n2 = nx * nx + ny * ny + nz * nz;  // (2A)^2; F . n / |n| / (|n| / 2) = 2 F . n / |n|^2
+        if (!(n2 > 0.0))
+            return 0.f;
+        return (float)(std::fabs(F[0] * nx + F[1] * ny + F[2] * nz) * 2.0 / n2);
+    }
+    /// the first triangle of mesh `index` in the scene's numbering (meshes in load order)
+    size_t mesh_first_face(size_t index) const {
+        size_t first = 0;
+        for (size_t i = 0; i < index && i < m_meshes.size(); i++)
+            first += m_meshes[i]->faces.size();
+        return first;
+    }
+    /// deme_inspect_tri_loads / deme_multi_inspect_tri_loads with the shell's threshold (either output may be null)
+    void tri_loads(uint32_t first, uint32_t n, double* force, uint32_t* count) {
+        if (m_multi)
+            mcheck(deme_multi_inspect_tri_loads(m_multi, DEME_TINY_FLOAT_HOST, first, n, force, count));
+        else
+            check(deme_inspect_tri_loads(m_ctx, DEME_TINY_FLOAT_HOST, first, n, force, count));
     }
     /// UpdateClumps (API.h:1267): clumps added with AddClumps after Initialize() join the running simulation; old owners keep
     /// their state and the contact list keeps its history (new clumps are appended, so sphere ids are stable)
@@ -2424,6 +2477,7 @@ class DEMSolver {
     }
     unsigned int m_out_content = QUAT | ABSV;                                      // API.h:1418
     unsigned int m_cnt_out_content = OWNER | GEO_ID | FORCE | CNT_POINT | CNT_WILDCARD;  // API.h:1422-1424
+    bool m_mesh_face_loads = false;  // EnableMeshFaceLoadOutput
     struct Keep {  // scene arrays the writers need after Initialize
         std::vector<uint32_t> sphOwner, objOwner, triOwner;
         std::vector<uint16_t> sphComp, inert;
@@ -3118,7 +3172,7 @@ class DEMSolver {
             snprintf(nm, sizeof nm, "%04d", (int)i);
             m_keep.templateName[m_templates[i]->mark] = m_templates[i]->m_name.empty() ? std::string(nm) : m_templates[i]->m_name;
         }
-        if (m_cnt_out_content & (FORCE | CNT_POINT | NORMAL | TORQUE))
+        if ((m_cnt_out_content & (FORCE | CNT_POINT | NORMAL | TORQUE)) || m_mesh_face_loads)
             each_ctx([&](deme_ctx* c) { return deme_set_record_contacts(c, 1); });
         // restart: existing sphere-sphere contacts of the batches (geometry ids are batch-relative, Structs.h:857)
         {
@@ -3444,6 +3498,32 @@ class DEMTracker {
             nodes[i] = nodes[i] + deformation[i];
         UpdateMesh(nodes);
     }
+    /// Not in the reference: the contact force ON every face of the tracked mesh, in the world frame (deme_inspect_tri_loads: summed
+    /// per triangle on the device in fp64, rounded to float once), one entry per face in the mesh's face order
+    std::vector<float3> GetMeshFaceForces(size_t offset = 0) {
+        const std::vector<double> f = face_loads("GetMeshFaceForces", offset);
+        std::vector<float3> out(f.size() / 3);
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = make_float3((float)f[3 * i], (float)f[3 * i + 1], (float)f[3 * i + 2]);
+        return out;
+    }
+    /// ... the number of sphere-mesh contacts every face carries
+    std::vector<unsigned int> GetMeshFaceContactCounts() {
+        mesh_only("GetMeshFaceContactCounts");
+        std::vector<uint32_t> n(GetMesh()->faces.size());
+        m_sys->tri_loads((uint32_t)m_sys->mesh_first_face(m_index), (uint32_t)n.size(), nullptr, n.data());
+        return std::vector<unsigned int>(n.begin(), n.end());
+    }
+    /// ... and the contact pressure |F . n| / A per face, normal and area from the face's current world nodes (0 for a degenerate face)
+    std::vector<float> GetMeshFacePressures() {
+        const std::vector<double> f = face_loads("GetMeshFacePressures", 0);
+        const std::vector<float3> nodes = GetMeshNodesGlobal();
+        const auto& faces = GetMesh()->faces;
+        std::vector<float> out(faces.size());
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = DEMSolver::face_pressure(nodes[(size_t)faces[i][0]], nodes[(size_t)faces[i][1]], nodes[(size_t)faces[i][2]], &f[3 * i]);
+        return out;
+    }
     /// the mesh a mesh tracker follows (AuxClasses.h:310)
     std::shared_ptr<DEMMeshConnected>& GetMesh() {
         if (m_kind != 2)
@@ -3478,6 +3558,17 @@ class DEMTracker {
             flat[3 * k] = v[k].x, flat[3 * k + 1] = v[k].y, flat[3 * k + 2] = v[k].z;
         m_sys->add_owner_acc(GetOwnerID(0), (uint32_t)m_n, linear ? flat.data() : nullptr,
                                         linear ? nullptr : flat.data());
+    }
+    void mesh_only(const char* call) const {
+        if (m_kind != 2)
+            throw std::runtime_error(std::string(call) + " needs a tracker of a mesh");
+    }
+    std::vector<double> face_loads(const char* call, size_t offset) {  // 3 doubles per face of the tracked mesh
+        mesh_only(call);
+        in_range(offset);
+        std::vector<double> f(3 * GetMesh()->faces.size());
+        m_sys->tri_loads((uint32_t)m_sys->mesh_first_face(m_index), (uint32_t)(f.size() / 3), f.data(), nullptr);
+        return f;
     }
     std::vector<bodyID_t> all_owner_ids() const { return first_owner_ids(m_n); }
     std::vector<bodyID_t> first_owner_ids(size_t n) const {  // the first min(n, all) tracked owners

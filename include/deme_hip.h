@@ -511,9 +511,32 @@ typedef struct DemeContactSums {
 } DemeContactSums;
 int deme_inspect_contacts(deme_ctx* ctx, int regionId, float forceThreshold, DemeContactSums* out);
 int deme_inspect_contact_counts(deme_ctx* ctx, int regionId, float forceThreshold, uint32_t* perOwner, size_t cap);
+/* Contact loads per mesh triangle (no counterpart in the reference): which faces carry the load, summed over the current contact
+ * list on the device.  The rows are those deme_download_contacts / deme_download_contact_records give.
+ *   A row is COUNTED when it is a sphere-mesh row (DEME_SPHERE_MESH_CONTACT) whose B is a triangle id < nTri, the owner of sphere
+ *   A is no ghost copy (a slab of a decomposed run), and (double)fx^2 + (double)fy^2 + (double)fz^2 >= (double)forceThreshold^2,
+ *   f the recorded force (record 0; the torque-only force takes no part) -- the test deme_inspect_contacts makes.  With a threshold
+ *   of 0 every such row of the list counts, rows with zero force included.
+ *   A counted row adds -f to its triangle -- the force ON the triangle, in the world frame; deme_inspect_contacts gives side B the
+ *   same sign -- and 1 to the triangle's count.  The force sum is fp64 over the fp32 records.  A triangle without a counted row
+ *   gets zeros.
+ * The order of every floating-point addition is fixed by the list and the grid (no floating-point atomics): two calls on the same
+ * state give the same bits.
+ * force: 3 doubles per asked triangle; contacts: one count per asked triangle; either may be NULL.  Only the asked range
+ * [firstTri, firstTri + nTris) comes to the host: 24 + 4 bytes per asked triangle for the columns asked for, added to
+ * deme_query_host_bytes.  nTris == 0 returns DEME_OK and launches nothing.
+ * Read-only: no reduction of the step is launched; the list, the prescriptions and the step's buffers stay as they are.
+ * Refused with DEME_ERR_INVALID and nothing written: a threshold that is negative or not finite; a range beyond the scene's
+ * triangles; both outputs NULL while nTris > 0; recording off or a seeded list (as deme_download_contact_records).
+ * deme_tri_loads_block_rows: the sorted rows one workgroup of the segmented sum takes (a triangle with more rows than that is
+ * summed by several workgroups). */
+int deme_inspect_tri_loads(deme_ctx* ctx, float forceThreshold, uint32_t firstTri, uint32_t nTris, double* force /* 3 per triangle, or NULL */,
+                           uint32_t* contacts /* 1 per triangle, or NULL */);
+unsigned deme_tri_loads_block_rows(void);
 
 /* timing of the kernels this library launched (HIP events on the context stream);
- * names: "calc_forces", "integrate", "detect"; returns avg ms per launch since last reset */
+ * names: "calc_forces", "integrate", "detect", and the passes of deme_inspect_tri_loads "tri_loads_select", "tri_loads_sort",
+ * "tri_loads_sums"; returns avg ms per launch since last reset */
 int deme_kernel_time_ms(deme_ctx* ctx, const char* name, double* avg_ms, uint64_t* launches);
 int deme_kernel_time_reset(deme_ctx* ctx);
 /* enable = 0: off; n > 0: every n-th launch of each timed kernel is bracketed with events (an event pair costs ~3 us of
@@ -761,6 +784,13 @@ int deme_multi_inspect_values(deme_multi* m, uint32_t quantity, float* out, size
  * deme_multi_query_host_bytes: 88 per slab, or 4 per global owner and slab. */
 int deme_multi_inspect_contacts(deme_multi* m, const char* regionCode /* NULL or blank: everywhere */, float forceThreshold, DemeContactSums* out);
 int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, float forceThreshold, uint32_t* perOwnerGlobal, size_t cap);
+/* deme_inspect_tri_loads for a decomposed run.  Triangles carry the same ids on every slab; every slab sums its own list on its
+ * device, and since a row whose sphere belongs to a ghost copy is not counted, each sphere-triangle pair is counted by exactly one
+ * slab.  The host adds the slabs' arrays in slab order.  The call waits for the run (deme_multi_sync).  Refused as the single-context
+ * call is (a slab without recording, or whose list is a seed).  A run that evaluates every cross-cut contact once
+ * (deme_halo_group_set_cross_contacts) would be refused too; no call of this interface puts a deme_multi into that mode today, so
+ * that refusal cannot be met yet.  Bytes, added to deme_multi_query_host_bytes: 24 + 4 per asked triangle and slab. */
+int deme_multi_inspect_tri_loads(deme_multi* m, float forceThreshold, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts);
 /* deme_add_owner_acc by GLOBAL owner id: a clump's entry goes to the slab that owns it, a replicated owner's to every slab */
 int deme_multi_add_owner_acc(deme_multi* m, uint32_t owner, uint32_t n, const float* acc, const float* angAcc);
 /* the visible HIP devices (0 and DEME_OK where there is none: what the constructors check ids against) */
