@@ -4,6 +4,9 @@ Written from the formulas as this repository states them (dem-engine_amd/csrc/de
 hertz_frictionless, side_contribution; oracle/deme_oracle.cpp: spheres_overlap, sphere_entity, calc_forces), with every
 operation in float64 -- numpy's sqrt and / are correctly rounded.  Inputs are the fp32 / codec values the kernels read, widened.
 tests/test_contact_zoo.py compares the oracle (fp32 reference arithmetic) and the HIP kernels with it contact by contact.
+The sphere-triangle kind (KIND_TRI, tests/test_triangle_zoo.py) is written from the closest point on a triangle as Ericson states
+it (Real-Time Collision Detection 5.1.5), not from csrc/deme_mesh.h: face region -> face normal and depth r - h, edge or vertex
+region -> the direction from the closest point to the centre and depth r - distance; the contact point is the closest point.
 
 Errors are measured relative to the per-contact SCALE  s = |k_n d| + |g_n v_n| + |k_t| |d_t| + |g_t| |v_t|  (the sum of the sizes
 of the spring and damping terms), not to |F|: F is a sum of terms that cancel, by design in the separating class.
@@ -13,7 +16,7 @@ import numpy as np
 TINY = 1e-12          # DEME_TINY_FLOAT: the |tangential force| and |v_rot| guards (1e-24 on the squares in the fast kernels)
 HUGE_RADIUS = float(np.float32(1e15))  # the radius an analytical object enters the model with
 TWO_SQRT56 = 1.825741858350554
-KIND_SPHERE, KIND_PLANE, KIND_CYL = 0, 1, 2
+KIND_SPHERE, KIND_PLANE, KIND_CYL, KIND_TRI = 0, 1, 2, 3
 
 
 def rot_matrix(q_wxyz):
@@ -86,8 +89,27 @@ def rolling_clock(E_cnt, beta, m_eff, rA, rB):
     return d, tc
 
 
+def closest_point_on_triangle(A, B, C, P):
+    """Ericson, Real-Time Collision Detection 5.1.5 (as tests/test_independent_pins.py states it), vectorised: the point of the
+    triangle closest to P and its Voronoi region: 0 face, 1 / 2 / 3 vertex A / B / C, 4 / 5 / 6 edge AB / AC / BC"""
+    ab, ac, bc = B - A, C - A, C - B
+    ap, bp, cp = P - A, P - B, P - C
+    d1, d2, d3, d4, d5, d6 = _dot(ab, ap), _dot(ac, ap), _dot(ab, bp), _dot(ac, bp), _dot(ab, cp), _dot(ac, cp)
+    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    conds = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+             (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0)]
+    region = np.select(conds, [1, 2, 4, 3, 5, 6], 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = 1.0 / (va + vb + vc)
+        pts = [A, B, A + (d1 / (d1 - d3))[:, None] * ab, C, A + (d2 / (d2 - d6))[:, None] * ac,
+               B + ((d4 - d3) / ((d4 - d3) + (d5 - d6)))[:, None] * bc, A + (vb * den)[:, None] * ab + (vc * den)[:, None] * ac]
+    q = np.select([c[:, None] for c in conds], pts[:6], pts[6])
+    return q, region
+
+
 def geometry(c):
-    """narrow phase in float64: touching, depth, normal (B2A), contact point, the owners' rotation matrices"""
+    """narrow phase in float64: touching, depth, normal (B2A), contact point, the owners' rotation matrices; for a triangle
+    also the Voronoi region of the closest point and the signed height h of the sphere's centre over the face"""
     n = len(c["rA"])
     RA, RB = rot_matrix(c["qA"]), rot_matrix(c["qB"])
     bodyA = c["posA"] + _mv(RA, c["relA"])
@@ -120,14 +142,35 @@ def geometry(c):
         nrm[cy], depth[cy] = u, dep
         cp[cy] = bodyA[cy] - u * (c["rA"][cy] - dep / 2.0)[:, None]
     touching = ~(depth < -c["extra"])
-    return dict(touching=touching, depth=depth, normal=nrm, cp=cp, RA=RA, RB=RB)
+    region, height = np.full(n, -1), np.full(n, np.nan)
+    tr = kind == KIND_TRI
+    if tr.any():  # sphere against one triangle: c["tri"] (n, 3, 3) holds the three nodes in the mesh owner's frame
+        N = c["posB"][tr][:, None, :] + np.einsum("nij,nkj->nki", RB[tr], c["tri"][tr])
+        A, B, C, P, r = N[:, 0], N[:, 1], N[:, 2], bodyA[tr], c["rA"][tr]
+        q, reg = closest_point_on_triangle(A, B, C, P)
+        fn = np.cross(B - A, C - A)
+        fn /= _len(fn)[:, None]
+        h = _dot(P - A, fn)
+        d = P - q
+        dist = _len(d)
+        face = reg == 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = np.where(face[:, None], fn, d / dist[:, None])
+        dep = np.where(face, r - h, r - dist)
+        nrm[tr], depth[tr], cp[tr], region[tr], height[tr] = u, dep, q, reg, h
+        # the extra margin counts on the positive side only; a sphere through the plane of the face with its centre a radius or
+        # more away from that plane is no contact (the two-sided test of the reference's narrow phase)
+        touching[tr] = ~((-dep > c["extra"][tr]) | ((dep > 0) & (np.abs(h) >= r)))
+    return dict(touching=touching, depth=depth, normal=nrm, cp=cp, RA=RA, RB=RB, region=region, height=height)
 
 
 def contact64(c, h, model="hertz"):
     """One contact evaluation per row of `c` (a dict of float64 arrays):
       posA, posB (n,3) decoded owner positions; qA, qB (n,4) w x y z; vA, vB; wA, wB body-frame angular velocities; mA, mB;
-      relA, rA: A's component; kind (0 sphere, 1 plane, 2 cylinder), relB, rB (sphere: component; else the object's position in
-      its owner's frame and HUGE_RADIUS), dirB, sizeB, signB (object direction, cylinder radius, +1 inward / -1 outward);
+      relA, rA: A's component; kind (0 sphere, 1 plane, 2 cylinder, 3 triangle), relB, rB (sphere: component; else the object's
+      position in its owner's frame and HUGE_RADIUS; triangle: zero and HUGE_RADIUS), dirB, sizeB, signB (object direction, cylinder
+      radius, +1 inward / -1 outward); tri (n,3,3), only where a triangle occurs: its nodes in the frame of the mesh owner, which
+      is the B side (posB, qB, vB, wB, mB);
       E_cnt, G_cnt, beta, mu, Crr: the material-pair entry; hist (n,4): delta_tan x/y/z, delta_time; extra: family extra margin.
     Returns a dict: touching, depth, normal, F (force on A), T (torque-only force), PA, PB (contact point in A's / B's body
     frame), hist (new), label, s (scale), kt, and the distances to the discontinuous thresholds (ft, vrot, clock, tc, d_coeff)."""
@@ -138,7 +181,7 @@ def contact64(c, h, model="hertz"):
     PB = _mtv(RB, g["cp"] - c["posB"])
     F, T, hist = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 4))
     s, kt_out = np.zeros(n), np.zeros(n)
-    ft_out, vrot_out = np.full(n, np.nan), np.full(n, np.nan)
+    ft_out, vrot_out, ftmax_out = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
     clock_out, tc_out, dco_out = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
     label = np.empty(n, dtype=object)
     label[~touching] = "apart"
@@ -200,11 +243,13 @@ def contact64(c, h, model="hertz"):
             T[i] = tq
             hist[i, :3], hist[i, 3] = dt, clock
             ft_out[i] = np.where(has_t, ft, np.nan)
+            ftmax_out[i] = np.where(has_t, ft_max, np.nan)
             vrot_out[i] = np.where(roll, vmag, np.nan)
             clock_out[i], tc_out[i], dco_out[i] = np.where(has_r, clock, np.nan), np.where(has_r, tc, np.nan), np.where(has_r, dco, np.nan)
         F[i], s[i], label[i] = f, sc, lab
     return dict(touching=touching, depth=depth, normal=nrm, F=F, T=T, PA=PA, PB=PB, hist=hist, label=label, s=s, kt=kt_out,
-                ft=ft_out, vrot=vrot_out, clock=clock_out, tc=tc_out, d_coeff=dco_out, RA=RA, RB=RB)
+                ft=ft_out, vrot=vrot_out, clock=clock_out, tc=tc_out, d_coeff=dco_out, RA=RA, RB=RB,
+                region=g["region"], height=g["height"], ft_max=ftmax_out)
 
 
 def owner_sums64(out, ownerA, ownerB, n_owners, mass, moi, mB_side, gravity=(0.0, 0.0, 0.0)):

@@ -484,7 +484,7 @@ def design_history(c, seed=5):
     return hist.astype(np.float32)
 
 
-def class_errors(x, ref, c):
+def class_errors(x, ref, c, classes=CLASSES):
     """per designed class: the largest |x - ref| relative to the contact's scale s (contact points: metres).  x: dict with F, T,
     PA, PB and, for the full model, hist"""
     s = ref["s"]
@@ -500,7 +500,7 @@ def class_errors(x, ref, c):
             eW = np.abs(x["hist"][:, 3] - ref["hist"][:, 3]) / np.maximum(ref["hist"][:, 3], H)
     ePA = np.abs(x["PA"] - ref["PA"]).max(1)
     ePB = np.abs(x["PB"] - ref["PB"]).max(1)
-    for cls in CLASSES:
+    for cls in classes:
         k = c["cls"] == cls
         kl = k & live
         g = lambda e, m: float(e[m].max()) if m.any() else 0.0
@@ -512,7 +512,7 @@ def class_errors(x, ref, c):
 
 def run_sides(pkg, z, sides, model):
     """One call sequence for every side (contexts and oracle sims): detect, migrate, seed the history, one force evaluation.
-    Returns the float64 inputs and the per-side results."""
+    Returns the float64 inputs and the per-side results.  (A zoo of another module brings its own gather_inputs.)"""
     for s in sides:
         s.set_margins(z.margins)
         s.detect()
@@ -520,7 +520,7 @@ def run_sides(pkg, z, sides, model):
     lists = [s.contacts() for s in sides]
     for l in lists[1:]:
         assert all(np.array_equal(a, b) for a, b in zip(l[:3], lists[0][:3])), "contact lists differ"
-    c = gather_inputs(pkg, z, lists[0], np.zeros((len(lists[0][0]), 4)))
+    c = getattr(z, "gather_inputs", gather_inputs)(pkg, z, lists[0], np.zeros((len(lists[0][0]), 4)))
     hist = design_history(c) if model == "hertz" else np.zeros((len(lists[0][0]), 4), np.float32)
     c["hist"] = hist.astype(np.float64)
     res = []
@@ -724,16 +724,19 @@ def _fast_bounds(e):
     return {cls: {q: min(FACTOR * max(e[cls][q], U32), CEILING) for q in ("F", "T", "H", "W")} for cls in CLASSES}
 
 
-def _owner_fails(tag, rg, z, c, ref, own):
+def _owner_fails(tag, rg, z, c, ref, own, tight=None):
     """a / alpha per owner against the float64 sums, relative to the owner's own sum of s / m (s |r| / MOI); and, for
-    every contact, A's and B's contributions equal and opposite"""
+    every contact, A's and B's contributions equal and opposite.  tight: the owners held to the per-owner bound (default: the
+    clumps); the others sum hundreds of terms and keep the suite's 1e-3 tree bound"""
     fails = []
     n = z.n_clumps
+    if tight is None:
+        tight = np.arange(len(own["sa"])) < n
     ba = min(FACTOR * max(own["e_a"], U32), CEILING)
     bl = min(FACTOR * max(own["e_al"], U32), CEILING)
     with np.errstate(divide="ignore", invalid="ignore"):
-        ea = np.where(own["sa"] > 0, np.abs(rg["a"] - own["a"]).max(1) / own["sa"], np.abs(rg["a"]).max(1))[:n]
-        el = np.where(own["sl"] > 0, np.abs(rg["al"] - own["al"]).max(1) / own["sl"], np.abs(rg["al"]).max(1))[:n]
+        ea = np.where(own["sa"] > 0, np.abs(rg["a"] - own["a"]).max(1) / own["sa"], np.abs(rg["a"]).max(1))[tight]
+        el = np.where(own["sl"] > 0, np.abs(rg["al"] - own["al"]).max(1) / own["sl"], np.abs(rg["al"]).max(1))[tight]
     record_measured(f"test_contact_zoo {tag} per owner", a=float(ea.max()), alpha=float(el.max()), bound_a=ba, bound_alpha=bl)
     if ea.max() > ba:
         fails.append((tag, "owner a", float(ea.max()), ba, int(ea.argmax())))
@@ -749,13 +752,13 @@ def _owner_fails(tag, rg, z, c, ref, own):
     IA, IB = c["moi"][oA], c["moi"][oB]
     fA = (rg["a"][oA] - (own["a"][oA] - aA)) * mA[:, None]
     fB = (rg["a"][oB] - (own["a"][oB] - aB)) * mB[:, None]
-    bA, bB = np.where(oA >= n, 1e-3, ba), np.where(oB >= n, 1e-3, ba)
+    bA, bB = np.where(tight[oA], ba, 1e-3), np.where(tight[oB], ba, 1e-3)
     lim = bA * own["sa"][oA] * mA + bB * own["sa"][oB] * mB
     en = np.abs(fA + fB).max(1)
     tA = m64._mv(ref["RA"], (rg["al"][oA] - (own["al"][oA] - alA)) * IA)
     tB = m64._mv(ref["RB"], (rg["al"][oB] - (own["al"][oB] - alB)) * IB)
     want = np.cross(c["posB"] - c["posA"], fA + ref["T"])
-    lA, lB = np.where(oA >= n, 1e-3, bl), np.where(oB >= n, 1e-3, bl)
+    lA, lB = np.where(tight[oA], bl, 1e-3), np.where(tight[oB], bl, 1e-3)
     limt = lA * own["sl"][oA] * IA.max(1) + lB * own["sl"][oB] * IB.max(1)
     et = np.abs(tA + tB - want).max(1)
     live = (lim > 0) & (limt > 0)  # (a contact of two owners without any force: both sides are exactly zero, or the checks below fail)
