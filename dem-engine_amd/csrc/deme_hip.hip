@@ -634,6 +634,7 @@ int status_to_error(deme_ctx* c, uint32_t st) {
 int do_margins(deme_ctx* c, uint32_t drift) {
     HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->stream));
     c->ctrFresh = true;
+    if (c->nOwners)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
     hipLaunchKernelGGL(k_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp, c->owners.as<OwnerRec>(),
                        drift, c->ctr.as<DetectCounters>());
     return DEME_OK;
@@ -1519,9 +1520,11 @@ int launch_integrate(deme_ctx* c, AccFrom from, Owners who = Owners::All) {
             return c->lastStatus;
         GatherArgs ga = gather_args(c);
         ga.revPhase = who == Owners::NotWaiting ? 1u : 0u;
+        if (c->nOwners)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
         hipLaunchKernelGGL(k_integrate<true>, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp,
                            c->owners.as<OwnerRec>(), c->acc.as<AccRec>(), ga, pa);
     } else {
+        if (c->nOwners)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
         hipLaunchKernelGGL(k_integrate<false>, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp,
                            c->owners.as<OwnerRec>(), c->acc.as<AccRec>(), gather_args(c), pa);
     }
@@ -1541,6 +1544,7 @@ int launch_integrate_later(deme_ctx* c, const uint32_t* ids, uint32_t n) {
 
 // a/alpha of every owner from the current contributions (stand-alone force pass and state downloads)
 void launch_full_reduction(deme_ctx* c) {
+    if (c->nOwners)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
     hipLaunchKernelGGL(k_gather_acc, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp, gather_args(c),
                        c->owners.as<OwnerRec>(), c->acc.as<AccRec>());
     launch_reduce_heavy(c, false);
@@ -1972,6 +1976,7 @@ int deme_upload_scene(deme_ctx* c, const DemeScene* s) {
         if (int rc = ensure(c, c->stage, fl.size()))
             return rc;
         HIPCK(hipMemcpyAsync(c->stage.p, fl.data(), nO, hipMemcpyHostToDevice, c->stream));
+        if (nO)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
         hipLaunchKernelGGL(k_set_ghost_bits, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, c->owners.as<OwnerRec>(),
                            c->stage.as<uint8_t>());
         HIPCK(hipStreamSynchronize(c->stream));  // fl is a local
@@ -2177,6 +2182,8 @@ int deme_set_margins(deme_ctx* c, const float* m) {
     if (int rc = ensure(c, c->stage, std::max<size_t>(c->nOwners, 4) * 4))
         return rc;
     HIPCK(hipMemcpyAsync(c->stage.p, m, (size_t)c->nOwners * 4, hipMemcpyHostToDevice, c->stream));
+    if (c->nOwners)  // (a launch of no workgroups is an error, and one that stays in the runtime's state until the next call that looks
+                     // at it -- a sort of another context -- reports it)
     hipLaunchKernelGGL(k_set_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->nOwners,
                        c->owners.as<OwnerRec>(), c->stage.as<float>(), c->dp.o2e);
     HIPCK(hipStreamSynchronize(c->stream));
@@ -2412,6 +2419,7 @@ static int async_part1(deme_ctx* c, uint64_t* nC) {
     HIPCK(hipStreamWaitEvent(c->detStream, c->evSnap, 0));
     ScopedTimer tm(c, "detect_async_part1", true, c->detStream);
     HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->detStream));
+    if (c->nOwners)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
     hipLaunchKernelGGL(k_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, c->detStream, c->dp, c->ownersSnap.as<OwnerRec>(),
                        K + D, c->ctr.as<DetectCounters>());
     c->ctrFresh = true;
@@ -4770,6 +4778,7 @@ int deme_inspect_contact_counts(deme_ctx* c, int region, float thr, uint32_t* pe
         return c->lastStatus;
     if (int rc = contact_inspect_launch(c, region, thr, true, nullptr))
         return rc;
+    if (nO)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
     hipLaunchKernelGGL(k_contact_counts_out, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, c->ciCounts.as<uint32_t>(), c->dp.o2e,
                        (const uint32_t*)nullptr, c->ciOut.as<uint32_t>(), (uint32_t)nO);
     std::vector<uint32_t> h(nO);
