@@ -132,9 +132,115 @@ __device__ inline void stage_owner_records(const OwnerRec* owners, uint32_t owne
     q[0] = mine[0], q[1] = mine[1], q[2] = mine[2], q[3] = mine[3];
 }
 
-// MODEL 0: full Hertzian (history float4: delta_tan x/y/z, delta_time), 1: frictionless.  One thread per contact of the hot
-// classes (sphere-sphere, sphere-analytical).  Outputs: the A side's world-frame force and torque (the caller reduces them
-// over the owner's run), the B side's record is stored here.
+// THE CONTACT LAW OF THE FAST MODE, stated once: forces_fast_body below and tile_contact (deme_tile.h) read their tables and owner
+// records their own way and call these three.  k_tile_step needs two evaluations of one contact to agree bit for bit.
+//
+// Sphere pair.  dO: the owner-to-owner offset A - B; relA / relB: the spheres relative to their owners, world frame.  Out: the
+// normal n (B2A), the overlap, the contact point relative to B's owner, and whether the pair is within the grace margin.
+__device__ inline void sphere_pair_fast(double dOx, double dOy, double dOz, f3 relA, f3 relB, float rA, float rB, float extraMargin, f3& n,
+                                        float& depth, f3& rBv, bool& touching) {
+    // centre-to-centre vector in fp64, as the reference forms it (DEMHelperKernels.cuh:292-326)
+    const double dx = (dOx + (double)relA.x) - (double)relB.x;
+    const double dy = (dOy + (double)relA.y) - (double)relB.y;
+    const double dz = (dOz + (double)relA.z) - (double)relB.z;
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    // (the sum of the radii in fp64: rounded to fp32 it is off by up to 3e-8 of itself -- nothing for equal radii, whose sum is
+    // exact, but 5e-10 m between unequal ones, 1e-5 of a typical overlap: found on the polydisperse bed of configs[4])
+    const double sumRd = (double)rA + (double)rB;
+    const float sumR = (float)sumRd;
+    const double num = sumRd * sumRd - d2;  // > 0 iff the spheres overlap; no cancellation left after this
+    const float d2f = (float)d2;
+    const float inv = frsq(d2f);
+    const float dist = d2f * inv;
+    n = mk3((float)dx * inv, (float)dy * inv, (float)dz * inv);
+    depth = (float)num * frcp(sumR + dist);
+    touching = !(depth < -extraMargin);
+    // contact point = B's centre + (rB - depth / 2) n  (calcContactPoint), relative to the two owners
+    const float s = rB - 0.5f * depth;
+    rBv = mk3(relB.x + s * n.x, relB.y + s * n.y, relB.z + s * n.z);
+}
+
+// MODEL 0: full Hertzian (history float4: delta_tan x/y/z, delta_time), 1: frictionless.  For a contact within the grace margin.
+// rAv / rBv: the contact point relative to A's / B's owner; wA / wB: angular velocities in the WORLD frame.  Sets force (on A)
+// and torque_only where the spheres overlap -- the caller zeroes both --, and updates the history.
+template <int MODEL>
+__device__ inline void hertz_fast(MatPair mp, float h, float massA, float massB, float rA, float rB, float depth, f3 n, f3 rAv, f3 rBv,
+                                  f3 vA, f3 vB, f3 wA, f3 wB, float4& hist, f3& force, f3& torque_only) {
+    static_assert(MODEL == 0 || MODEL == 1, "the built-in models");
+    if (depth > 0.f) {
+        const f3 rotVelA = fcross(wA, rAv), rotVelB = fcross(wB, rBv);
+        const f3 velB2A = fsub(fadd(vA, rotVelA), fadd(vB, rotVelB));
+        // (fdot(velB2A, n) with its contraction stated: which of the first two products the compiler fuses changes with the function
+        // the line stands in, and these are the tile kernels' bits)
+        const float projection = __builtin_fmaf(velB2A.z, n.z, __builtin_fmaf(velB2A.x, n.x, velB2A.y * n.y));
+        const float mass_eff = massA * massB * frcp(massA + massB);
+        const float sqrt_Rd = fsqrt(depth * (rA * rB) * frcp(rA + rB));
+        const float Sn = 2.f * mp.E_cnt * sqrt_Rd;
+        const float k_n = 0.6666666666666667f * Sn;
+        const float gamma_n = 1.825741858350554f * mp.beta * fsqrt(Sn * mass_eff);
+        const float Fn = k_n * depth + gamma_n * projection;
+        force = fscale(Fn, n);
+        if (MODEL == 0) {
+            const f3 vrel_tan = faxpy(-projection, n, velB2A);
+            f3 delta_tan = faxpy(h, vrel_tan, mk3(hist.x, hist.y, hist.z));
+            delta_tan = faxpy(-fdot(delta_tan, n), n, delta_tan);
+            hist.w += h;
+            if (mp.Crr > 0.0f) {  // FullHertzianForceModel.cu:73-100
+                bool roll = true;
+                const float R_eff = fsqrt((rA * rB) * frcp(rA + rB));
+                const float kn_simple = 1.3333333333333333f * mp.E_cnt * fsqrt(R_eff);
+                const float gn_simple = -2.f * fsqrt(1.6666666666666667f * mass_eff * mp.E_cnt) * mp.beta * fsqrt(fsqrt(R_eff));
+                const float d_coeff = gn_simple * frcp(2.f * fsqrt(kn_simple * mass_eff));
+                if (d_coeff < 1.0f) {
+                    const float t_collision = 3.1415926535897932f * fsqrt(mass_eff * frcp(kn_simple * (1.f - d_coeff * d_coeff)));
+                    if (hist.w <= t_collision)
+                        roll = false;
+                }
+                if (roll) {
+                    const f3 v_rot = fsub(rotVelB, rotVelA);
+                    const float m2 = fdot(v_rot, v_rot);
+                    if (m2 > 1e-24f)
+                        torque_only = fscale(frsq(m2) * mp.Crr * fabsf(Fn), v_rot);
+                }
+            }
+            if (mp.mu > 0.0f) {
+                const float kt = 8.f * mp.G_cnt * sqrt_Rd;
+                const float gt = -1.825741858350554f * mp.beta * fsqrt(mass_eff * kt);
+                f3 tf = faxpy(-kt, delta_tan, fscale(-gt, vrel_tan));
+                const float ft2 = fdot(tf, tf);
+                if (ft2 > 1e-24f) {
+                    const float ft_max = fabsf(Fn) * mp.mu;  // |force| = |Fn| |n|
+                    if (ft2 > ft_max * ft_max) {
+                        tf = fscale(ft_max * frsq(ft2), tf);
+                        delta_tan = fscale(-frcp(kt), faxpy(gt, vrel_tan, tf));
+                    }
+                } else {
+                    tf = mk3(0, 0, 0);
+                }
+                force = fadd(force, tf);
+            }
+            hist.x = delta_tan.x, hist.y = delta_tan.y, hist.z = delta_tan.z;
+        }
+    } else if (MODEL == 0) {
+        hist = make_float4(0, 0, 0, 0);  // in the list, within the margin, not touching: the model resets its history
+    }
+}
+
+// General analytical object (a few per cent of the list, at the walls): the reference's own arithmetic.  PA / PB: the owners in any
+// common frame (only differences enter); dir: the object's direction, world frame.  dd: the overlap in fp64 -- the callers round it
+// and test it against the grace margin (the tile kernel once for this and for its plane shortcut).
+__device__ inline void sphere_anal_fast(d3 PA, d3 PB, f3 relA, f3 relB, f3 dir, float rA, uint32_t type, float size1, float normal, f3& n,
+                                        double& dd, f3& rAv, f3& rBv) {
+    const d3 bodyA{PA.x + (double)relA.x, PA.y + (double)relA.y, PA.z + (double)relA.z};
+    const d3 bodyB{PB.x + (double)relB.x, PB.y + (double)relB.y, PB.z + (double)relB.z};
+    d3 cp;
+    sphere_entity(bodyA, rA, type, bodyB, dir, size1, normal, 0.0f, cp, n, dd);
+    rAv = mk3((float)(cp.x - PA.x), (float)(cp.y - PA.y), (float)(cp.z - PA.z));
+    rBv = mk3((float)(cp.x - PB.x), (float)(cp.y - PB.y), (float)(cp.z - PB.z));
+}
+
+// One thread per contact of the hot classes (sphere-sphere, sphere-analytical).  Outputs: the A side's world-frame force and
+// torque (the caller reduces them over the owner's run), the B side's record is stored here.
 template <int MODEL>
 __device__ inline void forces_fast_body(const DevParams& p, const ForceArgs& a, const uint32_t c, const uint4 ci, const OwnerRec& OA,
                                         const OwnerRec& OB, float4& outA4, float2& outA2) {
@@ -178,27 +284,9 @@ __device__ inline void forces_fast_body(const DevParams& p, const ForceArgs& a, 
         rB = cB.w;
         massB = p.massProps[OB.inertiaOff].x;
         const f3 relB = rot_apply(RB, mk3(cB.x, cB.y, cB.z));
-        // centre-to-centre vector in fp64, as the reference forms it (DEMHelperKernels.cuh:292-326)
-        const double dx = (dOx + (double)relA.x) - (double)relB.x;
-        const double dy = (dOy + (double)relA.y) - (double)relB.y;
-        const double dz = (dOz + (double)relA.z) - (double)relB.z;
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        // (the sum of the radii in fp64: rounded to fp32 it is off by up to 3e-8 of itself -- nothing for equal radii, whose sum is
-        // exact, but 5e-10 m between unequal ones, 1e-5 of a typical overlap: found on the polydisperse bed of configs[4])
-        const double sumRd = (double)rA + (double)rB;
-        const float sumR = (float)sumRd;
-        const double num = sumRd * sumRd - d2;  // > 0 iff the spheres overlap; no cancellation left after this
-        const float d2f = (float)d2;
-        const float inv = frsq(d2f);
-        const float dist = d2f * inv;
-        n = mk3((float)dx * inv, (float)dy * inv, (float)dz * inv);
-        depth = (float)num * frcp(sumR + dist);
-        touching = !(depth < -extraMargin);
-        // contact point = B's centre + (rB - depth / 2) n  (calcContactPoint), relative to the two owners
-        const float s = rB - 0.5f * depth;
-        rBv = mk3(relB.x + s * n.x, relB.y + s * n.y, relB.z + s * n.z);
+        sphere_pair_fast(dOx, dOy, dOz, relA, relB, rA, rB, extraMargin, n, depth, rBv, touching);
         rAv = fsub(rBv, dO);
-    } else {  // sphere-analytical (a few per cent of the list, at the walls): the reference's own arithmetic
+    } else {
         const AnalObj ob = p.anal[ci.w];
         matB = ob.mat;
         rB = 1e15f;  // DEME_HUGE_FLOAT
@@ -208,75 +296,16 @@ __device__ inline void forces_fast_body(const DevParams& p, const ForceArgs& a, 
         d3 PA = decode_pos(OA.voxelID, OA.locX, OA.locY, OA.locZ, p), PB = decode_pos(OB.voxelID, OB.locX, OB.locY, OB.locZ, p);
         PA.x += p.LBFX, PA.y += p.LBFY, PA.z += p.LBFZ;
         PB.x += p.LBFX, PB.y += p.LBFY, PB.z += p.LBFZ;
-        const d3 bodyA{PA.x + (double)relA.x, PA.y + (double)relA.y, PA.z + (double)relA.z};
-        const d3 bodyB{PB.x + (double)relB.x, PB.y + (double)relB.y, PB.z + (double)relB.z};
-        d3 cp;
         double dd;
-        sphere_entity(bodyA, rA, ob.type, bodyB, dir, ob.size1, ob.normal, 0.0f, cp, n, dd);
+        sphere_anal_fast(PA, PB, relA, relB, dir, rA, ob.type, ob.size1, ob.normal, n, dd, rAv, rBv);
         depth = (float)dd;
         touching = !(dd < -(double)extraMargin);  // the list entry keeps its type; only the grace margin retires it
-        rAv = mk3((float)(cp.x - PA.x), (float)(cp.y - PA.y), (float)(cp.z - PA.z));
-        rBv = mk3((float)(cp.x - PB.x), (float)(cp.y - PB.y), (float)(cp.z - PB.z));
     }
     f3 force = mk3(0, 0, 0), torque_only = mk3(0, 0, 0);
     if (touching) {
-        if (depth > 0.f) {
-            const MatPair mp = p.matPair[matA * p.nMat + matB];
-            const f3 wA = frot_apply(RA, mk3(OA.wx, OA.wy, OA.wz)), wB = frot_apply(RB, mk3(OB.wx, OB.wy, OB.wz));  // world frame
-            const f3 rotVelA = fcross(wA, rAv), rotVelB = fcross(wB, rBv);
-            const f3 velB2A = fsub(fadd(mk3(OA.vx, OA.vy, OA.vz), rotVelA), fadd(mk3(OB.vx, OB.vy, OB.vz), rotVelB));
-            const float projection = fdot(velB2A, n);
-            const float mass_eff = massA * massB * frcp(massA + massB);
-            const float sqrt_Rd = fsqrt(depth * (rA * rB) * frcp(rA + rB));
-            const float Sn = 2.f * mp.E_cnt * sqrt_Rd;
-            const float k_n = 0.6666666666666667f * Sn;
-            const float gamma_n = 1.825741858350554f * mp.beta * fsqrt(Sn * mass_eff);
-            const float Fn = k_n * depth + gamma_n * projection;
-            force = fscale(Fn, n);
-            if (MODEL == 0) {
-                const f3 vrel_tan = faxpy(-projection, n, velB2A);
-                f3 delta_tan = faxpy(p.h, vrel_tan, mk3(hist.x, hist.y, hist.z));
-                delta_tan = faxpy(-fdot(delta_tan, n), n, delta_tan);
-                hist.w += p.h;
-                if (mp.Crr > 0.0f) {  // FullHertzianForceModel.cu:73-100
-                    bool roll = true;
-                    const float R_eff = fsqrt((rA * rB) * frcp(rA + rB));
-                    const float kn_simple = 1.3333333333333333f * mp.E_cnt * fsqrt(R_eff);
-                    const float gn_simple = -2.f * fsqrt(1.6666666666666667f * mass_eff * mp.E_cnt) * mp.beta * fsqrt(fsqrt(R_eff));
-                    const float d_coeff = gn_simple * frcp(2.f * fsqrt(kn_simple * mass_eff));
-                    if (d_coeff < 1.0f) {
-                        const float t_collision = 3.1415926535897932f * fsqrt(mass_eff * frcp(kn_simple * (1.f - d_coeff * d_coeff)));
-                        if (hist.w <= t_collision)
-                            roll = false;
-                    }
-                    if (roll) {
-                        const f3 v_rot = fsub(rotVelB, rotVelA);
-                        const float m2 = fdot(v_rot, v_rot);
-                        if (m2 > 1e-24f)
-                            torque_only = fscale(frsq(m2) * mp.Crr * fabsf(Fn), v_rot);
-                    }
-                }
-                if (mp.mu > 0.0f) {
-                    const float kt = 8.f * mp.G_cnt * sqrt_Rd;
-                    const float gt = -1.825741858350554f * mp.beta * fsqrt(mass_eff * kt);
-                    f3 tf = faxpy(-kt, delta_tan, fscale(-gt, vrel_tan));
-                    const float ft2 = fdot(tf, tf);
-                    if (ft2 > 1e-24f) {
-                        const float ft_max = fabsf(Fn) * mp.mu;  // |force| = |Fn| |n|
-                        if (ft2 > ft_max * ft_max) {
-                            tf = fscale(ft_max * frsq(ft2), tf);
-                            delta_tan = fscale(-frcp(kt), faxpy(gt, vrel_tan, tf));
-                        }
-                    } else {
-                        tf = mk3(0, 0, 0);
-                    }
-                    force = fadd(force, tf);
-                }
-                hist.x = delta_tan.x, hist.y = delta_tan.y, hist.z = delta_tan.z;
-            }
-        } else if (MODEL == 0) {
-            hist = make_float4(0, 0, 0, 0);  // in the list, within the margin, not touching: the model resets its history
-        }
+        const f3 wA = frot_apply(RA, mk3(OA.wx, OA.wy, OA.wz)), wB = frot_apply(RB, mk3(OB.wx, OB.wy, OB.wz));  // world frame
+        hertz_fast<MODEL>(p.matPair[matA * p.nMat + matB], p.h, massA, massB, rA, rB, depth, n, rAv, rBv, mk3(OA.vx, OA.vy, OA.vz),
+                          mk3(OB.vx, OB.vy, OB.vz), wA, wB, hist, force, torque_only);
         const f3 tot = fadd(force, torque_only);
         const f3 tA = fcross(rAv, tot);
         f3 tB = fcross(tot, rBv);  // = r_B x (-F)

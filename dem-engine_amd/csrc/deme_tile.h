@@ -192,8 +192,6 @@ __device__ inline void tile_stage(const DevParams& p, const float mass, const Ow
     else
         tile_stage_owner_m(p, mass, r, u0x, u0y, u0z, dst, rot);
 }
-template <int MODEL>
-__device__ inline TileOwner tile_read(const uint4* sOwn, uint32_t at, uint32_t rot);  // `at`: slot x the launch's record stride (TileArgs::rs16)
 __device__ inline TileOwner tile_read_owner(const uint4* sOwn, uint32_t at, uint32_t rot) {
     const uint4* q = sOwn + at + rot;
     const uint4 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4], f = sOwn[at + (rot ? 0u : 5u)];
@@ -209,12 +207,13 @@ __device__ inline TileOwner tile_read_owner(const uint4* sOwn, uint32_t at, uint
     o.wx = __uint_as_float(f.x), o.wy = __uint_as_float(f.y), o.wz = __uint_as_float(f.z);
     return o;
 }
-template <>
-__device__ inline TileOwner tile_read<0>(const uint4* sOwn, uint32_t at, uint32_t rot) { return tile_read_owner(sOwn, at, rot); }
-template <>
-__device__ inline TileOwner tile_read<1>(const uint4* sOwn, uint32_t at, uint32_t rot) { return tile_read_owner(sOwn, at, rot); }
-template <>
-__device__ inline TileOwner tile_read<2>(const uint4* sOwn, uint32_t at, uint32_t) { return tile_read_owner_user(sOwn, at); }
+template <int MODEL>
+__device__ inline TileOwner tile_read(const uint4* sOwn, uint32_t at, uint32_t rot) {  // `at`: slot x the launch's record stride (TileArgs::rs16)
+    if constexpr (MODEL == 2)
+        return tile_read_owner_user(sOwn, at);
+    else
+        return tile_read_owner(sOwn, at, rot);
+}
 
 // what only a run-time compiled model needs beside the staged records (MODEL 2; everything here that the user's statements do
 // not name is dead code after inlining)
@@ -235,9 +234,8 @@ struct TileRecOut {
     f3 torqueOnly, locA, locB;
 };
 
-// One contact of the hot classes between two staged owners.  Arithmetic: forces_fast_body (deme_force_fast.h), with the
-// owner-level quantities taken from the staged records.  Returns the world-frame force on A, the torques about A's and B's
-// centres, and the updated history.
+// One contact of the hot classes between two staged owners, by the contact law of deme_force_fast.h (sphere_pair_fast, sphere_anal_fast,
+// hertz_fast).  Returns the world-frame force on A, the torques about A's and B's centres, and the updated history.
 // The small tables a contact indexes per lane (components, material pairs, analytical objects, family margins) are copied to LDS
 // by every workgroup: a global load in the contact loop makes its wait drain everything that was issued before it -- the vector
 // memory counter retires in order -- and that is where the streams of the next rounds are in flight.
@@ -255,7 +253,6 @@ __device__ inline void tile_contact(const DevParams& p, const TileTables& T, con
     const uint32_t cls = (inf.x >> 20) & 3u;
     const float4 cA = T.comp[inf.y & 0xFFFFu];
     const uint32_t matA = (inf.x >> 24) & 15u;
-    // sphere offsets with the reference's own rounding (no contraction: deme_device.h), see forces_fast_body
     const RotM &RA = A.R, &RB = B.R;
     const f3 relA = rot_apply(RA, mk3(cA.x, cA.y, cA.z));
     const float rA = cA.w;
@@ -279,23 +276,7 @@ __device__ inline void tile_contact(const DevParams& p, const TileTables& T, con
         massB = B.mass;
         const f3 relB = rot_apply(RB, mk3(cB.x, cB.y, cB.z));
         relBw = relB;
-        const double dx = (dOx + (double)relA.x) - (double)relB.x;
-        const double dy = (dOy + (double)relA.y) - (double)relB.y;
-        const double dz = (dOz + (double)relA.z) - (double)relB.z;
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        // (the sum of the radii in fp64: rounded to fp32 it is off by up to 3e-8 of itself -- nothing for equal radii, whose sum is
-        // exact, but 5e-10 m between unequal ones, 1e-5 of a typical overlap: found on the polydisperse bed of configs[4])
-        const double sumRd = (double)rA + (double)rB;
-        const float sumR = (float)sumRd;
-        const double num = sumRd * sumRd - d2;
-        const float d2f = (float)d2;
-        const float inv = frsq(d2f);
-        const float dist = d2f * inv;
-        n = mk3((float)dx * inv, (float)dy * inv, (float)dz * inv);
-        depth = (float)num * frcp(sumR + dist);
-        touching = !(depth < -extraMargin);
-        const float s = rB - 0.5f * depth;
-        rBv = mk3(relB.x + s * n.x, relB.y + s * n.y, relB.z + s * n.z);
+        sphere_pair_fast(dOx, dOy, dOz, relA, relB, rA, rB, extraMargin, n, depth, rBv, touching);
         rAv = fsub(rBv, dO);
     } else {  // sphere-analytical: the reference's arithmetic in the tile's frame (only differences of positions enter)
         const AnalObj ob = T.anal[inf.y >> 16];
@@ -306,31 +287,23 @@ __device__ inline void tile_contact(const DevParams& p, const TileTables& T, con
         const f3 dir = rot_apply(RB, mk3(ob.rotx, ob.roty, ob.rotz));
         relBw = relB;
         userType = ob.type == 0u ? 11u : 13u;
+        double dd;
         if (ob.type == 0u) {  // a plane -- the walls of every box -- in a few lines (checkSphereEntityOverlap's plane branch,
             // DEMHelperKernels.cuh:459-478): half of a packed bed's tiles touch the floor, and the general branch below is 150
             // instructions that every wavefront with one wall contact among its 64 would execute
             const double px = (dOx + (double)relA.x) - (double)relB.x, py = (dOy + (double)relA.y) - (double)relB.y,
                          pz = (dOz + (double)relA.z) - (double)relB.z;
             const float dist = (float)(px * (double)dir.x + py * (double)dir.y + pz * (double)dir.z);
-            const double dd = (double)rA - (double)dist;
-            depth = (float)dd;
-            touching = !(dd < -(double)extraMargin);
+            dd = (double)rA - (double)dist;
             const float sOff = (float)((double)dist + dd / 2.0);
             n = dir;
             rAv = mk3(relA.x - dir.x * sOff, relA.y - dir.y * sOff, relA.z - dir.z * sOff);  // contact point = sphere centre - s n
             rBv = fadd(rAv, dO);
         } else {
-            const d3 PA{A.px, A.py, A.pz}, PB{B.px, B.py, B.pz};
-            const d3 bodyA{PA.x + (double)relA.x, PA.y + (double)relA.y, PA.z + (double)relA.z};
-            const d3 bodyB{PB.x + (double)relB.x, PB.y + (double)relB.y, PB.z + (double)relB.z};
-            d3 cp;
-            double dd;
-            sphere_entity(bodyA, rA, ob.type, bodyB, dir, ob.size1, ob.normal, 0.0f, cp, n, dd);
-            depth = (float)dd;
-            touching = !(dd < -(double)extraMargin);
-            rAv = mk3((float)(cp.x - PA.x), (float)(cp.y - PA.y), (float)(cp.z - PA.z));
-            rBv = mk3((float)(cp.x - PB.x), (float)(cp.y - PB.y), (float)(cp.z - PB.z));
+            sphere_anal_fast(d3{A.px, A.py, A.pz}, d3{B.px, B.py, B.pz}, relA, relB, dir, rA, ob.type, ob.size1, ob.normal, n, dd, rAv, rBv);
         }
+        depth = (float)dd;
+        touching = !(dd < -(double)extraMargin);
     }
     force = mk3(0, 0, 0);
     f3 torque_only = mk3(0, 0, 0);
@@ -385,63 +358,9 @@ __device__ inline void tile_contact(const DevParams& p, const TileTables& T, con
     }
 #endif
     if (touching) {
-        if (depth > 0.f) {
-            const float massA = A.mass;
-            const MatPair mp = T.mat[matA * p.nMat + matB];
-            const f3 rotVelA = fcross(mk3(A.wx, A.wy, A.wz), rAv), rotVelB = fcross(mk3(B.wx, B.wy, B.wz), rBv);
-            const f3 velB2A = fsub(fadd(mk3(A.vx, A.vy, A.vz), rotVelA), fadd(mk3(B.vx, B.vy, B.vz), rotVelB));
-            const float projection = fdot(velB2A, n);
-            const float mass_eff = massA * massB * frcp(massA + massB);
-            const float sqrt_Rd = fsqrt(depth * (rA * rB) * frcp(rA + rB));
-            const float Sn = 2.f * mp.E_cnt * sqrt_Rd;
-            const float k_n = 0.6666666666666667f * Sn;
-            const float gamma_n = 1.825741858350554f * mp.beta * fsqrt(Sn * mass_eff);
-            const float Fn = k_n * depth + gamma_n * projection;
-            force = fscale(Fn, n);
-            if (MODEL == 0) {
-                const f3 vrel_tan = faxpy(-projection, n, velB2A);
-                f3 delta_tan = faxpy(p.h, vrel_tan, mk3(hist.x, hist.y, hist.z));
-                delta_tan = faxpy(-fdot(delta_tan, n), n, delta_tan);
-                hist.w += p.h;
-                if (mp.Crr > 0.0f) {  // FullHertzianForceModel.cu:73-100
-                    bool roll = true;
-                    const float R_eff = fsqrt((rA * rB) * frcp(rA + rB));
-                    const float kn_simple = 1.3333333333333333f * mp.E_cnt * fsqrt(R_eff);
-                    const float gn_simple = -2.f * fsqrt(1.6666666666666667f * mass_eff * mp.E_cnt) * mp.beta * fsqrt(fsqrt(R_eff));
-                    const float d_coeff = gn_simple * frcp(2.f * fsqrt(kn_simple * mass_eff));
-                    if (d_coeff < 1.0f) {
-                        const float t_collision = 3.1415926535897932f * fsqrt(mass_eff * frcp(kn_simple * (1.f - d_coeff * d_coeff)));
-                        if (hist.w <= t_collision)
-                            roll = false;
-                    }
-                    if (roll) {
-                        const f3 v_rot = fsub(rotVelB, rotVelA);
-                        const float m2 = fdot(v_rot, v_rot);
-                        if (m2 > 1e-24f)
-                            torque_only = fscale(frsq(m2) * mp.Crr * fabsf(Fn), v_rot);
-                    }
-                }
-                if (mp.mu > 0.0f) {
-                    const float kt = 8.f * mp.G_cnt * sqrt_Rd;
-                    const float gt = -1.825741858350554f * mp.beta * fsqrt(mass_eff * kt);
-                    f3 tf = faxpy(-kt, delta_tan, fscale(-gt, vrel_tan));
-                    const float ft2 = fdot(tf, tf);
-                    if (ft2 > 1e-24f) {
-                        const float ft_max = fabsf(Fn) * mp.mu;
-                        if (ft2 > ft_max * ft_max) {
-                            tf = fscale(ft_max * frsq(ft2), tf);
-                            delta_tan = fscale(-frcp(kt), faxpy(gt, vrel_tan, tf));
-                        }
-                    } else {
-                        tf = mk3(0, 0, 0);
-                    }
-                    force = fadd(force, tf);
-                }
-                hist.x = delta_tan.x, hist.y = delta_tan.y, hist.z = delta_tan.z;
-            }
-        } else if (MODEL == 0) {
-            hist = make_float4(0, 0, 0, 0);
-        }
+        if constexpr (MODEL != 2)  // (a run-time compiled model has returned above)
+            hertz_fast<MODEL>(T.mat[matA * p.nMat + matB], p.h, A.mass, massB, rA, rB, depth, n, rAv, rBv, mk3(A.vx, A.vy, A.vz),
+                              mk3(B.vx, B.vy, B.vz), mk3(A.wx, A.wy, A.wz), mk3(B.wx, B.wy, B.wz), hist, force, torque_only);
         const f3 tot = fadd(force, torque_only);
         tA = fcross(rAv, tot);
         tB = fcross(tot, rBv);  // = r_B x (-F)

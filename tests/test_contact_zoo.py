@@ -75,9 +75,10 @@ both models, the three numberings); no class needed a factor above 4:
   depth_1e-1       2.0e-06   0            3.3e-08   6.7e-08   9.0e-10      3.7e-08
   per owner: a 5.2e-06, alpha 2.5e-06; equal and opposite: 0.35 (forces) and 0.05 (torques) of their bounds;
   fused step against the unfused one: velocities within the fp32 rounding of v + a h, 0.003 of the bound on the angular velocities.
-MUTATIONS of tile_contact, each built and run once on an MI355X (not kept): the 9-material fast-mode cases of this file fail under
-every one of them -- T.mat[matA * nMat + matA] (all six cases), the `hist.w <= t_collision` test dropped (the three hertz cases:
-roll_young gets a torque-only force), tB negated (all six), B's component read through A's index (all six).  tests/test_fast_mode.py
+MUTATIONS, each built and run once on an MI355X (not kept), of the tile kernels' tile_contact and of the law it calls, hertz_fast of
+deme_force_fast.h (then still a copy inside tile_contact): the 9-material fast-mode cases of this file fail under every one of them
+-- tile_contact's T.mat[matA * nMat + matA] (all six cases), hertz_fast's `hist.w <= t_collision` test dropped (the three hertz
+cases: roll_young gets a torque-only force), tile_contact's tB negated (all six), B's component read through A's index (all six).  tests/test_fast_mode.py
 and tests/test_fast_mode_features.py without this file: the first mutation passes all 17 tests (their beds have one material), the
 second fails one (the recording test, whose bed has Crr = 0.05), the last two fail 13 and 14.
 """
