@@ -970,6 +970,13 @@ class Context:
         self._ck(self.lib.deme_tile_stats(self.h, out), "deme_tile_stats")
         return tuple(int(v) for v in out)
 
+    def heavy_owners(self):
+        """(heavy owners, heavy owners that are not fixed) of the current list: deme_heavy_owners"""
+        out = (C.c_uint32 * 2)()
+        self.lib.deme_heavy_owners.argtypes = [_P, C.POINTER(C.c_uint32)]
+        self._ck(self.lib.deme_heavy_owners(self.h, out), "deme_heavy_owners")
+        return int(out[0]), int(out[1])
+
     def set_tile_policy(self, min_contacts_per_tile_custom):
         self.lib.deme_set_tile_policy.argtypes = [_P, C.c_uint32]
         self._ck(self.lib.deme_set_tile_policy(self.h, int(min_contacts_per_tile_custom)), "deme_set_tile_policy")

@@ -1736,6 +1736,14 @@ int deme_tile_stats(const deme_ctx* c, uint32_t out[4]) {
     out[2] = L.tileMaxHalo, out[3] = L.tileMaxList;
     return DEME_OK;
 }
+int deme_heavy_owners(deme_ctx* c, uint32_t out[2]) {
+    if (!c || !out)
+        return DEME_ERR_INVALID;
+    ContactList& L = c->list[c->cur];
+    resolve_heavy_counts(c, L);
+    out[0] = L.nHeavy, out[1] = L.nHeavyFree;
+    return DEME_OK;
+}
 int deme_set_tile_policy(deme_ctx* c, uint32_t minContactsPerTileCustom) {
     if (!c)
         return DEME_ERR_INVALID;

@@ -199,6 +199,10 @@ int deme_get_arith_mode(const deme_ctx* ctx);
  * deme_tile_stats: {tiles, tiles that do not fit the LDS area and are evaluated by k_tile_forces_big -- one workgroup each, the
  * rest of the list stays tiled --, largest halo, largest local list} of the current list (zeros when it is not tiled). */
 int deme_tile_stats(const deme_ctx* ctx, uint32_t out[4]);
+/* (heavy owners, heavy owners that are not fixed) of the current list: the owners whose sums k_reduce_heavy takes -- more than 256
+ * A-side plus B-side entries, or replicated across slabs.  The list's general form (k_owner_ranges) and its tile form
+ * (k_owner_ranges_tile) count the entries from different structures and must flag the same owners. */
+int deme_heavy_owners(deme_ctx* ctx, uint32_t out[2]);
 /* A run-time compiled force model is compiled into the tile pass as well ("deme_custom_tile<MESH>": csrc/deme_jit.h splices the
  * user's statements where the Hertzian block of k_tile_forces is, the reference's vocabulary filled from the staged records,
  * DEMCalcForceKernels.cu:233-251).  A list takes it when its tiles hold at least minContactsPerTile contacts on average (default
