@@ -82,7 +82,7 @@ struct ContactList {
     bool fusedList = false;    // the list has the incoming structures of the one-kernel step (decided per detection)
     bool fusedChecked = false;  // ... and the device has been asked whether every closed tile fits
     // the heavy-owner counts of a tiled list are fetched without stopping the stream: the copy lands in pinned memory
-    // (deme_ctx::hrPinned), the first reader (launch_reduce_heavy, one force launch later) waits for its event
+    // (the PIN_HEAVY slot of deme_ctx::pin), the first reader (launch_reduce_heavy, one force launch later) waits for its event
     bool hrPending = false, heavyOverflow = false;
     uint32_t nHeavy = 0, nHeavyFree = 0, nSA = 0, nSM = 0;
     uint32_t nBigTiles = 0, tileMaxHalo = 0, tileMaxList = 0, tileMaxHaloIn = 0;
@@ -146,15 +146,14 @@ struct deme_ctx {
     // The contact list the steps read (list[cur]) and the one an asynchronous detection builds beside them (list[cur ^ 1]).
     // Shared by both, on purpose: the key and history double buffers with their selectors (keysSorted, wc, keysCur, wcCur ...),
     // the per-contact products of the force pass (conA*, conB*, aSum, rec32, rec[]), the pinned target of the heavy-owner
-    // read-back (hrPinned, hrEvent) and the closed-tile structures of the one-kernel step (recContact, inCnt ... below).
+    // read-back (the PIN_HEAVY slot, hrEvent) and the closed-tile structures of the one-kernel step (recContact, inCnt ... below).
     ContactList list[2];
     int cur = 0;
     // per-contact contributions of the force pass
     DevBuf conA4, conA2, conB4, conB2, aSum, rec32;
-    // One pinned block and one event serve the pending read-back (ContactList::hrPending) of both lists: a list's read-back is
+    // One pinned slot and one event serve the pending read-back (ContactList::hrPending) of both lists: a list's read-back is
     // resolved by the first force launch on it, or superseded when the list is built again, before the other list's is issued
     // -- an asynchronous cycle enqueues D >= 1 steps on the current list before part 2 builds the other.
-    RangeCounters* hrPinned = nullptr;
     hipEvent_t hrEvent = nullptr;
     bool ctrFresh = false;  // DetectCounters were zeroed by the margins kernel's launch and nothing has counted in them since
     bool conTile = false;     // the contributions in memory were written by the tile kernel
@@ -324,9 +323,26 @@ int records_refused(deme_ctx* c) {
 // The sizing read-backs of a detection: the host has nothing else to do, the GPU idles until it is back with the next launches,
 // and a blocking wait wakes up tens of microseconds late -- so the host polls the stream (for at most a few milliseconds; a
 // part 1 beside the steps, whose wait is long by design, blocks instead of burning a core).
+// They land in the context's pinned block (a copy into pageable memory goes through the runtime's staging buffer and costs tens
+// of microseconds of host time before the wait even starts), each in a slot of its own where two can be in flight at the same
+// time: part 1 on the detection stream beside ensure_legacy_lists on the main stream, and the heavy-owner counts of a tiled
+// list (ContactList::hrPending), which nobody waits for until the next force launch.
+constexpr size_t PIN_BYTES = 16384;
+constexpr size_t PIN_HEAVY = 0;      // RangeCounters: the pending heavy-owner counts
+constexpr size_t PIN_RANGES = 128;   // RangeCounters: part 2's tile counters
+constexpr size_t PIN_LEGACY = 256;   // RangeCounters: read_legacy_counts
+constexpr size_t PIN_TRI = 384;      // uint32_t: the triangle incidences
+constexpr size_t PIN_UNIQUE = 448;   // unsigned long long: the keys left once the marked contacts' duplicates are gone
+constexpr size_t PIN_DETECT = 1024;  // DetectHead: part 1's counters (the incidence total is read through the same slot)
+static_assert(PIN_HEAVY + sizeof(RangeCounters) <= PIN_RANGES && PIN_RANGES + sizeof(RangeCounters) <= PIN_LEGACY &&
+                  PIN_LEGACY + sizeof(RangeCounters) <= PIN_TRI && PIN_TRI + sizeof(uint32_t) <= PIN_UNIQUE &&
+                  PIN_UNIQUE + sizeof(unsigned long long) <= PIN_DETECT && PIN_DETECT + sizeof(DetectHead) <= PIN_BYTES,
+              "the read-back slots overlap or leave the pinned block");
+static_assert(PIN_RANGES % 8 == 0 && PIN_LEGACY % 8 == 0 && PIN_TRI % 8 == 0 && PIN_UNIQUE % 8 == 0 && PIN_DETECT % 8 == 0,
+              "a read-back slot is aligned for the counters it holds");
 template <typename T>
-static inline T* pin_at(deme_ctx* c, size_t off) {
-    return reinterpret_cast<T*>(c->pin + off);
+static inline T* pin_at(deme_ctx* c, size_t slot) {
+    return reinterpret_cast<T*>(c->pin + slot);
 }
 static hipError_t sync_readback(deme_ctx* c, hipStream_t st, bool spin) {
     if (c->spinSync && spin) {
@@ -340,6 +356,19 @@ static hipError_t sync_readback(deme_ctx* c, hipStream_t st, bool spin) {
         }
     }
     return hipStreamSynchronize(st);
+}
+// One read-back: `bytes` of device counters from `dev` into `slot`, ordered on `st`, and the wait for them.  nullptr: the copy or
+// the wait failed (the error is in c->err, its code in c->lastStatus).
+template <typename T>
+const T* read_back(deme_ctx* c, size_t slot, const void* dev, hipStream_t st, bool spin, size_t bytes = sizeof(T)) {
+    T* host = pin_at<T>(c, slot);
+    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+        e = sync_readback(c, st, spin);
+    if (e == hipSuccess)
+        return host;
+    fail(c, DEME_ERR_HIP, "a detection's read-back failed: %s", hipGetErrorString(e));
+    return nullptr;
 }
 
 int ensure(deme_ctx* c, DevBuf& b, size_t bytes, bool keep = false) {
@@ -631,12 +660,263 @@ int status_to_error(deme_ctx* c, uint32_t st) {
     return DEME_OK;
 }
 
-int do_margins(deme_ctx* c, uint32_t drift) {
-    HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->stream));
-    c->ctrFresh = true;
+// The margins of the owner records `ow` for `drift` steps, on `st`.  The fill in front zeroes the detection's counters (the whole
+// DetectBlock, the segment counters with it) and the kernel may leave status bits in them (velocity limit, non-finite state):
+// the detection that follows does not zero them again, and the status comes back with its first read-back.
+int launch_margins(deme_ctx* c, hipStream_t st, OwnerRec* ow, uint32_t drift) {
+    HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), st));
     if (c->nOwners)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
-    hipLaunchKernelGGL(k_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->dp, c->owners.as<OwnerRec>(),
-                       drift, c->ctr.as<DetectCounters>());
+        hipLaunchKernelGGL(k_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, st, c->dp, ow, drift, c->ctr.as<DetectCounters>());
+    c->ctrFresh = true;
+    return DEME_OK;
+}
+int do_margins(deme_ctx* c, uint32_t drift) {
+    return launch_margins(c, c->stream, c->owners.as<OwnerRec>(), drift);
+}
+
+int do_migrate(deme_ctx* c);
+
+// What the stages of part 1 share: the caller's choices, the raw key arena of this attempt, the sizes read so far.
+struct DetectRun {
+    hipStream_t st;
+    OwnerRec* ow;
+    bool async;               // beside the steps, on the detection stream: the waits block instead of polling
+    bool statusSeen = false;  // the status word the margins kernel left has been examined
+    KeyArena ar{};
+    bool segmented = false;
+    uint32_t P = 0;              // (bin, sphere) incidences
+    uint32_t nStats = 0, compactBlocks = 0;  // k_sweep's window records still to be added up; slot-blocks the early k_compact_keys covered
+    uint64_t raw = 0, segMax = 0;            // keys the emitting kernels counted: in all, in the longest segment
+    DetectCounters hc{};
+};
+inline unsigned bin_id_bits(const deme_ctx* c) { return bits_for((uint64_t)c->hp.nbX * c->hp.nbY * c->hp.nbZ, 32); }
+
+// The raw key arena: 64 segments with a counter each once it is large enough for every segment to hold a fair share of any list
+// (see KeyArena); one segment, counted in DetectCounters::nContactsRaw, below that.
+void open_key_arena(deme_ctx* c, DetectRun& d) {
+    DetectBlock* blk = c->ctr.as<DetectBlock>();
+    d.segmented = c->keySegMin && c->cntCap >= c->keySegMin && c->cntCap >= DEME_KEY_SEGS * 64u;
+    d.ar.keys = c->keysRaw.as<uint64_t>();
+    d.ar.segMask = d.segmented ? DEME_KEY_SEGS - 1u : 0u;
+    d.ar.segCap = d.segmented ? (uint64_t)c->cntCap / DEME_KEY_SEGS : (uint64_t)c->cntCap;
+    d.ar.ctr = d.segmented ? blk->segCtr : &blk->c.nContactsRaw;
+}
+
+// Part 1's read-back: `bytes` of the counter block (sizeof(DetectHead): with the segments' counts), the counters also in d.hc.
+// The first one of a detection brings the status the margins kernel left.  nullptr: failed, the code is in c->lastStatus.
+const DetectHead* read_detect_counters(deme_ctx* c, DetectRun& d, size_t bytes) {
+    const DetectHead* hh = read_back<DetectHead>(c, PIN_DETECT, c->ctr.p, d.st, !d.async, bytes);
+    if (!hh || (!d.statusSeen && status_to_error(c, hh->c.status & ~DEME_ST_INCIDENCE)))
+        return nullptr;
+    d.statusSeen = true;
+    d.hc = hh->c;
+    return hh;
+}
+
+// Stage 1, the (bin, sphere) incidences: bounds and counts per sphere, their prefix, the pairs themselves.  Leaves d.P.
+int detect_sphere_incidences(deme_ctx* c, DetectRun& d) {
+    const uint32_t nS = c->nSpheres;
+    d.P = 0;
+    auto fill_incidence = [&]() {
+        hipLaunchKernelGGL(k_fill_incidence, dim3(grid_for(nS)), dim3(256), 0, d.st, c->dp, c->binLo.as<uint4>(), c->binN.as<uint2>(),
+                           c->binPartial.as<uint32_t>(), c->incKeys[0].as<uint32_t>(), c->incVals[0].as<uint32_t>(), (uint64_t)c->incCap);
+    };
+    if (nS) {
+        c->geoStale = false;
+        hipLaunchKernelGGL(k_sphere_prep, dim3(grid_for(nS)), dim3(256), 0, d.st, c->dp, d.ow, c->spheres.as<SphereRec>(),
+                           c->geo.as<GeoRec>(), c->binLo.as<uint4>(), c->binN.as<uint2>(), c->binPartial.as<uint32_t>(), d.ar,
+                           c->ctr.as<DetectCounters>(), c->sphFam.as<uint16_t>());
+        // (one workgroup: the prefix of one sum per workgroup above, and the total for the read-back below)
+        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, d.st, c->binPartial.as<uint32_t>(), c->binPartial.as<uint32_t>(),
+                           grid_for(nS), &c->ctr.as<DetectBlock>()->c.nIncidence);
+        // the incidences go out before the host knows how many there are (the kernel guards the arena's end): the GPU works
+        // through the read-back instead of idling
+        const bool early = c->incCap != 0;
+        if (early)
+            fill_incidence();
+        if (!read_detect_counters(c, d, sizeof(DetectCounters)))
+            return c->lastStatus;
+        if (d.hc.status & DEME_ST_INCIDENCE)
+            return fail(c, DEME_ERR_OVERFLOW,
+                        "a sphere touches more than %u bins (margin far larger than the bin size): the incidence list cannot be built",
+                        DEME_MAX_BINS_PER_SPHERE);
+        if (d.hc.nIncidence > 0xFFFFFFFFull)  // (the total is exact in 64 bits; the offsets the kernels work with have wrapped)
+            return fail(c, DEME_ERR_OVERFLOW, "%llu bin-sphere incidences do not fit the 32-bit list offsets (use larger bins)",
+                        d.hc.nIncidence);
+        d.P = (uint32_t)d.hc.nIncidence;
+        const bool grow = d.P > c->incCap;
+        if (grow)
+            if (int rc = grow_incidence_arena(c, (size_t)d.P + d.P / 4 + 1024))
+                return rc;
+        if (d.P && (grow || !early))  // (the early fill stopped at the old arena's end, or there was no arena to fill)
+            fill_incidence();
+    }
+    c->nInc = d.P;
+    return DEME_OK;
+}
+
+// Stage 2: the incidences sorted by bin, the sweep over each bin's spheres (it appends the sphere-sphere keys), and the windows'
+// statistics (bins in use, the fullest bin) on their way to the counters.
+int detect_sort_sweep(deme_ctx* c, DetectRun& d) {
+    d.nStats = 0;
+    if (!d.P)
+        return DEME_OK;
+    const uint32_t P = d.P;
+    const hipStream_t st = d.st;
+    const unsigned bits = bin_id_bits(c);
+    // bin ids of up to 22 bits: two passes of 11 bits (16 keys per thread) take as long as three of 8 and save a pass's launches
+    const bool twoPass = bits > 16 && bits <= 22;
+    auto sort = [&](auto cfg, void* tmp, size_t& bytes) {
+        return deme_radix_sort<decltype(cfg), true>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(), c->incVals[0].as<uint32_t>(),
+                                                    c->incVals[1].as<uint32_t>(), (size_t)P, (size_t)c->incCap, 0, bits, DEME_SORT_OWN_FROM_INCIDENCES, st);
+    };
+    if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+            return twoPass ? sort(DemeRadixCfg<11, 16>{}, tmp, bytes) : sort(DemeRadixCfg<8>{}, tmp, bytes);
+        }))
+        return rc;
+    const uint32_t nWin = (uint32_t)grid_for(P, SW_T);
+    if (int rc = ensure(c, c->binStat, (size_t)nWin * sizeof(uint2)))
+        return rc;
+    static_assert(SW_WPB == 1, "k_sweep writes one statistics record per window");
+    hipLaunchKernelGGL(k_sweep, dim3(nWin), dim3(SW_T), 0, st, c->dp, c->incKeys[1].as<uint32_t>(), c->incVals[1].as<uint32_t>(), P,
+                       c->geo.as<GeoRec>(), c->sphFam.as<uint16_t>(), d.ar, c->binStat.as<uint2>());
+    if (d.segmented)  // (the workgroups of k_compact_keys add the windows' statistics up)
+        d.nStats = nWin;
+    else
+        hipLaunchKernelGGL(k_bin_stats_final, dim3((nWin + 2047u) / 2048u), dim3(256), 0, st, c->binStat.as<uint2>(), nWin,
+                           c->ctr.as<DetectCounters>());
+    return DEME_OK;
+}
+
+// Stage 3, sphere-triangle contacts (only when a mesh is loaded and some sphere is registered in a bin): the (bin, triangle)
+// incidences, sorted by bin, swept against the spheres' (the sweep appends the sphere-mesh keys).
+int detect_triangles(deme_ctx* c, DetectRun& d) {
+    c->nTriInc = 0;
+    if (!c->nTri || !d.P)
+        return DEME_OK;
+    const uint32_t nT = c->nTri;
+    const hipStream_t st = d.st;
+    hipLaunchKernelGGL(k_tri_prep, dim3(grid_for(nT)), dim3(256), 0, st, c->dp, nT, c->tris.as<TriRec>(), d.ow,
+                       c->triWorld.as<TriWorld>(), c->triLo.as<int4>(), c->triHi.as<int4>(), c->triCounts.as<uint32_t>());
+    if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->triCounts.as<uint32_t>(), c->triOffsets.as<uint32_t>(), 0u, (size_t)nT + 1,
+                                           rocprim::plus<uint32_t>(), st);
+        }))
+        return rc;
+    const uint32_t* tp = read_back<uint32_t>(c, PIN_TRI, c->triOffsets.as<uint32_t>() + nT, st, false);
+    if (!tp)
+        return c->lastStatus;
+    const uint32_t TP = *tp;
+    if (TP > c->triCap) {
+        const size_t cap = (size_t)TP + TP / 4 + 1024;
+        for (int k = 0; k < 2; k++)
+            if (ensure(c, c->triKeys[k], cap * 4) || ensure(c, c->triVals[k], cap * 4))
+                return c->lastStatus;
+        c->triCap = cap;
+    }
+    c->nTriInc = TP;
+    if (!TP)
+        return DEME_OK;
+    hipLaunchKernelGGL(k_tri_fill, dim3(grid_for(nT)), dim3(256), 0, st, c->dp, nT, c->triWorld.as<TriWorld>(), c->triLo.as<int4>(),
+                       c->triHi.as<int4>(), c->triOffsets.as<uint32_t>(), c->triKeys[0].as<uint32_t>(), c->triVals[0].as<uint32_t>(),
+                       (uint64_t)c->triCap);
+    if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, c->triKeys[0].as<uint32_t>(), c->triKeys[1].as<uint32_t>(),
+                                             c->triVals[0].as<uint32_t>(), c->triVals[1].as<uint32_t>(), (size_t)TP, 0, bin_id_bits(c), st);
+        }))
+        return rc;
+    hipLaunchKernelGGL(k_tri_sweep, dim3(grid_for(TP)), dim3(256), 0, st, c->dp, TP, c->triKeys[1].as<uint32_t>(),
+                       c->triVals[1].as<uint32_t>(), c->triWorld.as<TriWorld>(), d.P, c->incKeys[1].as<uint32_t>(),
+                       c->incVals[1].as<uint32_t>(), c->geo.as<GeoRec>(), c->sphFam.as<uint16_t>(), d.ar);
+    return DEME_OK;
+}
+// Stage 4, closing the arena: how many keys the emitting kernels counted (d.raw; d.segMax in the longest segment).  The gaps
+// between the segments are closed while the host waits for the counts: a launch sized from the last detection's longest segment,
+// the rest (if a segment grew past that) once the counts are known (detect_order_keys).
+int detect_close_arena(deme_ctx* c, DetectRun& d) {
+    d.compactBlocks = 0;
+    if (d.segmented) {
+        d.compactBlocks = (uint32_t)std::min<uint64_t>(grid_for(std::max<uint64_t>(c->lastSegMax + c->lastSegMax / 8 + 1024, 1)), grid_for(d.ar.segCap));
+        hipLaunchKernelGGL(k_compact_keys, dim3(d.compactBlocks, DEME_KEY_SEGS), dim3(256), 0, d.st, c->keysRaw.as<uint64_t>(), d.ar.segCap,
+                           c->ctr.as<DetectBlock>(), 0u, c->keysSorted[c->keysCur ^ 1].as<uint64_t>(), c->binStat.as<uint2>(), d.nStats);
+    }
+    // one copy: the counters and, with the segmented arena, the 64 counts k_compact_keys has put beside them
+    const DetectHead* hh = read_detect_counters(c, d, d.segmented ? sizeof(DetectHead) : sizeof(DetectCounters));
+    if (!hh)
+        return c->lastStatus;
+    d.raw = d.hc.nContactsRaw, d.segMax = 0;
+    if (d.segmented) {
+        d.raw = 0;
+        for (uint32_t g = 0; g < DEME_KEY_SEGS; g++) {
+            d.raw += hh->segCount[g];
+            d.segMax = std::max<uint64_t>(d.segMax, hh->segCount[g]);
+        }
+    }
+    return DEME_OK;
+}
+
+// The one rule by which the contact arena grows: the capacity that `raw` keys with `segMax` of them in one segment, and `marks`
+// persistent keys appended behind them, ask of an arena of `cap` slots in segments of `segCap` -- or 0 when everything fits.
+size_t contact_arena_wanted(uint64_t raw, uint64_t segMax, uint64_t segCap, size_t marks, size_t cap) {
+    size_t grow = 0;
+    if (raw > cap || segMax > segCap) {  // the arena, or one segment of it, is too small for the emitting kernels
+        const size_t want = std::max<size_t>(raw, (size_t)segMax * DEME_KEY_SEGS);
+        grow = want + want / 4 + 1024;
+    }
+    if (marks && raw + marks > std::max(cap, grow))  // ... or for the marked contacts behind what they emitted
+        grow = (size_t)raw + marks + raw / 4 + 1024;
+    return grow;
+}
+
+// Stage 5, ordering the keys: the rest of the compaction, the marked contacts (they join the list whether or not the sweep found
+// them: DEMCubContactDetection.cu:605-802), and the list order in the next key buffer.  Returns the list's length in *nCout.
+int detect_order_keys(deme_ctx* c, DetectRun& d, uint64_t* nCout) {
+    const hipStream_t st = d.st;
+    const size_t nPersist = c->hPersist.size();
+    uint64_t nC = d.raw + nPersist;
+    const int next = c->keysCur ^ 1;
+    uint64_t* rawKeys = c->keysRaw.as<uint64_t>();
+    if (d.segmented) {  // (the next list's buffer is free until the rank sort fills it)
+        c->lastSegMax = d.segMax;
+        if (grid_for(d.segMax) > d.compactBlocks)
+            hipLaunchKernelGGL(k_compact_keys, dim3((unsigned)grid_for(d.segMax) - d.compactBlocks, DEME_KEY_SEGS), dim3(256), 0, st,
+                               c->keysRaw.as<uint64_t>(), d.ar.segCap, c->ctr.as<DetectBlock>(), d.compactBlocks,
+                               c->keysSorted[next].as<uint64_t>(), (const uint2*)nullptr, 0u);
+        if (d.raw)
+            rawKeys = c->keysSorted[next].as<uint64_t>();
+    }
+    if (nPersist)
+        HIPCK(hipMemcpyAsync(rawKeys + d.raw, c->persistKeys.p, nPersist * 8, hipMemcpyDeviceToDevice, st));
+    if (nC) {
+        // key = A << 33 | class << 31 | B.  One radix sort over the occupied upper bits [31, 33 + bits(A)) groups the keys by
+        // (sphere A, class) -- 3 passes at 3e6 spheres, where a full 64-bit order took 6 to 8 -- and k_segment_rank_sort puts each
+        // group's few partners in order (DEMCubContactDetection.cu:811-1110 runs five full sorts for the same list order)
+        const unsigned bitsA = bits_for(c->dp.nSpheres, 31);
+        if (int rc = ensure(c, c->keysMid, (size_t)c->cntCap * 8))  // (its own scratch: an asynchronous detection runs beside force passes)
+            return rc;
+        uint64_t* mid = c->keysMid.as<uint64_t>();
+        if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                return deme_radix_sort<DemeRadixCfg<8>, false>(tmp, bytes, rawKeys, mid, nullptr, nullptr, (size_t)nC, (size_t)c->cntCap, 31,
+                                                               33 + bitsA, DEME_SORT_OWN_FROM_KEYS64, st);
+            }))
+            return rc;
+        hipLaunchKernelGGL(k_segment_rank_sort, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, mid,
+                           c->keysSorted[next].as<uint64_t>());
+        if (nPersist) {  // a marked contact the sweep found as well appears once (markDuplicateContacts)
+            unsigned long long* cnt = &c->ctr.as<DetectBlock>()->c.nContactsRaw;
+            if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+                    return rocprim::unique(tmp, bytes, c->keysSorted[next].as<uint64_t>(), c->keysRaw.as<uint64_t>(), cnt, (size_t)nC,
+                                           rocprim::equal_to<uint64_t>(), st);
+                }))
+                return rc;
+            const unsigned long long* nU = read_back<unsigned long long>(c, PIN_UNIQUE, cnt, st, false);
+            if (!nU)
+                return c->lastStatus;
+            nC = *nU;
+            HIPCK(hipMemcpyAsync(c->keysSorted[next].p, c->keysRaw.p, (size_t)nC * 8, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    *nCout = nC;
     return DEME_OK;
 }
 
@@ -645,238 +925,37 @@ int do_margins(deme_ctx* c, uint32_t drift) {
 // while the main stream keeps stepping with the current list (deme_set_async_detection; the reference's kT does the same on its
 // own GPU thread).  Part 2 -- history map and the per-owner gather lists the force and integration kernels read -- runs on the
 // main stream when the list is swapped in.
-int do_migrate(deme_ctx* c);
+// Part 1 is an attempt repeated with a larger contact arena until every key has a slot: the stages above, and one decision.
 int detect_part1(deme_ctx* c, hipStream_t st, OwnerRec* ow, bool async, uint64_t* nCout) {
-    const uint32_t nS = c->nSpheres;
-    DetectCounters hc{};
-    // The margins kernel's launch zeroes the counters (the whole DetectBlock, the segment counters with it: one fill) and may leave
-    // status bits (velocity limit, non-finite state): when it has just run the block is not zeroed again and its status comes back
-    // with the first sizing read-back below (no read-back of its own).
-    const bool countersFresh = c->ctrFresh;
+    DetectRun d{st, ow, async};
+    const bool countersFresh = c->ctrFresh;  // (launch_margins has just zeroed them and left its status there)
     c->ctrFresh = false;
-    bool statusSeen = false;
-
-    DetectBlock* blk = c->ctr.as<DetectBlock>();
     for (int attempt = 0; attempt < 4; attempt++) {
         if (attempt > 0 || !countersFresh)
             HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), st));
-        // the raw key arena: 64 segments with a counter each once it is large enough for every segment to hold a fair share of any
-        // list (see KeyArena); one segment, counted in DetectCounters::nContactsRaw, below that
-        const bool segmented = c->keySegMin && c->cntCap >= c->keySegMin && c->cntCap >= DEME_KEY_SEGS * 64u;
-        KeyArena ar;
-        ar.keys = c->keysRaw.as<uint64_t>();
-        ar.segMask = segmented ? DEME_KEY_SEGS - 1u : 0u;
-        ar.segCap = segmented ? (uint64_t)c->cntCap / DEME_KEY_SEGS : (uint64_t)c->cntCap;
-        ar.ctr = segmented ? blk->segCtr : &blk->c.nContactsRaw;
-        if (nS) {
-            c->geoStale = false;
-            hipLaunchKernelGGL(k_sphere_prep, dim3(grid_for(nS)), dim3(256), 0, st, c->dp,
-                               ow, c->spheres.as<SphereRec>(), c->geo.as<GeoRec>(),
-                               c->binLo.as<uint4>(), c->binN.as<uint2>(), c->binPartial.as<uint32_t>(),
-                               ar, c->ctr.as<DetectCounters>(), c->sphFam.as<uint16_t>());
-            // (one workgroup: the prefix of one sum per workgroup above, and the total for the read-back below)
-            hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, st, c->binPartial.as<uint32_t>(), c->binPartial.as<uint32_t>(),
-                               grid_for(nS), &blk->c.nIncidence);
-        }
-        uint32_t P = 0;
-        bool filled = false;
-        auto fill_incidence = [&]() {
-            hipLaunchKernelGGL(k_fill_incidence, dim3(grid_for(nS)), dim3(256), 0, st, c->dp,
-                               c->binLo.as<uint4>(), c->binN.as<uint2>(), c->binPartial.as<uint32_t>(),
-                               c->incKeys[0].as<uint32_t>(), c->incVals[0].as<uint32_t>(), (uint64_t)c->incCap);
-            filled = true;
-        };
-        if (nS && c->incCap)  // the incidences go out before the host knows how many there are (the kernel guards the arena's end):
-            fill_incidence();  // the GPU works through the read-back below instead of idling; repeated if the arena has to grow
-        if (nS) {
-            // (read-backs land in pinned memory: a copy into pageable memory goes through the runtime's staging buffer and costs
-            // tens of microseconds of host time before the wait even starts)
-            HIPCK(hipMemcpyAsync(pin_at<DetectCounters>(c, 1024), c->ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
-            HIPCK(sync_readback(c, st, !async));
-            hc = *pin_at<DetectCounters>(c, 1024);
-            if (!statusSeen) {
-                statusSeen = true;
-                if (int rc = status_to_error(c, hc.status & ~DEME_ST_INCIDENCE))
-                    return rc;
-            }
-            if (hc.status & DEME_ST_INCIDENCE)
-                return fail(c, DEME_ERR_OVERFLOW,
-                            "a sphere touches more than %u bins (margin far larger than the bin size): the incidence list cannot be built",
-                            DEME_MAX_BINS_PER_SPHERE);
-            if (hc.nIncidence > 0xFFFFFFFFull)  // (the total is exact in 64 bits; the offsets the kernels work with have wrapped)
-                return fail(c, DEME_ERR_OVERFLOW, "%llu bin-sphere incidences do not fit the 32-bit list offsets (use larger bins)",
-                            hc.nIncidence);
-            P = (uint32_t)hc.nIncidence;
-        }
-        if (P > c->incCap) {
-            if (int rc = grow_incidence_arena(c, (size_t)P + P / 4 + 1024))
-                return rc;
-            filled = false;
-        }
-        c->nInc = P;
-        uint32_t nStats = 0;  // records of k_sweep's windows that are still to be added up
-        const unsigned bits = bits_for((uint64_t)c->hp.nbX * c->hp.nbY * c->hp.nbZ, 32);  // of a bin id
-        if (P) {
-            if (!filled)
-                fill_incidence();
-            // bin ids of up to 22 bits: two passes of 11 bits (16 keys per thread) take as long as three of 8 and save a pass's launches
-            const bool twoPass = bits > 16 && bits <= 22;
-            if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                    return twoPass ? deme_radix_sort<DemeRadixCfg<11, 16>, true>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
-                                                                                 c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P,
-                                                                                 (size_t)c->incCap, 0, bits, DEME_SORT_OWN_FROM_INCIDENCES, st)
-                                   : deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->incKeys[0].as<uint32_t>(), c->incKeys[1].as<uint32_t>(),
-                                                                            c->incVals[0].as<uint32_t>(), c->incVals[1].as<uint32_t>(), (size_t)P,
-                                                                            (size_t)c->incCap, 0, bits, DEME_SORT_OWN_FROM_INCIDENCES, st);
-                }))
-                return rc;
-            const uint32_t nWin = (uint32_t)grid_for(P, SW_T);
-            if (int rc = ensure(c, c->binStat, (size_t)nWin * sizeof(uint2)))
-                return rc;
-            static_assert(SW_WPB == 1, "k_sweep writes one statistics record per window");
-            hipLaunchKernelGGL(k_sweep, dim3(nWin), dim3(SW_T), 0, st, c->dp,
-                               c->incKeys[1].as<uint32_t>(), c->incVals[1].as<uint32_t>(), P, c->geo.as<GeoRec>(),
-                               c->sphFam.as<uint16_t>(), ar, c->binStat.as<uint2>());
-            if (segmented)  // (the workgroups of k_compact_keys add the windows' statistics up)
-                nStats = nWin;
-            else
-                hipLaunchKernelGGL(k_bin_stats_final, dim3((nWin + 2047u) / 2048u), dim3(256), 0, st, c->binStat.as<uint2>(), nWin,
-                                   c->ctr.as<DetectCounters>());
-        }
-        // ---- sphere-triangle contacts (only when a mesh is loaded and some sphere is registered in a bin)
-        c->nTriInc = 0;
-        if (c->nTri && P) {
-            const uint32_t nT = c->nTri;
-            hipLaunchKernelGGL(k_tri_prep, dim3(grid_for(nT)), dim3(256), 0, st, c->dp, nT, c->tris.as<TriRec>(),
-                               ow, c->triWorld.as<TriWorld>(), c->triLo.as<int4>(),
-                               c->triHi.as<int4>(), c->triCounts.as<uint32_t>());
-            size_t tmp = c->scanTmp.bytes;
-            HIPCK(rocprim::exclusive_scan(c->scanTmp.p, tmp, c->triCounts.as<uint32_t>(), c->triOffsets.as<uint32_t>(), 0u,
-                                          (size_t)nT + 1, rocprim::plus<uint32_t>(), st));
-            uint32_t TP = 0;
-            HIPCK(hipMemcpyAsync(&TP, c->triOffsets.as<uint32_t>() + nT, 4, hipMemcpyDeviceToHost, st));
-            HIPCK(hipStreamSynchronize(st));
-            if (TP > c->triCap) {
-                const size_t cap = (size_t)TP + TP / 4 + 1024;
-                for (int k = 0; k < 2; k++)
-                    if (ensure(c, c->triKeys[k], cap * 4) || ensure(c, c->triVals[k], cap * 4))
-                        return c->lastStatus;
-                c->triCap = cap;
-            }
-            c->nTriInc = TP;
-            if (TP) {
-                hipLaunchKernelGGL(k_tri_fill, dim3(grid_for(nT)), dim3(256), 0, st, c->dp, nT,
-                                   c->triWorld.as<TriWorld>(), c->triLo.as<int4>(), c->triHi.as<int4>(),
-                                   c->triOffsets.as<uint32_t>(), c->triKeys[0].as<uint32_t>(), c->triVals[0].as<uint32_t>(),
-                                   (uint64_t)c->triCap);
-                if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                        return rocprim::radix_sort_pairs(tmp, bytes, c->triKeys[0].as<uint32_t>(), c->triKeys[1].as<uint32_t>(),
-                                                         c->triVals[0].as<uint32_t>(), c->triVals[1].as<uint32_t>(), (size_t)TP, 0, bits, st);
-                    }))
-                    return rc;
-                hipLaunchKernelGGL(k_tri_sweep, dim3(grid_for(TP)), dim3(256), 0, st, c->dp, TP,
-                                   c->triKeys[1].as<uint32_t>(), c->triVals[1].as<uint32_t>(), c->triWorld.as<TriWorld>(), P,
-                                   c->incKeys[1].as<uint32_t>(), c->incVals[1].as<uint32_t>(), c->geo.as<GeoRec>(),
-                                   c->sphFam.as<uint16_t>(), ar);
-            }
-        }
-        // the gaps between the arena's segments are closed while the host waits for the counts: a launch sized from the last
-        // detection's longest segment, the rest (if a segment grew past that) after the read-back
-        const int nextEarly = c->keysCur ^ 1;
-        uint32_t compactBlocks = 0;
-        if (segmented) {
-            compactBlocks = (uint32_t)std::min<uint64_t>(grid_for(std::max<uint64_t>(c->lastSegMax + c->lastSegMax / 8 + 1024, 1)), grid_for(ar.segCap));
-            hipLaunchKernelGGL(k_compact_keys, dim3(compactBlocks, DEME_KEY_SEGS), dim3(256), 0, st, c->keysRaw.as<uint64_t>(), ar.segCap,
-                               blk, 0u, c->keysSorted[nextEarly].as<uint64_t>(), c->binStat.as<uint2>(), nStats);
-        }
-        // one copy: the counters and, with the segmented arena, the 64 counts k_compact_keys has put beside them
-        const DetectHead* hh = pin_at<DetectHead>(c, 1024);
-        HIPCK(hipMemcpyAsync(pin_at<DetectHead>(c, 1024), c->ctr.p, segmented ? sizeof(DetectHead) : sizeof(DetectCounters), hipMemcpyDeviceToHost, st));
-        HIPCK(sync_readback(c, st, !async));
-        hc = hh->c;
-        if (!statusSeen) {
-            statusSeen = true;
-            if (int rc = status_to_error(c, hc.status & ~DEME_ST_INCIDENCE))
-                return rc;
-        }
-        unsigned long long segMax = 0;
-        if (segmented) {
-            hc.nContactsRaw = 0;
-            for (uint32_t g = 0; g < DEME_KEY_SEGS; g++) {
-                hc.nContactsRaw += hh->segCount[g];
-                segMax = std::max(segMax, hh->segCount[g]);
-            }
-        }
-        if (hc.nContactsRaw > c->cntCap || segMax > ar.segCap) {  // arena (or one segment of it) too small: grow and redo the emitting kernels
-            if (async)
+        open_key_arena(c, d);
+        if (int rc = detect_sphere_incidences(c, d))
+            return rc;
+        if (int rc = detect_sort_sweep(c, d))
+            return rc;
+        if (int rc = detect_triangles(c, d))
+            return rc;
+        if (int rc = detect_close_arena(c, d))
+            return rc;
+        if (const size_t cap = contact_arena_wanted(d.raw, d.segMax, d.ar.segCap, c->hPersist.size(), c->cntCap)) {
+            if (async)  // (the steps in flight read buffers of the arena)
                 HIPCK(hipStreamSynchronize(c->stream));
-            const size_t want = std::max<size_t>(hc.nContactsRaw, (size_t)segMax * DEME_KEY_SEGS);
-            if (int rc = grow_contact_arena(c, want + want / 4 + 1024))
+            if (int rc = grow_contact_arena(c, cap))
                 return rc;
-            continue;
+            continue;  // the emitting kernels run again
         }
-        c->nActiveBins = hc.nActiveBins;
-        c->maxInBin = hc.maxInBin ? hc.maxInBin : (P ? 1u : 0u);
+        c->nActiveBins = d.hc.nActiveBins;
+        c->maxInBin = d.hc.maxInBin ? d.hc.maxInBin : (d.P ? 1u : 0u);
         if (c->maxInBin > c->dp.errOutBinSphNum)
             return fail(c, DEME_ERR_BIN_TOO_FULL,
                         "a bin contains %u sphere components, exceeding the allowance %u (SetMaxSphereInBin)", c->maxInBin,
                         c->dp.errOutBinSphNum);
-        uint64_t nC = hc.nContactsRaw;
-        const size_t nPersist = c->hPersist.size();
-        if (nPersist) {  // marked contacts join the list whether or not the sweep found them (DEMCubContactDetection.cu:605-802)
-            if (nC + nPersist > c->cntCap) {
-                if (async)
-                HIPCK(hipStreamSynchronize(c->stream));
-            if (int rc = grow_contact_arena(c, (size_t)nC + nPersist + nC / 4 + 1024))
-                    return rc;
-                continue;
-            }
-            nC += nPersist;
-        }
-        const int next = c->keysCur ^ 1;
-        uint64_t* rawKeys = c->keysRaw.as<uint64_t>();
-        if (segmented) {  // (the gaps were closed above; the next list's buffer is free until the rank sort fills it)
-            c->lastSegMax = segMax;
-            if (grid_for(segMax) > compactBlocks)
-                hipLaunchKernelGGL(k_compact_keys, dim3((unsigned)grid_for(segMax) - compactBlocks, DEME_KEY_SEGS), dim3(256), 0, st,
-                                   c->keysRaw.as<uint64_t>(), ar.segCap, blk, compactBlocks, c->keysSorted[next].as<uint64_t>(),
-                                   (const uint2*)nullptr, 0u);
-            if (hc.nContactsRaw)
-                rawKeys = c->keysSorted[next].as<uint64_t>();
-        }
-        if (nPersist)
-            HIPCK(hipMemcpyAsync(rawKeys + hc.nContactsRaw, c->persistKeys.p, nPersist * 8, hipMemcpyDeviceToDevice, st));
-        if (nC) {
-            // key = A << 33 | class << 31 | B.  One radix sort over the occupied upper bits [31, 33 + bits(A)) groups the keys by
-            // (sphere A, class) -- 3 passes at 3e6 spheres, where a full 64-bit order took 6 to 8 -- and k_segment_rank_sort puts each
-            // group's few partners in order (DEMCubContactDetection.cu:811-1110 runs five full sorts for the same list order)
-            const unsigned bitsA = bits_for(c->dp.nSpheres, 31);
-            if (int rc = ensure(c, c->keysMid, (size_t)c->cntCap * 8))  // (its own scratch: an asynchronous detection runs beside force passes)
-                return rc;
-            uint64_t* mid = c->keysMid.as<uint64_t>();
-            if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                    return deme_radix_sort<DemeRadixCfg<8>, false>(tmp, bytes, rawKeys, mid, nullptr, nullptr, (size_t)nC, (size_t)c->cntCap, 31,
-                                                                   33 + bitsA, DEME_SORT_OWN_FROM_KEYS64, st);
-                }))
-                return rc;
-            hipLaunchKernelGGL(k_segment_rank_sort, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, mid,
-                               c->keysSorted[next].as<uint64_t>());
-            if (nPersist) {  // a marked contact the sweep found as well appears once (markDuplicateContacts)
-                unsigned long long* cnt = &blk->c.nContactsRaw;
-                if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
-                        return rocprim::unique(tmp, bytes, c->keysSorted[next].as<uint64_t>(), c->keysRaw.as<uint64_t>(), cnt, (size_t)nC,
-                                               rocprim::equal_to<uint64_t>(), st);
-                    }))
-                    return rc;
-                unsigned long long nU = 0;
-                HIPCK(hipMemcpyAsync(&nU, cnt, 8, hipMemcpyDeviceToHost, st));
-                HIPCK(hipStreamSynchronize(st));
-                nC = nU;
-                HIPCK(hipMemcpyAsync(c->keysSorted[next].p, c->keysRaw.p, (size_t)nC * 8, hipMemcpyDeviceToDevice, st));
-            }
-        }
-        *nCout = nC;
-        return DEME_OK;
+        return detect_order_keys(c, d, nCout);
     }
     return fail(c, DEME_ERR_OVERFLOW, "contact arena kept overflowing");
 }
@@ -915,8 +994,10 @@ int build_legacy_lists(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStrea
 }
 // ... and its heavy-owner counts on the host (a wait for `st`)
 int read_legacy_counts(deme_ctx* c, ContactList& L, hipStream_t st, RangeCounters& hr) {
-    HIPCK(hipMemcpyAsync(&hr, L.rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
+    const RangeCounters* got = read_back<RangeCounters>(c, PIN_LEGACY, L.rangeCtr.p, st, false);
+    if (!got)
+        return c->lastStatus;
+    hr = *got;
     if (hr.nHeavy > L.heavyList.bytes / 4)
         return fail(c, DEME_ERR_OVERFLOW, "%u owners exceed the heavy-owner list", hr.nHeavy);
     L.nHeavy = hr.nHeavy, L.nHeavyFree = hr.nHeavyFree;
@@ -939,8 +1020,9 @@ int ensure_legacy_lists(deme_ctx* c) {
 
 // May a list of nC contacts get tile structures (deme_tile.h)?  The fast mode; a user model only with its tile kernels compiled and
 // enough contacts per tile to pay for them; no replicated free owners; tables that the tile kernels can stage.
+inline uint32_t tile_count(const deme_ctx* c) { return (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB; }
 bool tile_eligible(const deme_ctx* c, uint64_t nC) {
-    const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
+    const uint32_t nTiles = tile_count(c);
     if (!nC || c->arith != DEME_ARITH_FAST || !c->hShared.empty())
         return false;
     if (c->hp.forceModel == DEME_FORCE_CUSTOM && !(c->customTileFn[0] && nC >= (uint64_t)c->tileMinContactsCustom * nTiles))
@@ -952,15 +1034,24 @@ bool tile_eligible(const deme_ctx* c, uint64_t nC) {
     return pieces <= DEME_TILE_T && c->nMassProps <= DEME_TILE_T && c->nAnal <= 65535 && c->nComp <= 65535 &&
            tile_table_bytes(c->nComp, c->nMat, c->nAnal, c->nMassProps, c->dp.familyTrivial) <= DEME_TILE_TABLE_MAX;
 }
+// May a tiled list whose counters read `hr` get the closed-tile structures of the one-kernel step (deme_tile_step.h)?  Switched on
+// (DEME_FUSED = 1 / 0 overrides the context's switch for the whole process), every tile fits, the built-in models, and nothing
+// the one kernel does not do: records, a mesh, ghosts, prescriptions, family rules, replicated owners, the adaptive controllers.
+// Never with asynchronous detection on: the closed-tile structures exist once -- see deme_ctx.
+bool fused_eligible(const deme_ctx* c, const RangeCounters& hr) {
+    static const int fusedEnv = getenv("DEME_FUSED") ? atoi(getenv("DEME_FUSED")) : -1;
+    const int fusedMode = fusedEnv < 0 ? c->fusedEnable : fusedEnv;  // 0 off, 1 on, 2 by the size of the bed
+    return (fusedMode == 2 ? c->nOwners <= DEME_FUSED_AUTO_MAX_OWNERS : fusedMode != 0) && hr.nBig == 0 &&
+           c->hp.forceModel != DEME_FORCE_CUSTOM && !c->record && c->nTri == 0 && !c->hasGhosts && !c->prescFn && !c->rulesFn &&
+           c->hShared.empty() && c->asyncLead == 0 && !c->ad.autoBinSize && !c->ad.autoUpdateFreq;
+}
 
-// Part 2 of a detection: the history map and the structures of `L`, built on `st` from the owner records `ow` (the live ones --
-// or, beside steps that are integrating them, the snapshot part 1 was made from) and the nC keys part 1 left in the next key
-// buffer.  Everything fallible comes first and touches `L` only; the context turns to the new list in the last lines.
-int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st, uint64_t nC) {
+// ---- part 2 of a detection, piece by piece: each builds structures of `L` on `st` and touches nothing else of the context
+// The history map of the nC keys in the next key buffer against the current list, the owners of every contact, the work list of
+// the mesh-variant force kernel and the starts of the A owners' runs.
+int build_owner_arrays(deme_ctx* c, ContactList& L, hipStream_t st, uint64_t nC, bool tileEligible) {
     const int next = c->keysCur ^ 1;
-    L.invalidate();  // (a pending read-back of this list's last build is superseded)
-    const bool tileEligible = tile_eligible(c, nC);
-    const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
+    const uint32_t nTiles = tile_count(c);
     if (nC) {
         const uint64_t nPrev = c->haveList ? c->nContacts : 0;
         hipLaunchKernelGGL(k_history, dim3(grid_for(nC)), dim3(256), 0, st, (uint32_t)nC, c->keysSorted[next].as<uint64_t>(),
@@ -991,73 +1082,109 @@ int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st
         HIPCK(hipMemsetAsync(L.aStart.p, 0, ((size_t)c->nOwners + 1) * 4, st));
     }
     L.nListed = nC, L.listKeys = next;
-    bool tiled = false;
-    RangeCounters hr{};
-    if (tileEligible) {  // owner tiles (deme_tile.h): the builders of the list structures k_tile_forces and the integrator read
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, st, L.tileRem.as<uint32_t>(), L.tileBase.as<uint32_t>(), nTiles + 1,
-                           &L.rangeCtr.as<RangeCounters>()->nRemote);
-        hipLaunchKernelGGL(k_tile_build, dim3(nTiles), dim3(256), 0, st, c->dp, c->nOwners, L.info.as<uint4>(),
-                           L.ownerB[0].as<uint32_t>(), L.aStart.as<uint32_t>(), ow, L.tileBase.as<uint32_t>(), L.tInfo.as<uint2>(),
-                           L.hList.as<uint32_t>(), L.hCount.as<uint32_t>(),
-                           c->hasGhosts ? L.tileMode.as<uint32_t>() : (uint32_t*)nullptr, L.lOff.as<uint16_t>(),
-                           L.lPos.as<uint16_t>(), L.lCount.as<uint32_t>(), L.rankC.as<uint32_t>(), L.remKey[0].as<uint32_t>(),
-                           L.remVal.as<uint32_t>(), L.tileOrg.as<int64_t>(), L.rangeCtr.as<RangeCounters>(), nTiles,
-                           L.tileBig.as<uint32_t>(), L.bigList.as<uint32_t>(), c->recContact.as<uint32_t>());
-        hipLaunchKernelGGL(k_tile_stats, dim3((nTiles + 1023u) / 1024u), dim3(256), 0, st, nTiles, L.hCount.as<uint32_t>(),
-                           L.lCount.as<uint32_t>(), L.rangeCtr.as<RangeCounters>());
-        uint32_t nR = 0;  // crossing contacts = records = entries of the sort below: the one size the host has to know
-        HIPCK(hipMemcpyAsync(pin_at<RangeCounters>(c, 128), L.rangeCtr.p, sizeof(hr), hipMemcpyDeviceToHost, st));
-        HIPCK(sync_readback(c, st, true));  // (part 2 is short, also beside the steps)
-        hr = *pin_at<RangeCounters>(c, 128);
-        // (nExtra: the records of the tiles that do not fit (k_tile_forces_big): every contact of such a tile has one)
-        nR = (uint32_t)hr.nRemote + hr.nExtra;
-        L.nBigTiles = hr.nBig;
-        const unsigned obits = bits_for(c->nOwners, 32);
-        if (nR) {
-            if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
-                    return deme_radix_sort<DemeRadixCfg<10>, true>(tmp, bytes, L.remKey[0].as<uint32_t>(), L.remKey[1].as<uint32_t>(),
-                                                                   L.remVal.as<uint32_t>(), L.rIdx.as<uint32_t>(), (size_t)nR, (size_t)c->cntCap, 0, obits,
-                                                                   DEME_SORT_OWN_FROM_RECORDS, st);
-                }))
-                return rc;
-            hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nR)), dim3(256), 0, st, nR, L.remKey[1].as<uint32_t>(), c->nOwners,
-                               L.rStart.as<uint32_t>());
-        } else {
-            HIPCK(hipMemsetAsync(L.rStart.p, 0, ((size_t)c->nOwners + 1) * 4, st));
-        }
-        hipLaunchKernelGGL(k_owner_ranges_tile, dim3(grid_for(c->nOwners)), dim3(256), 0, st, c->dp, ow, L.aStart.as<uint32_t>(),
-                           L.lOff.as<uint16_t>(), L.rStart.as<uint32_t>(), L.heavy.as<uint8_t>(), L.fixedFlag.as<uint8_t>(),
-                           L.heavyList.as<uint32_t>(), (uint32_t)(L.heavyList.bytes / 4), L.rangeCtr.as<RangeCounters>());
-        tiled = true;
-        // closed tiles (deme_tile_step.h): the contacts that hold a tile's owners as B from other tiles, in the tile's frame
-        // (never for a context with asynchronous detection on: the closed-tile structures exist once -- see deme_ctx)
-        static const int fusedEnv = getenv("DEME_FUSED") ? atoi(getenv("DEME_FUSED")) : -1;  // (1 / 0 override the context's switch)
-        const int fusedMode = fusedEnv < 0 ? c->fusedEnable : fusedEnv;  // 0 off, 1 on, 2 by the size of the bed
-        if ((fusedMode == 2 ? c->nOwners <= DEME_FUSED_AUTO_MAX_OWNERS : fusedMode != 0) && hr.nBig == 0 && c->hp.forceModel != DEME_FORCE_CUSTOM && !c->record && c->nTri == 0 &&
-            !c->hasGhosts && !c->prescFn && !c->rulesFn && c->hShared.empty() && c->asyncLead == 0 &&
-            !c->ad.autoBinSize && !c->ad.autoUpdateFreq) {
-            hipLaunchKernelGGL(k_in_count, dim3(grid_for((size_t)c->nOwners + 1)), dim3(256), 0, st, c->dp, ow,
-                               L.rStart.as<uint32_t>(), c->inCnt.as<uint32_t>());
-            if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
-                    return rocprim::exclusive_scan(tmp, bytes, c->inCnt.as<uint32_t>(), c->inStart.as<uint32_t>(), 0u, (size_t)c->nOwners + 1,
-                                                   rocprim::plus<uint32_t>(), st);
-                }))
-                return rc;
-            hipLaunchKernelGGL(k_tile_incoming, dim3(nTiles), dim3(256), 0, st, c->dp, c->nOwners, L.info.as<uint4>(),
-                               L.rStart.as<uint32_t>(), L.rIdx.as<uint32_t>(), c->recContact.as<uint32_t>(), c->inStart.as<uint32_t>(),
-                               L.hList.as<uint32_t>(), L.hCount.as<uint32_t>(), c->hCountIn.as<uint32_t>(), c->tInfoIn.as<uint2>(),
-                               c->inContact.as<uint32_t>(), L.rangeCtr.as<RangeCounters>());
-            L.fusedList = true;  // (whether every closed tile fits comes back with the counters below: fused_ready)
-        }
+    return DEME_OK;
+}
+// Owner tiles (deme_tile.h): the list structures k_tile_forces and the integrator read.  `hr`: the counters as the host needs them
+// in the middle -- the tiles' extremes and the number of crossing contacts, the one size the sort of their records has to know.
+int build_tiles(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st, RangeCounters& hr) {
+    const uint32_t nTiles = tile_count(c);
+    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, st, L.tileRem.as<uint32_t>(), L.tileBase.as<uint32_t>(), nTiles + 1,
+                       &L.rangeCtr.as<RangeCounters>()->nRemote);
+    hipLaunchKernelGGL(k_tile_build, dim3(nTiles), dim3(256), 0, st, c->dp, c->nOwners, L.info.as<uint4>(),
+                       L.ownerB[0].as<uint32_t>(), L.aStart.as<uint32_t>(), ow, L.tileBase.as<uint32_t>(), L.tInfo.as<uint2>(),
+                       L.hList.as<uint32_t>(), L.hCount.as<uint32_t>(),
+                       c->hasGhosts ? L.tileMode.as<uint32_t>() : (uint32_t*)nullptr, L.lOff.as<uint16_t>(),
+                       L.lPos.as<uint16_t>(), L.lCount.as<uint32_t>(), L.rankC.as<uint32_t>(), L.remKey[0].as<uint32_t>(),
+                       L.remVal.as<uint32_t>(), L.tileOrg.as<int64_t>(), L.rangeCtr.as<RangeCounters>(), nTiles,
+                       L.tileBig.as<uint32_t>(), L.bigList.as<uint32_t>(), c->recContact.as<uint32_t>());
+    hipLaunchKernelGGL(k_tile_stats, dim3((nTiles + 1023u) / 1024u), dim3(256), 0, st, nTiles, L.hCount.as<uint32_t>(),
+                       L.lCount.as<uint32_t>(), L.rangeCtr.as<RangeCounters>());
+    const RangeCounters* got = read_back<RangeCounters>(c, PIN_RANGES, L.rangeCtr.p, st, true);  // (part 2 is short, also beside the steps)
+    if (!got)
+        return c->lastStatus;
+    hr = *got;
+    // crossing contacts = records = entries of the sort below
+    // (nExtra: the records of the tiles that do not fit (k_tile_forces_big): every contact of such a tile has one)
+    const uint32_t nR = (uint32_t)hr.nRemote + hr.nExtra;
+    L.nBigTiles = hr.nBig;
+    const unsigned obits = bits_for(c->nOwners, 32);
+    if (nR) {
+        if (int rc = with_temp(c, c->sortTmp, [&](void* tmp, size_t& bytes) {
+                return deme_radix_sort<DemeRadixCfg<10>, true>(tmp, bytes, L.remKey[0].as<uint32_t>(), L.remKey[1].as<uint32_t>(),
+                                                               L.remVal.as<uint32_t>(), L.rIdx.as<uint32_t>(), (size_t)nR, (size_t)c->cntCap, 0, obits,
+                                                               DEME_SORT_OWN_FROM_RECORDS, st);
+            }))
+            return rc;
+        hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nR)), dim3(256), 0, st, nR, L.remKey[1].as<uint32_t>(), c->nOwners,
+                           L.rStart.as<uint32_t>());
+    } else {
+        HIPCK(hipMemsetAsync(L.rStart.p, 0, ((size_t)c->nOwners + 1) * 4, st));
     }
-    if (tiled) {  // (hr holds the tile extremes already; nSA / nSM are not used by the tile path)
-        if (!c->hrPinned) {
-            HIPCK(hipHostMalloc((void**)&c->hrPinned, sizeof(RangeCounters), hipHostMallocDefault));
-            HIPCK(hipEventCreateWithFlags(&c->hrEvent, hipEventDisableTiming));
-        }
-        HIPCK(hipMemcpyAsync(c->hrPinned, L.rangeCtr.p, sizeof(RangeCounters), hipMemcpyDeviceToHost, st));
-        HIPCK(hipEventRecord(c->hrEvent, st));
-        L.hrPending = true;
+    hipLaunchKernelGGL(k_owner_ranges_tile, dim3(grid_for(c->nOwners)), dim3(256), 0, st, c->dp, ow, L.aStart.as<uint32_t>(),
+                       L.lOff.as<uint16_t>(), L.rStart.as<uint32_t>(), L.heavy.as<uint8_t>(), L.fixedFlag.as<uint8_t>(),
+                       L.heavyList.as<uint32_t>(), (uint32_t)(L.heavyList.bytes / 4), L.rangeCtr.as<RangeCounters>());
+    return DEME_OK;
+}
+// Closed tiles (deme_tile_step.h): the contacts that hold a tile's owners as B from other tiles, in the tile's frame.  Whether
+// every closed tile fits comes back with the pending heavy-owner counts (resolve_heavy_counts).
+int build_closed_tiles(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st) {
+    const uint32_t nTiles = tile_count(c);
+    hipLaunchKernelGGL(k_in_count, dim3(grid_for((size_t)c->nOwners + 1)), dim3(256), 0, st, c->dp, ow,
+                       L.rStart.as<uint32_t>(), c->inCnt.as<uint32_t>());
+    if (int rc = with_temp(c, c->scanTmp, [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->inCnt.as<uint32_t>(), c->inStart.as<uint32_t>(), 0u, (size_t)c->nOwners + 1,
+                                           rocprim::plus<uint32_t>(), st);
+        }))
+        return rc;
+    hipLaunchKernelGGL(k_tile_incoming, dim3(nTiles), dim3(256), 0, st, c->dp, c->nOwners, L.info.as<uint4>(),
+                       L.rStart.as<uint32_t>(), L.rIdx.as<uint32_t>(), c->recContact.as<uint32_t>(), c->inStart.as<uint32_t>(),
+                       L.hList.as<uint32_t>(), L.hCount.as<uint32_t>(), c->hCountIn.as<uint32_t>(), c->tInfoIn.as<uint2>(),
+                       c->inContact.as<uint32_t>(), L.rangeCtr.as<RangeCounters>());
+    L.fusedList = true;
+    return DEME_OK;
+}
+// The heavy-owner counts of a tiled list are fetched without stopping the stream: the first reader waits for the event
+// (resolve_heavy_counts, one force launch later).
+int fetch_heavy_counts(deme_ctx* c, ContactList& L, hipStream_t st) {
+    if (!c->hrEvent)
+        HIPCK(hipEventCreateWithFlags(&c->hrEvent, hipEventDisableTiming));
+    HIPCK(hipMemcpyAsync(pin_at<RangeCounters>(c, PIN_HEAVY), L.rangeCtr.p, sizeof(RangeCounters), hipMemcpyDeviceToHost, st));
+    HIPCK(hipEventRecord(c->hrEvent, st));
+    L.hrPending = true;
+    return DEME_OK;
+}
+// The list of nC contacts is built (in list[cur], or in the list the caller is about to flip to): the context turns to it.
+void commit_list(deme_ctx* c, uint64_t nC) {
+    c->fusedPrevValid = false;  // (a replay of the last fused step would read the list it was taken with)
+    c->conValid = false;
+    c->nPrev = c->haveList ? c->nContacts : 0;
+    c->nContacts = nC;
+    c->keysCur ^= 1;
+    c->listSerial++;
+    c->haveList = true;
+    c->seeded = false;
+    c->mapFresh = true;
+    c->nDetections++;
+}
+
+void order_watch_drift(deme_ctx* c, const RangeCounters& hr);  // (deme_order.inc)
+// Part 2 of a detection: the history map and the structures of `L`, built on `st` from the owner records `ow` (the live ones --
+// or, beside steps that are integrating them, the snapshot part 1 was made from) and the nC keys part 1 left in the next key
+// buffer.  Everything fallible comes first and touches `L` only; the two calls at the end cannot fail and turn the context.
+int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st, uint64_t nC) {
+    L.invalidate();  // (a pending read-back of this list's last build is superseded)
+    const bool tiled = tile_eligible(c, nC);
+    RangeCounters hr{};
+    if (int rc = build_owner_arrays(c, L, st, nC, tiled))
+        return rc;
+    if (tiled) {
+        if (int rc = build_tiles(c, L, ow, st, hr))
+            return rc;
+        if (fused_eligible(c, hr))
+            if (int rc = build_closed_tiles(c, L, ow, st))
+                return rc;
+        if (int rc = fetch_heavy_counts(c, L, st))  // (hr holds the tile extremes already; nSA / nSM are not used by the tile path)
+            return rc;
     } else {
         if (int rc = build_legacy_lists(c, L, ow, st))
             return rc;
@@ -1068,28 +1195,9 @@ int detect_part2(deme_ctx* c, ContactList& L, const OwnerRec* ow, hipStream_t st
     L.tileMaxHalo = hr.tileMaxHalo, L.tileMaxList = hr.tileMaxList;
     L.nSA = hr.nSA;
     L.nSM = hr.nSM;
-    // ---- the list is built: the context turns to it
-    c->fusedPrevValid = false;  // (a replay of the last fused step would read the list it was taken with)
-    if (tiled && c->orderEligible) {  // has the bed drifted away from the order it was given?  (order_renew at the next detection)
-        const uint32_t fit = std::max(1u, nTiles - std::min(nTiles, hr.nBig));
-        const uint32_t mean16 = (uint32_t)(16ull * hr.tileHaloSum / fit);
-        if (!c->orderBaseHalo) {
-            c->orderBaseHalo = std::max(mean16, 16u);
-            c->orderDetAt = c->nDetections;
-        } else if (c->nDetections - c->orderDetAt >= 20 && nTiles > 4 &&
-                   (hr.nBig > std::max(4u, nTiles / 64u) || mean16 > c->orderBaseHalo + c->orderBaseHalo / 2)) {
-            c->orderRenewDue = true;
-        }
-    }
-    c->conValid = false;
-    c->nPrev = c->haveList ? c->nContacts : 0;
-    c->nContacts = nC;
-    c->keysCur = next;
-    c->listSerial++;
-    c->haveList = true;
-    c->seeded = false;
-    c->mapFresh = true;
-    c->nDetections++;
+    if (tiled)
+        order_watch_drift(c, hr);
+    commit_list(c, nC);
     return DEME_OK;
 }
 
@@ -1158,10 +1266,11 @@ void resolve_heavy_counts(deme_ctx* c, ContactList& L) {
         return;
     }
     const size_t cap = L.heavyList.bytes / 4;
-    L.nHeavy = c->hrPinned->nHeavy, L.nHeavyFree = c->hrPinned->nHeavyFree;
+    const RangeCounters* hr = pin_at<RangeCounters>(c, PIN_HEAVY);
+    L.nHeavy = hr->nHeavy, L.nHeavyFree = hr->nHeavyFree;
     if (L.fusedList) {  // the halos were extended by the incoming contacts' owners (k_tile_incoming): the kernels' LDS follows
-        L.tileMaxHaloIn = c->hrPinned->tileMaxHaloIn;
-        if (c->hrPinned->nBigIn)  // a closed tile does not fit: this list keeps force pass + integrator
+        L.tileMaxHaloIn = hr->tileMaxHaloIn;
+        if (hr->nBigIn)  // a closed tile does not fit: this list keeps force pass + integrator
             L.fusedList = false;
         L.fusedChecked = true;
     }
@@ -1579,7 +1688,7 @@ int deme_ctx_create(int device, deme_ctx** out) {
         return DEME_ERR_HIP;
     }
     hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->stream);
-    if (hipHostMalloc((void**)&c->pin, 16384, hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc((void**)&c->pin, PIN_BYTES, hipHostMallocDefault) != hipSuccess) {
         deme_ctx_destroy(c);
         return DEME_ERR_HIP;
     }
@@ -1624,10 +1733,8 @@ void deme_ctx_destroy(deme_ctx* c) {
         for (DevBuf* b : l.buffers())
             if (b->p)
                 hipFree(b->p);
-    if (c->hrPinned) {
-        hipHostFree(c->hrPinned);
+    if (c->hrEvent)
         hipEventDestroy(c->hrEvent);
-    }
     if (c->detStream) {
         hipStreamSynchronize(c->detStream);
         hipEventDestroy(c->evSnap);
@@ -2407,14 +2514,19 @@ static bool async_detection_can_start(deme_ctx* c, uint32_t stepsLeftInCall) {
         return false;
     return c->stepsSinceCD == K - D;
 }
+static int async_stream(deme_ctx* c) {  // the detection stream and its two events, made once
+    if (c->detStream)
+        return DEME_OK;
+    HIPCK(hipStreamCreateWithFlags(&c->detStream, hipStreamNonBlocking));
+    HIPCK(hipEventCreateWithFlags(&c->evSnap, hipEventDisableTiming));
+    HIPCK(hipEventCreateWithFlags(&c->evP1, hipEventDisableTiming));
+    return DEME_OK;
+}
 // the three phases of one asynchronous detection: the owner snapshot (on the main stream, between two integrations), part 1 beside
 // the next D steps, the swap
 static int async_snapshot(deme_ctx* c) {
-    if (!c->detStream) {
-        HIPCK(hipStreamCreateWithFlags(&c->detStream, hipStreamNonBlocking));
-        HIPCK(hipEventCreateWithFlags(&c->evSnap, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&c->evP1, hipEventDisableTiming));
-    }
+    if (int rc = async_stream(c))
+        return rc;
     if (int rc = ensure(c, c->ownersSnap, (size_t)c->nOwners * sizeof(OwnerRec)))
         return rc;
     HIPCK(hipMemcpyAsync(c->ownersSnap.p, c->owners.p, (size_t)c->nOwners * sizeof(OwnerRec), hipMemcpyDeviceToDevice, c->stream));
@@ -2426,11 +2538,8 @@ static int async_part1(deme_ctx* c, uint64_t* nC) {
     const uint32_t K = c->hp.cdUpdateFreq, D = c->asyncLead;
     HIPCK(hipStreamWaitEvent(c->detStream, c->evSnap, 0));
     ScopedTimer tm(c, "detect_async_part1", true, c->detStream);
-    HIPCK(hipMemsetAsync(c->ctr.p, 0, sizeof(DetectBlock), c->detStream));
-    if (c->nOwners)  // (an ownerless scene: no launch of no workgroups, see deme_set_margins)
-    hipLaunchKernelGGL(k_margins, dim3(grid_for(c->nOwners)), dim3(256), 0, c->detStream, c->dp, c->ownersSnap.as<OwnerRec>(),
-                       K + D, c->ctr.as<DetectCounters>());
-    c->ctrFresh = true;
+    if (int rc = launch_margins(c, c->detStream, c->ownersSnap.as<OwnerRec>(), K + D))
+        return rc;
     if (int rc = detect_part1(c, c->detStream, c->ownersSnap.as<OwnerRec>(), true, nC))
         return rc;
     HIPCK(hipEventRecord(c->evP1, c->detStream));
@@ -2446,11 +2555,8 @@ static int async_size_next(deme_ctx* c) {
 // streams, events and buffers of the asynchronous detection, made when it is switched on (a first cycle that allocates a
 // gigabyte of list structures inside a short timed run costs more than the detection it hides)
 static int async_prepare(deme_ctx* c) {
-    if (!c->detStream) {
-        HIPCK(hipStreamCreateWithFlags(&c->detStream, hipStreamNonBlocking));
-        HIPCK(hipEventCreateWithFlags(&c->evSnap, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&c->evP1, hipEventDisableTiming));
-    }
+    if (int rc = async_stream(c))
+        return rc;
     if (!c->haveParams || !c->haveScene)
         return DEME_OK;
     if (int rc = ensure(c, c->ownersSnap, (size_t)c->nOwners * sizeof(OwnerRec)))

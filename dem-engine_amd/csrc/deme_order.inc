@@ -218,11 +218,28 @@ int order_current_view(deme_ctx* c) {
     return DEME_OK;
 }
 
+// Has the bed drifted away from the order it was given?  Called by every detection that built tiles, with their counters: the
+// mean halo of the fitting tiles and the tiles that do not fit, against what they were at the first detection after the last
+// ordering.  Sets orderRenewDue (order_renew at the next detection).
+void order_watch_drift(deme_ctx* c, const RangeCounters& hr) {
+    if (!c->orderEligible)
+        return;
+    const uint32_t nTiles = (c->nOwners + DEME_TILE_NB - 1) / DEME_TILE_NB;
+    const uint32_t fit = std::max(1u, nTiles - std::min(nTiles, hr.nBig));
+    const uint32_t mean16 = (uint32_t)(16ull * hr.tileHaloSum / fit);
+    if (!c->orderBaseHalo) {
+        c->orderBaseHalo = std::max(mean16, 16u);
+        c->orderDetAt = c->nDetections;
+    } else if (c->nDetections - c->orderDetAt >= 20 && nTiles > 4 &&
+               (hr.nBig > std::max(4u, nTiles / 64u) || mean16 > c->orderBaseHalo + c->orderBaseHalo / 2)) {
+        c->orderRenewDue = true;
+    }
+}
 
 }  // namespace
 
 // Renew the engine's order of a RUNNING simulation (a mixer, a flowing bed: the clumps drift away from the tiles they were put in,
-// the tiles' halos grow, tiles stop fitting -- detect_part2 watches both and sets orderRenewDue; deme_renew_order forces it).
+// the tiles' halos grow, tiles stop fitting -- order_watch_drift watches both and sets orderRenewDue; deme_renew_order forces it).
 // Called at the start of a detection, on a synchronised context: the owners' positions come to the host, the order is computed as
 // at upload (order_compute), and everything that is kept in engine slots follows -- owner and sphere records, the sphere -> owner
 // references, pending added accelerations, persistent marks, and the current contact list with its history, re-keyed and re-sorted

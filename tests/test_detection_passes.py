@@ -101,6 +101,15 @@ def test_two_level_scan_uneven_counts(pkg):
     assert cnt[255] == 27 and (np.delete(cnt, 255) == 1).all()
 
 
+def test_incidence_arena_grows_after_early_fill(pkg):
+    """600 spheres of 8 mm at bin centres, 3 cm apart: every one reaches into 27 bins, 16 200 incidences against the arena of
+    max(8 x 600, 4096) = 4800 slots the upload made.  k_fill_incidence has gone out before the host knows the total and stopped
+    at the arena's end; the list must be the one filled again into the grown arena"""
+    n = 600
+    cnt = _check_incidence(pkg, _grid(n, 0.03, origin=0.025), np.full(n, 0.008))
+    assert (cnt == 27).all() and int(cnt.sum()) == 16200 > max(8 * n, 4096)
+
+
 def _dense(pkg, n=800, cd_freq=0):
     return pkg.model.packed_bed(n, seed=23, cd_freq=cd_freq, spacing_mult=1.5)  # (test_contact_arena_growth's scene: > 6 contacts a sphere)
 
@@ -134,16 +143,31 @@ def test_folded_clears_two_detections(pkg):
     ctx2.close()
 
 
-def test_folded_clears_async_detection(pkg):
-    """detections beside the steps (two lists, a stream of their own) on a bed that does not move: spheres 0.2 mm apart, no
-    gravity, margins of 0.15 mm from the safety velocity over K + D = 30 steps.  Every asynchronous detection must build the
-    list that one lock-step detection with the same margins builds -- nothing left over from the detection before it"""
-    K, D = 20, 10
+# (spheres, pitch, safety adder, D, detections checked, pairs per sphere the list must exceed, pairs of the first list if stated)
+ASYNC_BEDS = {
+    # spheres 0.2 mm apart, margins of 0.15 mm from the safety velocity over K + D = 30 steps: the near pairs along the grid's axes
+    "axis_pairs": (3000, 0.0022, 1.0, 10, 3, 1, None),
+    # 10 x 10 x 10 spheres 0.02 mm apart.  A resting owner's margin is adder x h x drift (k_margins) = 3 x 5e-6 x drift: twice
+    # that is 0.6 mm over the K steps of the first, lock-step detection -- the 2700 axis pairs, inside the 6 x 1000 slots the
+    # upload gave the contact arena -- and 1.05 mm over K + D = 35, which takes in the face diagonals (gap 0.857 mm; the body
+    # diagonals at 1.499 mm stay out): 7560 pairs (both counts from tests/_detect64.py), so the arena grows in part 1 of the
+    # first asynchronous detection, beside the steps
+    "arena_grows_beside_the_steps": (1000, 0.00202, 3.0, 15, 2, 6, 2700),
+}
+
+
+@pytest.mark.parametrize("bed_name", list(ASYNC_BEDS))
+def test_folded_clears_async_detection(pkg, bed_name):
+    """detections beside the steps (two lists, a stream of their own) on a bed that does not move (no gravity, no overlap).
+    Every asynchronous detection must build the list that one lock-step detection with the same margins builds -- nothing left
+    over from the detection before it"""
+    K = 20
+    n, pitch, adder, D, rounds, per_sphere, first = ASYNC_BEDS[bed_name]
 
     def bed():
-        b = _spheres(pkg, _grid(3000, 0.0022), cd_freq=K)
+        b = _spheres(pkg, _grid(n, pitch), cd_freq=K)
         b.SetGravitationalAcceleration((0, 0, 0))
-        b.SetExpandSafetyAdder(1.0)
+        b.SetExpandSafetyAdder(adder)
         return b
 
     ref, *_ = _context(pkg, bed())
@@ -152,17 +176,21 @@ def test_folded_clears_async_detection(pkg):
     want = ref.contacts()[:3]
     nb, mx = int(ref.counts().nActiveBins), int(ref.counts().maxSpheresInBin)
     ref.close()
-    assert len(want[0]) > 3000  # the near pairs along the grid's axes
+    assert len(want[0]) > per_sphere * n
     ctx, *_ = _context(pkg, bed())
     ctx.set_async_detection(D)
-    for steps in (2 * K + 1, K, K):  # after the second, third and fourth detection
+    ctx.set_timing(1)
+    ctx.step(1)  # the first detection, in lock-step with margins for K steps
+    assert first is None or int(ctx.counts().nContacts) == first < 6 * n
+    for steps in (2 * K,) + (K,) * (rounds - 1):  # after the second, third ... detection
         ctx.step(steps)
         c = ctx.counts()
         got = ctx.contacts()[:3]
         assert int(c.nContacts) == len(got[0]) == len(want[0])
         assert all(np.array_equal(g, w) for g, w in zip(got, want))
         assert (int(c.nActiveBins), int(c.maxSpheresInBin)) == (nb, mx)
-    assert int(ctx.counts().nDetections) >= 4
+    assert int(ctx.counts().nDetections) >= rounds + 1
+    assert ctx.kernel_time_ms("detect_async_part1")[1] >= 1  # (the asynchronous path really served)
     ctx.close()
 
 

@@ -374,6 +374,27 @@ def test_persistent_contacts(pkg, orc):
     assert np.array_equal(a, ta) and np.array_equal(b, tb) and np.array_equal(t, tt)
 
 
+def test_persistent_marks_grow_the_contact_arena(pkg, orc):
+    """The marks push the contact arena over after the sweep's keys fitted.  The dense bed of test_contact_arena_growth lists n
+    contacts and leaves an arena of 1.25 n + 1024 slots; with every contact marked, the next detection appends n marks to the
+    n keys of the sweep: 2 n slots, more than the arena has once n > 1366.  It grows, the emitting kernels run again, and the
+    duplicates go: the list is the first one, row for row, on both sides."""
+    b = pkg.model.packed_bed(800, seed=23, cd_freq=0, spacing_mult=1.5)
+    ctx, sim, p, sc = pair(pkg, orc, b)
+    ctx.detect(), sim.detect()
+    first = assert_same_contacts(ctx, sim)[:3]
+    n = len(first[0])
+    assert n > 6 * sc.nSpheres and n > 1366
+    ctx.mark_persistent_contacts(), sim.mark_persistent_contacts()
+    assert ctx.num_persistent_contacts() == sim.num_persistent_contacts() == n
+    for _ in range(2):  # the detection that grows the arena, and the next one in the grown arena
+        ctx.detect(), sim.detect()
+        again = assert_same_contacts(ctx, sim)[:3]
+        assert all(np.array_equal(x, y) for x, y in zip(again, first))
+        assert len(set(zip(*(x.tolist() for x in again)))) == n  # every marked contact listed once
+        assert ctx.num_persistent_contacts() == n
+
+
 def test_persistent_contacts_need_history(pkg):
     b = persistent_scene(pkg)
     b.UseFrictionlessHertzianModel()
