@@ -621,6 +621,7 @@ struct Sim {
     std::vector<float> tri1, tri2, tri3;  // xyz interleaved
     std::vector<uint16_t> triMat;
     std::vector<uint32_t> triIncBin, triIncTri;  // bin-sorted (stable) triangle incidence list
+    std::vector<float> triSandwich;              // the last detection's world-frame sandwich triangles: a1 a2 a3 b1 b2 b3 per triangle
     // tables
     std::vector<float> Radii, relX, relY, relZ, mass, moiX, moiY, moiZ;
     std::vector<uint8_t> objType;
@@ -904,6 +905,7 @@ int detect(Sim& s) {
             T3f a1, a2, a3, b1, b2, b3;
         };
         std::vector<TriW> tw(s.nTri);
+        s.triSandwich.assign(18 * (size_t)s.nTri, 0.f);
         std::vector<uint32_t> tb, tt;
         const float bhs = (float)(s.p.binSize / 2. + 0.001 * s.p.binSize);  // DEME_BIN_ENLARGE_RATIO_FOR_FACETS
         const float bh[3] = {bhs, bhs, bhs};
@@ -928,6 +930,9 @@ int detect(Sim& s) {
                 w[k] = {(float)(oX + r.x), (float)(oY + r.y), (float)(oZ + r.z)};  // double3 + float3 -> float3
             }
             tw[t] = {w[0], w[1], w[2], w[3], w[4], w[5]};
+            for (int k = 0; k < 6; k++)
+                s.triSandwich[18 * (size_t)t + 3 * k] = w[k].x, s.triSandwich[18 * (size_t)t + 3 * k + 1] = w[k].y,
+                                   s.triSandwich[18 * (size_t)t + 3 * k + 2] = w[k].z;
             // boundingBoxIntersectBin (DEMHelperKernels.cuh:528-565) on both sandwich triangles, merged
             int L[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, U[3] = {-1, -1, -1};
             const int nbm[3] = {(int)s.p.nbX - 1, (int)s.p.nbY - 1, (int)s.p.nbZ - 1};
@@ -1719,6 +1724,11 @@ size_t orc_sim_get_tri_incidence(void* h, uint32_t* bins, uint32_t* tris, size_t
     std::copy(s->triIncBin.begin(), s->triIncBin.begin() + n, bins);
     std::copy(s->triIncTri.begin(), s->triIncTri.begin() + n, tris);
     return s->triIncBin.size();
+}
+size_t orc_sim_get_tri_sandwich(void* h, float* out, size_t cap) {
+    Sim* s = (Sim*)h;
+    std::copy(s->triSandwich.begin(), s->triSandwich.begin() + std::min(cap, s->triSandwich.size()), out);
+    return s->triSandwich.size();
 }
 void orc_sim_set_tri_nodes(void* h, const float* n1, const float* n2, const float* n3) {
     Sim* s = (Sim*)h;

@@ -392,6 +392,22 @@ class OracleSim:
         arrs = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in (n1, n2, n3)]
         self.L.orc_sim_set_tri_nodes(C.c_void_p(self.h), *[_p(a) for a in arrs])
 
+    def tri_incidence(self):
+        """the last detection's (bin, triangle) incidences, sorted by bin"""
+        self.L.orc_sim_get_tri_incidence.restype = C.c_size_t
+        n = int(self.L.orc_sim_get_tri_incidence(C.c_void_p(self.h), None, None, C.c_size_t(0)))
+        b, t = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self.L.orc_sim_get_tri_incidence(C.c_void_p(self.h), _p(b), _p(t), C.c_size_t(n))
+        return b, t
+
+    def tri_sandwich(self):
+        """the last detection's sandwich triangles in the world frame, fp32: (nTri, 6, 3) = a1 a2 a3 b1 b2 b3"""
+        self.L.orc_sim_get_tri_sandwich.restype = C.c_size_t
+        n = int(self.L.orc_sim_get_tri_sandwich(C.c_void_p(self.h), None, C.c_size_t(0)))
+        out = np.zeros(n, np.float32)
+        self.L.orc_sim_get_tri_sandwich(C.c_void_p(self.h), _p(out), C.c_size_t(n))
+        return out.reshape(-1, 6, 3)
+
     def sphere_geometry(self):
         n = self.n_spheres
         X, Y, Z = (np.zeros(n) for _ in range(3))
