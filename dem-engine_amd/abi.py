@@ -103,6 +103,21 @@ class DemeContactSums(C.Structure):
     _fields_ = [("virial", C.c_double * 9), ("sides", C.c_uint64), ("clumps", C.c_uint64)]
 
 
+# the columns of deme_inspect_fields: dtype and entries per cell
+FIELD_COLUMN_SHAPES = {"clumps": (np.uint32, 1), "mass": (np.float64, 1), "volume": (np.float64, 1), "momentum": (np.float64, 3),
+                       "kinetic": (np.float64, 6), "sides": (np.uint32, 1), "virial": (np.float64, 9)}
+FIELD_COLUMNS = tuple(FIELD_COLUMN_SHAPES)
+FIELDS_MAX_CELLS = 1 << 21  # DEME_FIELDS_MAX_CELLS
+
+
+class DemeFieldGrid(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("cell", C.c_double * 3), ("n", C.c_uint32 * 3)]
+
+
+class DemeFieldColumns(C.Structure):
+    _fields_ = [(name, _P) for name in ("clumps", "mass", "volume", "momentum", "kinetic", "sides", "virial")]
+
+
 class DemeAdaptive(C.Structure):
     """include/deme_hip.h DemeAdaptive; the defaults are the reference's (DEM/Structs.h:204-216)"""
     _fields_ = [("autoBinSize", C.c_uint32), ("binObserveSteps", C.c_uint32), ("binMaxRate", C.c_float), ("binAcc", C.c_float),
@@ -222,6 +237,8 @@ def load_library():
         "deme_multi_inspect_contact_counts": [_P, C.c_char_p, C.c_float, _P, C.c_size_t],
         "deme_inspect_tri_loads": [_P, C.c_float, C.c_uint32, C.c_uint32, _P, _P],
         "deme_multi_inspect_tri_loads": [_P, C.c_float, C.c_uint32, C.c_uint32, _P, _P],
+        "deme_inspect_fields": [_P, C.POINTER(DemeFieldGrid), C.c_float, C.POINTER(DemeFieldColumns)],
+        "deme_multi_inspect_fields": [_P, C.POINTER(DemeFieldGrid), C.c_float, C.POINTER(DemeFieldColumns)],
         "deme_query_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_scatter_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
@@ -247,6 +264,8 @@ def load_library():
     lib.deme_sort_tile_keys.restype = C.c_uint
     lib.deme_tri_loads_block_rows.argtypes = []
     lib.deme_tri_loads_block_rows.restype = C.c_uint
+    lib.deme_fields_block_rows.argtypes = []
+    lib.deme_fields_block_rows.restype = C.c_uint
     lib.deme_halo_unique_id.argtypes = [_P]
     lib.deme_halo_unique_id.restype = C.c_int
     lib.deme_halo_group_create.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]
@@ -730,6 +749,10 @@ class Multi:
         """deme_multi_inspect_tri_loads: Context.inspect_tri_loads of every slab's own list, the slabs' arrays added in slab order"""
         return _inspect_tri_loads(self, self.lib.deme_multi_inspect_tri_loads, "deme_multi_inspect_tri_loads", force_threshold, first, count)
 
+    def inspect_fields(self, origin, cell, n, columns=FIELD_COLUMNS, force_threshold=1e-12):
+        """deme_multi_inspect_fields: Context.inspect_fields of every slab's own clumps, the slabs' columns added in slab order"""
+        return _inspect_fields(self, self.lib.deme_multi_inspect_fields, "deme_multi_inspect_fields", origin, cell, n, columns, force_threshold)
+
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied from the devices to the host since the run was created"""
         v = C.c_uint64(0)
@@ -826,6 +849,29 @@ def sort_tile_keys():
 def tri_loads_block_rows():
     """sorted rows one workgroup of the per-triangle sum takes (inspect_tri_loads): a longer run is summed by several"""
     return int(load_library().deme_tri_loads_block_rows())
+
+
+def fields_block_rows():
+    """sorted entries one workgroup of the per-cell sums takes (inspect_fields): a longer run is summed by several"""
+    return int(load_library().deme_fields_block_rows())
+
+
+def _inspect_fields(self, fn, name, origin, cell, n, columns, force_threshold):
+    """the call both Context.inspect_fields and Multi.inspect_fields make"""
+    unknown = [k for k in columns if k not in FIELD_COLUMN_SHAPES]
+    if unknown:
+        raise ValueError(f"{name}: unknown columns {unknown}; known: {FIELD_COLUMNS}")
+    grid = DemeFieldGrid((C.c_double * 3)(*[float(v) for v in origin]), (C.c_double * 3)(*[float(v) for v in cell]),
+                         (C.c_uint32 * 3)(*[int(v) for v in n]))
+    n_cells = int(grid.n[0]) * int(grid.n[1]) * int(grid.n[2])
+    rows = n_cells if n_cells <= FIELDS_MAX_CELLS else 0  # (a grid the library refuses: nothing is allocated for it)
+    out, cols = {}, DemeFieldColumns()
+    for k in columns:
+        dtype, width = FIELD_COLUMN_SHAPES[k]
+        out[k] = np.zeros(rows if width == 1 else (rows, width), dtype)
+        setattr(cols, k, out[k].ctypes.data if rows else C.addressof(grid))  # (named, never written: the grid is refused first)
+    self._ck(fn(self.h, C.byref(grid), float(force_threshold), C.byref(cols)), name)
+    return out
 
 
 def _inspect_tri_loads(self, fn, name, force_threshold, first, count):
@@ -1253,6 +1299,13 @@ class Context:
         summed over the current list on the device.  (force[n, 3] float64 -- the force ON each triangle, world frame --,
         contacts[n] uint32: the counted sphere-mesh rows of each)"""
         return _inspect_tri_loads(self, self.lib.deme_inspect_tri_loads, "deme_inspect_tri_loads", force_threshold, first, count)
+
+    def inspect_fields(self, origin, cell, n, columns=FIELD_COLUMNS, force_threshold=1e-12):
+        """deme_inspect_fields: per-cell sums on the grid of n = (nx, ny, nz) cells of edges `cell` whose cell (0, 0, 0) has its lower
+        corner at `origin` (world frame), summed on the device.  A dict of the named columns, cell ix + nx * (iy + ny * iz) in row
+        that number: clumps, sides uint32 (nCells,); mass, volume float64 (nCells,); momentum (nCells, 3); kinetic (nCells, 6: xx, yy,
+        zz, xy, xz, yz); virial (nCells, 9: row-major).  The contact columns (sides, virial) need contact recording."""
+        return _inspect_fields(self, self.lib.deme_inspect_fields, "deme_inspect_fields", origin, cell, n, columns, force_threshold)
 
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied to the host since the context was created (count read-backs, hit

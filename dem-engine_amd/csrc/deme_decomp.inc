@@ -1833,6 +1833,48 @@ int deme_multi_inspect_tri_loads(deme_multi* m, float thr, uint32_t firstTri, ui
     return DEME_OK;
 }
 
+// ---- per-cell sums on a grid of a decomposed run (deme_fields.h) ------------------------------------------------------------------------
+// Every slab holds its clumps in the world frame and counts its own clumps only (ghost copies never count), so a clump, and every
+// side it carries, is counted by one slab.  All slabs' passes are enqueued first, each on its device, then the host takes the asked
+// columns slab by slab and adds them in slab order.  The refusals of the contact inspectors (pairsOnce; a slab whose list is a seed, as
+// on the step after a migration) apply only when a contact column is asked.
+int deme_multi_inspect_fields(deme_multi* m, const DemeFieldGrid* grid, float thr, const DemeFieldColumns* out) {
+    const char* who = "deme_multi_inspect_fields";
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    char msg[320];
+    if (int rc = fields_args_refused(msg, who, grid, thr, out))
+        return mfail(m, rc, "%s", msg);
+    const bool askOwner = fields_ask_owner(out), askContact = fields_ask_contact(out);
+    if (askContact)
+        for (auto* g : m->groups)
+            if (g->pairsOnce)
+                return mfail(m, DEME_ERR_INVALID, "%s: the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab "
+                             "that does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
+    if (int rc = deme_multi_sync(m))
+        return rc;
+    DemeFieldColumns perSlab = *out;  // (a slab with an empty list is not asked for its records: slab_records_refused)
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            perSlab.sides = r.c->nContacts ? out->sides : nullptr, perSlab.virial = r.c->nContacts ? out->virial : nullptr;
+            return fields_ctx_refused(r.c, &perSlab);
+        }))
+        return rc;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int { return fields_launch(r.c, grid, thr, askOwner, askContact); }))
+        return rc;
+    const size_t nC = (size_t)grid->n[0] * grid->n[1] * grid->n[2];
+    FieldHost sum(out, nC), h(out, nC);
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            if (int rc = fields_fetch(r.c, nC, h))
+                return rc;
+            m->qHostBytes += h.bytes;
+            sum.add(h);
+            return DEME_OK;
+        }))
+        return rc;
+    sum.hand_over(out);
+    return DEME_OK;
+}
+
 // ---- moving the slab boundaries (load balance of a bed that drifts or piles up) --------------------------------------------------------
 // deme_halo_group_migrate keeps the boundaries where the plan put them.  deme_multi_rebalance recomputes them from the clumps'
 // CURRENT coordinates -- equal counts again, snapped to bin faces like the plan's -- and lets the same migration move the clumps that

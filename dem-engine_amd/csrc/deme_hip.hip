@@ -50,6 +50,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_query.h"
 #include "deme_contact_inspect.h"
 #include "deme_tri_loads.h"
+#include "deme_fields.h"
 #include "deme_sort.h"
 
 using namespace deme_dev;
@@ -138,6 +139,9 @@ struct deme_ctx {
     // triangle loads (deme_tri_loads.h): the (triangle, row) pairs before and after the sort, the sort's own scratch (never the
     // detection's: an asynchronous detection may be sorting), the blocks' partials, the sums and counts per triangle; kept likewise
     DevBuf tlTri[2], tlRow[2], tlTmp, tlPartial, tlForce, tlCount;
+    // field inspector (deme_fields.h): the cell of every owner slot, the (cell, slot) and (cell, side) pairs before and after their
+    // sorts, the sorts' own scratch, the blocks' partials, the columns of every cell; kept likewise
+    DevBuf fiCellOf, fiOwnKey[2], fiOwnVal[2], fiSideKey[2], fiSideVal[2], fiTmp, fiPartial, fiOut;
     std::map<std::string, int> regionBySource;  // deme_multi_inspect_contacts: a region string compiles once per slab context
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
@@ -1753,7 +1757,9 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
                      &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr, &c->qState,
                      &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut, &c->tlTri[0], &c->tlTri[1], &c->tlRow[0], &c->tlRow[1],
-                     &c->tlTmp, &c->tlPartial, &c->tlForce, &c->tlCount};
+                     &c->tlTmp, &c->tlPartial, &c->tlForce, &c->tlCount, &c->fiCellOf, &c->fiOwnKey[0], &c->fiOwnKey[1], &c->fiOwnVal[0],
+                     &c->fiOwnVal[1], &c->fiSideKey[0], &c->fiSideKey[1], &c->fiSideVal[0], &c->fiSideVal[1], &c->fiTmp, &c->fiPartial,
+                     &c->fiOut};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -4999,6 +5005,214 @@ int deme_inspect_tri_loads(deme_ctx* c, float thr, uint32_t firstTri, uint32_t n
         memcpy(force, hf.data(), hf.size() * 8);
     if (contacts)
         memcpy(contacts, hn.data(), hn.size() * 4);
+    return DEME_OK;
+}
+
+// ---- per-cell sums on a grid (deme_fields.h) ------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t FIELD_CELL_BYTES = 168;  // of fiOut: two counts and 20 doubles a cell
+// what deme_inspect_fields refuses of its arguments alone, in the order it does (the text goes to msg)
+int fields_args_refused(char (&msg)[320], const char* who, const DemeFieldGrid* g, float thr, const DemeFieldColumns* out) {
+    msg[0] = 0;
+    if (!g || !out) {
+        snprintf(msg, sizeof msg, "%s: null %s", who, !g ? "grid" : "columns");
+        return DEME_ERR_INVALID;
+    }
+    bool finite = true, positive = true, cells = true;
+    for (int k = 0; k < 3; k++)
+        finite = finite && std::isfinite(g->origin[k]) && std::isfinite(g->cell[k]), positive = positive && g->cell[k] > 0.0, cells = cells && g->n[k];
+    const uint64_t cap = DEME_FIELDS_MAX_CELLS;
+    if (!finite)
+        snprintf(msg, sizeof msg, "%s: the grid's origin (%g, %g, %g) and cell edges (%g, %g, %g) must be finite", who, g->origin[0], g->origin[1],
+                 g->origin[2], g->cell[0], g->cell[1], g->cell[2]);
+    else if (!positive)
+        snprintf(msg, sizeof msg, "%s: the cell edges are (%g, %g, %g); each must be > 0", who, g->cell[0], g->cell[1], g->cell[2]);
+    else if (!cells)
+        snprintf(msg, sizeof msg, "%s: the grid has %u x %u x %u cells; each count must be > 0", who, g->n[0], g->n[1], g->n[2]);
+    else if (g->n[0] > cap || (uint64_t)g->n[0] * g->n[1] > cap || (uint64_t)g->n[0] * g->n[1] * g->n[2] > cap)  // (no product overflows)
+        snprintf(msg, sizeof msg, "%s: the grid has %u x %u x %u cells; at most %llu in all", who, g->n[0], g->n[1], g->n[2], (unsigned long long)cap);
+    else if (!out->clumps && !out->mass && !out->volume && !out->momentum && !out->kinetic && !out->sides && !out->virial)
+        snprintf(msg, sizeof msg, "%s: null output (every column)", who);
+    else if (!std::isfinite(thr) || thr < 0.f)
+        snprintf(msg, sizeof msg, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    return msg[0] ? DEME_ERR_INVALID : DEME_OK;
+}
+inline bool fields_ask_owner(const DemeFieldColumns* o) { return o->clumps || o->mass || o->volume || o->momentum || o->kinetic; }
+inline bool fields_ask_contact(const DemeFieldColumns* o) { return o->sides || o->virial; }
+// what one context refuses of a question whose arguments are in order (the text is left in c->err)
+int fields_ctx_refused(deme_ctx* c, const DemeFieldColumns* out) {
+    if (out->volume && !c->haveVolumes)
+        return fail(c, DEME_ERR_INVALID, "clump_volume needs the templates' volumes (deme_upload_volumes)");
+    if (!fields_ask_contact(out))
+        return DEME_OK;
+    if (int rc = records_refused(c))
+        return rc;
+    if (c->haveList && c->nContacts >= ((uint64_t)1 << 31))
+        return fail(c, DEME_ERR_INVALID, "the list has %llu rows; two entries a row are indexed with 32 bits", (unsigned long long)c->nContacts);
+    return DEME_OK;
+}
+// the columns of nC cells in fiOut
+struct FieldOutDev {
+    FieldOwnerOut own;
+    FieldSideOut side;
+};
+FieldOutDev fields_out(deme_ctx* c, size_t nC) {
+    char* b = c->fiOut.as<char>();
+    double* d = reinterpret_cast<double*>(b + 8 * nC);
+    FieldOutDev o;
+    o.own.clumps = reinterpret_cast<uint32_t*>(b), o.side.sides = reinterpret_cast<uint32_t*>(b) + nC;
+    o.own.mass = d, o.own.volume = d + nC, o.own.momentum = d + 2 * nC, o.own.kinetic = d + 5 * nC, o.side.virial = d + 11 * nC;
+    return o;
+}
+// The passes of one context, enqueued on its stream: the asked groups of columns are left in fiOut.  Nothing the step reads is
+// written.
+int fields_launch(deme_ctx* c, const DemeFieldGrid* g, float thr, bool askOwner, bool askContact) {
+    const size_t nO = c->nOwners, n = askContact && c->haveList ? (size_t)c->nContacts : 0;
+    const size_t nC = (size_t)g->n[0] * g->n[1] * g->n[2];
+    if (ensure(c, c->fiOut, nC * FIELD_CELL_BYTES))
+        return c->lastStatus;
+    const FieldOutDev o = fields_out(c, nC);
+    if (askOwner) {
+        HIPCK(hipMemsetAsync(o.own.clumps, 0, nC * 4, c->stream));
+        HIPCK(hipMemsetAsync(o.own.mass, 0, nC * 11 * 8, c->stream));
+    }
+    if (askContact) {
+        HIPCK(hipMemsetAsync(o.side.sides, 0, nC * 4, c->stream));
+        HIPCK(hipMemsetAsync(o.side.virial, 0, nC * 9 * 8, c->stream));
+    }
+    if (!nO)
+        return DEME_OK;
+    const unsigned gridO = grid_for(nO, FIELDS_BLOCK_ROWS), gridS = grid_for(std::max<size_t>(2 * n, 1), FIELDS_BLOCK_ROWS);
+    if (ensure(c, c->fiCellOf, nO * 4) ||
+        ensure(c, c->fiPartial, std::max((size_t)gridO * 2 * sizeof(FieldOwnerPartial), (size_t)gridS * 2 * sizeof(FieldSidePartial))))
+        return c->lastStatus;
+    for (int k = 0; k < 2; k++)
+        if (ensure(c, c->fiOwnKey[k], nO * 4) || ensure(c, c->fiOwnVal[k], nO * 4) ||
+            (n && (ensure(c, c->fiSideKey[k], 2 * n * 4) || ensure(c, c->fiSideVal[k], 2 * n * 4))))
+            return c->lastStatus;
+    QueryTables t{};
+    t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
+    t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
+    {
+        ScopedTimer tm(c, "fields_cells", true);
+        FieldCellArgs a{};
+        a.nSlots = (uint32_t)nO, a.nClumps = c->nOwnerClumps, a.nCells = (uint32_t)nC, a.owners = c->owners.as<OwnerRec>();
+        for (int k = 0; k < 3; k++)
+            a.g.origin[k] = g->origin[k], a.g.cell[k] = g->cell[k], a.g.n[k] = g->n[k];
+        a.cellOf = c->fiCellOf.as<uint32_t>(), a.key = c->fiOwnKey[0].as<uint32_t>(), a.slot = c->fiOwnVal[0].as<uint32_t>();
+        hipLaunchKernelGGL(k_field_cells, dim3(grid_for(nO)), dim3(256), 0, c->stream, c->dp, a);
+        if (n) {
+            FieldSideSelectArgs s{};
+            s.n = (uint32_t)n, s.nSlots = (uint32_t)nO, s.nCells = (uint32_t)nC, s.keys = c->keysSorted[c->keysCur].as<uint64_t>(), s.t = t;
+            s.cellOf = c->fiCellOf.as<uint32_t>(), s.force = c->rec[0].as<float>(), s.thr2 = (double)thr * (double)thr;
+            s.key = c->fiSideKey[0].as<uint32_t>(), s.val = c->fiSideVal[0].as<uint32_t>();
+            hipLaunchKernelGGL(k_field_side_select, dim3(grid_for(n)), dim3(256), 0, c->stream, s);
+        }
+    }
+    // (the key nCells of the uncounted entries takes part: one value more than the cells)
+    const unsigned bits = bits_for((uint64_t)nC + 1, 32);
+    {
+        ScopedTimer tm(c, "fields_sort", true);
+        if (askOwner)
+            if (int rc = with_temp(c, c->fiTmp, [&](void* tmp, size_t& bytes) {
+                    return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->fiOwnKey[0].as<uint32_t>(), c->fiOwnKey[1].as<uint32_t>(),
+                                                                  c->fiOwnVal[0].as<uint32_t>(), c->fiOwnVal[1].as<uint32_t>(), nO, nO, 0, bits,
+                                                                  DEME_SORT_OWN_FROM_RECORDS, c->stream);
+                }))
+                return rc;
+        if (n)
+            if (int rc = with_temp(c, c->fiTmp, [&](void* tmp, size_t& bytes) {
+                    return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->fiSideKey[0].as<uint32_t>(), c->fiSideKey[1].as<uint32_t>(),
+                                                                  c->fiSideVal[0].as<uint32_t>(), c->fiSideVal[1].as<uint32_t>(), 2 * n, 2 * n, 0,
+                                                                  bits, DEME_SORT_OWN_FROM_RECORDS, c->stream);
+                }))
+                return rc;
+    }
+    ScopedTimer tm(c, "fields_sums", true);
+    if (askOwner) {
+        hipLaunchKernelGGL(k_field_owner_sums, dim3(gridO), dim3(256), 0, c->stream, (uint32_t)nO, (uint32_t)nC, c->fiOwnKey[1].as<uint32_t>(),
+                           c->fiOwnVal[1].as<uint32_t>(), c->owners.as<OwnerRec>(), c->massProps.as<float4>(),
+                           c->haveVolumes ? c->volumes.as<float>() : (const float*)nullptr, o.own, c->fiPartial.as<FieldOwnerPartial>());
+        hipLaunchKernelGGL(k_field_owner_final, dim3(1), dim3(256), 0, c->stream, 2u * gridO, (uint32_t)nC, c->fiPartial.as<FieldOwnerPartial>(),
+                           o.own);
+    }
+    if (n) {
+        FieldSideSumArgs s{};
+        s.n = (uint32_t)(2 * n), s.nCells = (uint32_t)nC, s.nSlots = (uint32_t)nO;
+        s.keys = c->fiSideKey[1].as<uint32_t>(), s.vals = c->fiSideVal[1].as<uint32_t>(), s.list = c->keysSorted[c->keysCur].as<uint64_t>();
+        s.t = t, s.owners = c->owners.as<OwnerRec>();
+        s.force = c->rec[0].as<float>(), s.cpA = c->rec[2].as<float>(), s.cpB = c->rec[3].as<float>();
+        s.out = o.side, s.partial = c->fiPartial.as<FieldSidePartial>();
+        hipLaunchKernelGGL(k_field_side_sums, dim3(gridS), dim3(256), 0, c->stream, s);
+        hipLaunchKernelGGL(k_field_side_final, dim3(1), dim3(256), 0, c->stream, 2u * gridS, (uint32_t)nC, c->fiPartial.as<FieldSidePartial>(),
+                           o.side);
+    }
+    HIPCK(hipGetLastError());
+    return DEME_OK;
+}
+// the asked columns on the host, before they are handed to the caller
+struct FieldHost {
+    std::vector<uint32_t> clumps, sides;
+    std::vector<double> mass, volume, momentum, kinetic, virial;
+    uint64_t bytes = 0;  // of the asked columns
+    FieldHost(const DemeFieldColumns* a, size_t nC)
+        : clumps(a->clumps ? nC : 0), sides(a->sides ? nC : 0), mass(a->mass ? nC : 0), volume(a->volume ? nC : 0),
+          momentum(a->momentum ? 3 * nC : 0), kinetic(a->kinetic ? 6 * nC : 0), virial(a->virial ? 9 * nC : 0) {
+        bytes = 4 * (uint64_t)(clumps.size() + sides.size()) + 8 * (uint64_t)(mass.size() + volume.size() + momentum.size() + kinetic.size() + virial.size());
+    }
+    void add(const FieldHost& h) {
+        auto sum = [](auto& a, const auto& b) {
+            for (size_t i = 0; i < a.size(); i++)
+                a[i] += b[i];
+        };
+        sum(clumps, h.clumps), sum(sides, h.sides), sum(mass, h.mass), sum(volume, h.volume), sum(momentum, h.momentum), sum(kinetic, h.kinetic),
+            sum(virial, h.virial);
+    }
+    void hand_over(const DemeFieldColumns* a) const {
+        auto copy = [](auto* dst, const auto& v) {
+            if (dst && !v.empty())
+                memcpy(dst, v.data(), v.size() * sizeof v[0]);
+        };
+        copy(a->clumps, clumps), copy(a->sides, sides), copy(a->mass, mass), copy(a->volume, volume), copy(a->momentum, momentum),
+            copy(a->kinetic, kinetic), copy(a->virial, virial);
+    }
+};
+// the asked columns of the sums fields_launch left, to h; waits for the stream
+int fields_fetch(deme_ctx* c, size_t nC, FieldHost& h) {
+    const FieldOutDev o = fields_out(c, nC);
+    auto get = [&](auto& v, const void* src) -> hipError_t {
+        return v.empty() ? hipSuccess : hipMemcpyAsync(v.data(), src, v.size() * sizeof v[0], hipMemcpyDeviceToHost, c->stream);
+    };
+    HIPCK(get(h.clumps, o.own.clumps));
+    HIPCK(get(h.sides, o.side.sides));
+    HIPCK(get(h.mass, o.own.mass));
+    HIPCK(get(h.volume, o.own.volume));
+    HIPCK(get(h.momentum, o.own.momentum));
+    HIPCK(get(h.kinetic, o.own.kinetic));
+    HIPCK(get(h.virial, o.side.virial));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+}  // namespace
+
+unsigned deme_fields_block_rows(void) { return FIELDS_BLOCK_ROWS; }
+
+int deme_inspect_fields(deme_ctx* c, const DemeFieldGrid* grid, float thr, const DemeFieldColumns* out) {
+    if (int rc = check_ready(c))
+        return rc;
+    char msg[320];
+    if (int rc = fields_args_refused(msg, "deme_inspect_fields", grid, thr, out))
+        return fail(c, rc, "%s", msg);
+    if (int rc = fields_ctx_refused(c, out))
+        return rc;
+    if (int rc = fields_launch(c, grid, thr, fields_ask_owner(out), fields_ask_contact(out)))
+        return rc;
+    const size_t nC = (size_t)grid->n[0] * grid->n[1] * grid->n[2];
+    FieldHost h(out, nC);  // (the caller's arrays are written once the call cannot fail any more)
+    if (int rc = fields_fetch(c, nC, h))
+        return rc;
+    c->qHostBytes += h.bytes;
+    h.hand_over(out);
     return DEME_OK;
 }
 

@@ -1608,7 +1608,12 @@ class DEMSolver {
     std::shared_ptr<class DEMTracker> Track(const std::shared_ptr<DEMClumpBatch>& batch);
     std::shared_ptr<class DEMTracker> Track(const std::shared_ptr<DEMExternObj>& obj);
     std::shared_ptr<class DEMTracker> Track(const std::shared_ptr<DEMMeshConnected>& mesh);
+    /// Not in the reference: per-cell fields on a regular grid of nx x ny x nz cells of edges cellSize whose cell (0, 0, 0) has its
+    /// lower corner at origin (world frame) -- solid fraction, mean velocity, granular temperature, kinetic and contact stress,
+    /// coordination -- summed on the device (deme_inspect_fields).  See DEMFieldInspector.
+    std::shared_ptr<class DEMFieldInspector> CreateFieldInspector(float3 origin, float3 cellSize, unsigned nx, unsigned ny, unsigned nz);
     friend class DEMInspector;
+    friend class DEMFieldInspector;
     friend class DEMTracker;
 
     // ---- output (API.h:1096-1122, 1318-1324); formats of dT.cpp:1254-1405, 1491-1618, 1620-1848
@@ -2478,6 +2483,7 @@ class DEMSolver {
     unsigned int m_out_content = QUAT | ABSV;                                      // API.h:1418
     unsigned int m_cnt_out_content = OWNER | GEO_ID | FORCE | CNT_POINT | CNT_WILDCARD;  // API.h:1422-1424
     bool m_mesh_face_loads = false;  // EnableMeshFaceLoadOutput
+    bool m_all_volumes = false;      // every clump template declared a volume (DEMFieldInspector asks the volume column then)
     struct Keep {  // scene arrays the writers need after Initialize
         std::vector<uint32_t> sphOwner, objOwner, triOwner;
         std::vector<uint16_t> sphComp, inert;
@@ -2840,6 +2846,7 @@ class DEMSolver {
             mass.push_back(ts[i]->mass), moix.push_back(ts[i]->MOI.x), moiy.push_back(ts[i]->MOI.y), moiz.push_back(ts[i]->MOI.z);
             volumes.push_back(ts[i]->volume);
         }
+        m_all_volumes = !volumes.empty() && std::all_of(volumes.begin(), volumes.end(), [](float v) { return v != 0.f; });
         if (Radii.size() > 65535)
             throw std::runtime_error("more than 65535 clump components");
         double bin = m_bin_size > 0 ? m_bin_size : (double)(m_bin_multiple * smallest);  // a float product, like the reference's
@@ -3309,6 +3316,174 @@ class DEMInspector {
     int m_region = -1;
 };
 
+/// Not in the reference: fields on a regular grid, cell by cell (deme_inspect_fields / deme_multi_inspect_fields: the sums are made
+/// on the device, only the columns of the grid come to the host).  A clump belongs to the cell its centre of mass lies in -- a cell's
+/// lower faces belong to it, its upper faces to the next cell -- and a contact side to the cell of its clump.  Update() makes the
+/// one library call; the getters derive their fields from what it brought, with V the volume of a cell.  Cell (ix, iy, iz) is entry
+/// ix + nx * (iy + ny * iz) of every array.  An empty cell gives zeros, never NaN.
+///   GetClumpCounts()          clumps in the cell
+///   GetMass()                 their mass
+///   GetSolidFraction()        their declared volume / V; needs every clump template to declare a volume (SetVolume), zeros otherwise
+///   GetMeanVelocity()         momentum / mass
+///   GetGranularTemperature()  trace(K - p (x) p / mass) / (3 mass), K = sum m v (x) v
+///   GetKineticStress()        -(K - p (x) p / mass) / V: xx, yy, zz, xy, xz, yz
+///   GetContactStress()        sum of arm (x) force over the force-carrying contact sides of the cell's clumps / V: 9 values,
+///                             row-major (Love-Weber; compression negative)
+///   GetCoordination()         force-carrying contact sides per clump
+/// The last two need the contact output content to include forces and contact points (the default), like "clump_virial".
+class DEMFieldInspector {
+  public:
+    DEMFieldInspector(DEMSolver* sys, float3 origin, float3 cellSize, unsigned nx, unsigned ny, unsigned nz) : m_sys(sys) {
+        m_grid.origin[0] = origin.x, m_grid.origin[1] = origin.y, m_grid.origin[2] = origin.z;
+        m_grid.cell[0] = cellSize.x, m_grid.cell[1] = cellSize.y, m_grid.cell[2] = cellSize.z;
+        m_grid.n[0] = nx, m_grid.n[1] = ny, m_grid.n[2] = nz;
+    }
+    /// the sums of the current state and contact list, cell by cell: one call into the library
+    void Update() {
+        const uint64_t n = (uint64_t)m_grid.n[0] * m_grid.n[1] * m_grid.n[2];
+        const size_t nC = n <= DEME_FIELDS_MAX_CELLS ? (size_t)n : 0;  // (a grid the library refuses: nothing is allocated for it)
+        m_contacts = (m_sys->m_cnt_out_content & FORCE) && (m_sys->m_cnt_out_content & CNT_POINT);
+        m_volumes = m_sys->m_all_volumes;
+        std::vector<uint32_t> clumps(nC), sides(m_contacts ? nC : 0);
+        std::vector<double> mass(nC), volume(m_volumes ? nC : 0), momentum(3 * nC), kinetic(6 * nC), virial(m_contacts ? 9 * nC : 0);
+        DemeFieldColumns cols{};
+        cols.clumps = clumps.data(), cols.mass = mass.data(), cols.momentum = momentum.data(), cols.kinetic = kinetic.data();
+        cols.volume = m_volumes ? volume.data() : nullptr;
+        cols.sides = m_contacts ? sides.data() : nullptr, cols.virial = m_contacts ? virial.data() : nullptr;
+        if (!nC)  // (named, never written: the grid is refused before any column is looked at)
+            cols.clumps = reinterpret_cast<uint32_t*>(&m_grid);
+        if (m_sys->decomposed())
+            m_sys->mcheck(deme_multi_inspect_fields(m_sys->m_multi, &m_grid, DEME_TINY_FLOAT_HOST, &cols));
+        else
+            m_sys->check(deme_inspect_fields(m_sys->m_ctx, &m_grid, DEME_TINY_FLOAT_HOST, &cols));
+        m_clumps.swap(clumps), m_sides.swap(sides), m_mass.swap(mass), m_volume.swap(volume), m_momentum.swap(momentum);
+        m_kinetic.swap(kinetic), m_virial.swap(virial);
+        m_updated = true;
+    }
+    size_t GetNumCells() const { return (size_t)m_grid.n[0] * m_grid.n[1] * m_grid.n[2]; }
+    double GetCellVolume() const { return m_grid.cell[0] * m_grid.cell[1] * m_grid.cell[2]; }
+    const std::vector<uint32_t>& GetClumpCounts() const { return updated(), m_clumps; }
+    const std::vector<double>& GetMass() const { return updated(), m_mass; }
+    /// the sums as the library brought them: momentum (3 a cell), sum m v (x) v (6), contact sides (1), arm (x) force (9)
+    const std::vector<double>& GetMomentum() const { return updated(), m_momentum; }
+    const std::vector<double>& GetKineticSum() const { return updated(), m_kinetic; }
+    const std::vector<uint32_t>& GetContactSideCounts() const { return with_contacts(), m_sides; }
+    const std::vector<double>& GetVirial() const { return with_contacts(), m_virial; }
+    std::vector<double> GetSolidFraction() const {
+        updated();
+        std::vector<double> f(m_clumps.size(), 0.0);
+        for (size_t c = 0; c < m_volume.size(); c++)
+            f[c] = m_volume[c] / GetCellVolume();
+        return f;
+    }
+    std::vector<double> GetMeanVelocity() const {  // 3 a cell
+        updated();
+        std::vector<double> v(m_momentum.size(), 0.0);
+        for (size_t c = 0; c < m_mass.size(); c++)
+            if (m_mass[c] > 0.0)
+                for (int k = 0; k < 3; k++)
+                    v[3 * c + k] = m_momentum[3 * c + k] / m_mass[c];
+        return v;
+    }
+    std::vector<double> GetGranularTemperature() const {
+        const std::vector<double> f = fluctuation();
+        std::vector<double> t(m_mass.size(), 0.0);
+        for (size_t c = 0; c < m_mass.size(); c++)
+            if (m_mass[c] > 0.0)
+                t[c] = (f[6 * c] + f[6 * c + 1] + f[6 * c + 2]) / (3.0 * m_mass[c]);
+        return t;
+    }
+    std::vector<double> GetKineticStress() const {  // 6 a cell: xx, yy, zz, xy, xz, yz
+        std::vector<double> s = fluctuation();
+        for (double& v : s)
+            v = v == 0.0 ? 0.0 : -v / GetCellVolume();
+        return s;
+    }
+    std::vector<double> GetContactStress() const {  // 9 a cell, row-major
+        with_contacts();
+        std::vector<double> s(m_virial);
+        for (double& v : s)
+            v /= GetCellVolume();
+        return s;
+    }
+    std::vector<double> GetCoordination() const {
+        with_contacts();
+        std::vector<double> z(m_clumps.size(), 0.0);
+        for (size_t c = 0; c < z.size(); c++)
+            if (m_clumps[c])
+                z[c] = (double)m_sides[c] / (double)m_clumps[c];
+        return z;
+    }
+    /// a legacy-VTK STRUCTURED_POINTS file of the grid with the fields of the last Update() as CELL_DATA
+    void WriteVtk(const std::string& outfilename) const {
+        updated();
+        std::ostringstream o;
+        o.precision(9);
+        o << "# vtk DataFile Version 2.0\nDEM fields on a grid\nASCII\nDATASET STRUCTURED_POINTS\n";
+        o << "DIMENSIONS " << m_grid.n[0] + 1 << " " << m_grid.n[1] + 1 << " " << m_grid.n[2] + 1 << "\n";
+        o << "ORIGIN " << m_grid.origin[0] << " " << m_grid.origin[1] << " " << m_grid.origin[2] << "\n";
+        o << "SPACING " << m_grid.cell[0] << " " << m_grid.cell[1] << " " << m_grid.cell[2] << "\n";
+        const size_t nC = m_clumps.size();
+        o << "\nCELL_DATA " << nC << "\n";
+        auto scalars = [&](const char* name, const char* type, const auto& v) {
+            o << "SCALARS " << name << " " << type << " 1\nLOOKUP_TABLE default\n";
+            for (size_t c = 0; c < nC; c++)
+                o << v[c] << "\n";
+        };
+        auto tensors = [&](const char* name, const std::vector<double>& v, bool symmetric) {  // 6 (xx yy zz xy xz yz) or 9 a cell
+            static const int sym[9] = {0, 3, 4, 3, 1, 5, 4, 5, 2};
+            o << "TENSORS " << name << " double\n";
+            for (size_t c = 0; c < nC; c++) {
+                for (int k = 0; k < 9; k++)
+                    o << (symmetric ? v[6 * c + sym[k]] : v[9 * c + k]) << (k % 3 == 2 ? "\n" : " ");
+                o << "\n";
+            }
+        };
+        scalars("clumps", "int", m_clumps);
+        scalars("mass", "double", m_mass);
+        if (m_volumes)
+            scalars("solid_fraction", "double", GetSolidFraction());
+        const std::vector<double> vel = GetMeanVelocity();
+        o << "VECTORS mean_velocity double\n";
+        for (size_t c = 0; c < nC; c++)
+            o << vel[3 * c] << " " << vel[3 * c + 1] << " " << vel[3 * c + 2] << "\n";
+        scalars("granular_temperature", "double", GetGranularTemperature());
+        tensors("kinetic_stress", GetKineticStress(), true);
+        if (m_contacts) {
+            scalars("coordination", "double", GetCoordination());
+            tensors("contact_stress", GetContactStress(), false);
+        }
+        m_sys->flush(outfilename, o);
+    }
+
+  private:
+    // K - p (x) p / mass per cell (xx, yy, zz, xy, xz, yz); zeros for an empty cell
+    std::vector<double> fluctuation() const {
+        updated();
+        static const int I[6] = {0, 1, 2, 0, 0, 1}, J[6] = {0, 1, 2, 1, 2, 2};
+        std::vector<double> f(m_kinetic.size(), 0.0);
+        for (size_t c = 0; c < m_mass.size(); c++)
+            if (m_mass[c] > 0.0)
+                for (int k = 0; k < 6; k++)
+                    f[6 * c + k] = m_kinetic[6 * c + k] - m_momentum[3 * c + I[k]] * m_momentum[3 * c + J[k]] / m_mass[c];
+        return f;
+    }
+    void updated() const {
+        if (!m_updated)
+            throw std::runtime_error("DEMFieldInspector: call Update() first");
+    }
+    void with_contacts() const {
+        updated();
+        if (!m_contacts)  // (the sentence the library gives "clump_virial" then)
+            throw std::runtime_error("contact recording is off (deme_set_record_contacts)");
+    }
+    DEMSolver* m_sys;
+    DemeFieldGrid m_grid{};
+    bool m_updated = false, m_contacts = false, m_volumes = false;
+    std::vector<uint32_t> m_clumps, m_sides;
+    std::vector<double> m_mass, m_volume, m_momentum, m_kinetic, m_virial;
+};
+
 /// Access to the state of the owners of one loaded object (a batch of clumps, an analytical object, a mesh):
 /// getters read the current device state, setters write it back (DEMTracker, AuxClasses.h:93-420).
 class DEMTracker {
@@ -3617,6 +3792,9 @@ class DEMTracker {
     }
 };
 
+inline std::shared_ptr<DEMFieldInspector> DEMSolver::CreateFieldInspector(float3 origin, float3 cellSize, unsigned nx, unsigned ny, unsigned nz) {
+    return std::make_shared<DEMFieldInspector>(this, origin, cellSize, nx, ny, nz);
+}
 inline std::shared_ptr<DEMInspector> DEMSolver::CreateInspector(const std::string& quantity) {
     return std::make_shared<DEMInspector>(this, quantity);
 }

@@ -537,10 +537,64 @@ int deme_inspect_contact_counts(deme_ctx* ctx, int regionId, float forceThreshol
 int deme_inspect_tri_loads(deme_ctx* ctx, float forceThreshold, uint32_t firstTri, uint32_t nTris, double* force /* 3 per triangle, or NULL */,
                            uint32_t* contacts /* 1 per triangle, or NULL */);
 unsigned deme_tri_loads_block_rows(void);
+/* Field inspector (no counterpart in the reference): per-cell sums on a regular grid -- what solid fraction, mean velocity, granular
+ * temperature, contact stress and coordination are derived from, cell by cell -- summed on the device.
+ *   GRID.  nCells = n[0] * n[1] * n[2]; the id of cell (ix, iy, iz) is ix + n[0] * (iy + n[1] * iz); every per-cell array is in that
+ *   order.
+ *   CELL OF AN OWNER.  P_k is the owner's centre of mass in the world frame in fp64, decoded as the run-time compiled kernels decode
+ *   it (decode_pos(...)_k + (double)LBF_k).  u_k = (P_k - origin[k]) / cell[k] in fp64, no contraction.  The owner is inside iff
+ *   u_k >= 0.0 && u_k < (double)n[k] on all three axes (a NaN is outside); i_k = (uint32_t)u_k.  So a cell's lower face belongs to
+ *   it, its upper face to the next cell, and the grid's upper faces to nobody.
+ *   A COUNTED OWNER is an own clump owner -- its caller id is < nOwnerClumps, the test deme_inspect_contacts makes -- that is no
+ *   ghost copy and lies inside the grid.  Fixed and prescribed families count like any clump; mesh and analytical owners never do.
+ *   OWNER COLUMNS of a cell: sums over its counted owners, every term converted to fp64 first and computed as written:
+ *     clumps    uint32_t   1
+ *     mass      double     (double)m, m the mass of the owner's mass-property entry
+ *     volume    double     (double)volume of that entry, as declared with deme_upload_volumes
+ *     momentum  3 doubles  (double)m * (double)v_k
+ *     kinetic   6 doubles  xx, yy, zz, xy, xz, yz: ((double)m * (double)v_i) * (double)v_j
+ *   CONTACT COLUMNS of a cell.  A row is COUNTED by the test of deme_inspect_contacts: record 0, the squared fp32 components summed
+ *   in fp64 and compared >= (double)forceThreshold^2.  A SIDE of a counted row belongs to the cell of its owner, if that owner is a
+ *   counted owner -- the cell of the owner's centre of mass, not of the contact point: the per-particle Love-Weber average
+ *   sigma = (1 / V) sum_p sum_c r (x) f.
+ *     sides     uint32_t   1 per counted side
+ *     virial    9 doubles  row-major, the r_i * f_j deme_inspect_contacts adds for the side: r = R(q) cp with the stored quaternion;
+ *                          side A carries +f and cpA, side B -f and cpB
+ *   DERIVED, by the caller, with V = cell[0] * cell[1] * cell[2]: solid fraction volume / V; mean velocity momentum / mass; kinetic
+ *   stress -(kinetic - p (x) p / mass) / V; granular temperature trace(kinetic - p (x) p / mass) / (3 mass); contact stress
+ *   virial / V; coordination sides / clumps.
+ *   ORDER.  Within a cell the terms are added in a fixed order -- owner slots ascending; sides in list order, A before B -- down a
+ *   tree of fixed shape: two calls on one state give the same bits.  No floating-point atomics; no workgroup waits for another.
+ * Any column may be NULL; only the asked columns come to the host: 4, 8, 24, 48 or 72 bytes per cell, added to
+ * deme_query_host_bytes.  The caller's arrays are written once the call can no longer fail.  Owner columns alone need no contact
+ * records.  Read-only: the list, the prescriptions and the step's buffers stay as they are.
+ * Refused with DEME_ERR_INVALID and nothing written, in this order: a null grid or null columns; an origin or cell edge that is not
+ * finite; a cell edge <= 0; an n[k] == 0; nCells > 2^21; every column NULL; a threshold that is negative or not finite; volume asked
+ * without uploaded volumes; sides or virial asked with recording off or a seeded list (as deme_download_contact_records); a list of
+ * 2^31 rows or more.
+ * deme_fields_block_rows: the sorted entries one workgroup of the segmented sums takes. */
+typedef struct DemeFieldGrid {
+    double origin[3]; /* world frame: lower corner of cell (0, 0, 0) */
+    double cell[3];   /* edge lengths */
+    uint32_t n[3];    /* cells along x, y, z */
+} DemeFieldGrid;
+typedef struct DemeFieldColumns { /* any may be NULL; nCells entries (times 3 / 6 / 9) each */
+    uint32_t* clumps;
+    double* mass;
+    double* volume;
+    double* momentum;
+    double* kinetic;
+    uint32_t* sides;
+    double* virial;
+} DemeFieldColumns;
+#define DEME_FIELDS_MAX_CELLS (1u << 21)
+int deme_inspect_fields(deme_ctx* ctx, const DemeFieldGrid* grid, float forceThreshold, const DemeFieldColumns* out);
+unsigned deme_fields_block_rows(void);
 
 /* timing of the kernels this library launched (HIP events on the context stream);
- * names: "calc_forces", "integrate", "detect", and the passes of deme_inspect_tri_loads "tri_loads_select", "tri_loads_sort",
- * "tri_loads_sums"; returns avg ms per launch since last reset */
+ * names: "calc_forces", "integrate", "detect", the passes of deme_inspect_tri_loads "tri_loads_select", "tri_loads_sort",
+ * "tri_loads_sums", and those of deme_inspect_fields "fields_cells" (both select kernels), "fields_sort", "fields_sums"; returns avg
+ * ms per launch since last reset */
 int deme_kernel_time_ms(deme_ctx* ctx, const char* name, double* avg_ms, uint64_t* launches);
 int deme_kernel_time_reset(deme_ctx* ctx);
 /* enable = 0: off; n > 0: every n-th launch of each timed kernel is bracketed with events (an event pair costs ~3 us of
@@ -795,6 +849,12 @@ int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, flo
  * (deme_halo_group_set_cross_contacts) would be refused too; no call of this interface puts a deme_multi into that mode today, so
  * that refusal cannot be met yet.  Bytes, added to deme_multi_query_host_bytes: 24 + 4 per asked triangle and slab. */
 int deme_multi_inspect_tri_loads(deme_multi* m, float forceThreshold, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts);
+/* deme_inspect_fields for a decomposed run.  Every slab sums over its OWN clumps on its device (a clump is an own clump of one slab
+ * only, ghost copies never count); all slabs' passes are enqueued first, then the host takes the asked columns slab by slab and adds
+ * them in slab order: the asked columns' bytes per cell and slab, added to deme_multi_query_host_bytes.  The refusals of
+ * deme_inspect_fields; when a contact column is asked also those of deme_multi_inspect_contacts (a run that evaluates every cross-cut
+ * contact once; a slab whose list is a seed, as on the step after a migration). */
+int deme_multi_inspect_fields(deme_multi* m, const DemeFieldGrid* grid, float forceThreshold, const DemeFieldColumns* out);
 /* deme_add_owner_acc by GLOBAL owner id: a clump's entry goes to the slab that owns it, a replicated owner's to every slab */
 int deme_multi_add_owner_acc(deme_multi* m, uint32_t owner, uint32_t n, const float* acc, const float* angAcc);
 /* the visible HIP devices (0 and DEME_OK where there is none: what the constructors check ids against) */
