@@ -118,6 +118,20 @@ class DemeFieldColumns(C.Structure):
     _fields_ = [(name, _P) for name in ("clumps", "mass", "volume", "momentum", "kinetic", "sides", "virial")]
 
 
+class DemeClusterSummary(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("vertices", "edges", "clusters", "singletons", "largestSize", "largestLabel")]
+
+
+# the columns of the cluster table of deme_inspect_clusters: dtype and entries per row
+CLUSTER_COLUMN_SHAPES = {"label": (np.uint32, 1), "size": (np.uint32, 1), "mass": (np.float64, 1), "moment": (np.float64, 3)}
+CLUSTER_COLUMNS = tuple(CLUSTER_COLUMN_SHAPES)
+CLUSTER_NONE = 0xFFFFFFFF  # the label of an owner that is no vertex
+
+
+class DemeClusterColumns(C.Structure):
+    _fields_ = [(name, _P) for name in CLUSTER_COLUMNS]
+
+
 class DemeAdaptive(C.Structure):
     """include/deme_hip.h DemeAdaptive; the defaults are the reference's (DEM/Structs.h:204-216)"""
     _fields_ = [("autoBinSize", C.c_uint32), ("binObserveSteps", C.c_uint32), ("binMaxRate", C.c_float), ("binAcc", C.c_float),
@@ -239,6 +253,11 @@ def load_library():
         "deme_multi_inspect_tri_loads": [_P, C.c_float, C.c_uint32, C.c_uint32, _P, _P],
         "deme_inspect_fields": [_P, C.POINTER(DemeFieldGrid), C.c_float, C.POINTER(DemeFieldColumns)],
         "deme_multi_inspect_fields": [_P, C.POINTER(DemeFieldGrid), C.c_float, C.POINTER(DemeFieldColumns)],
+        "deme_inspect_clusters": [_P, C.c_float, C.POINTER(DemeClusterSummary), _P, C.c_size_t, C.POINTER(DemeClusterColumns), C.c_size_t,
+                                  C.POINTER(C.c_size_t)],
+        "deme_multi_inspect_clusters": [_P, C.c_float, C.POINTER(DemeClusterSummary), _P, C.c_size_t, C.POINTER(DemeClusterColumns),
+                                        C.c_size_t, C.POINTER(C.c_size_t)],
+        "deme_clusters_link_retries": [_P, C.POINTER(C.c_uint64)],
         "deme_query_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_scatter_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
@@ -753,6 +772,10 @@ class Multi:
         """deme_multi_inspect_fields: Context.inspect_fields of every slab's own clumps, the slabs' columns added in slab order"""
         return _inspect_fields(self, self.lib.deme_multi_inspect_fields, "deme_multi_inspect_fields", origin, cell, n, columns, force_threshold)
 
+    def inspect_clusters(self, force_threshold=1e-12, summary=True, labels=True, table=True):
+        """deme_multi_inspect_clusters: Context.inspect_clusters in GLOBAL owner ids; the slabs' local trees are united on the host"""
+        return _inspect_clusters(self, self.lib.deme_multi_inspect_clusters, "deme_multi_inspect_clusters", force_threshold, summary, labels, table)
+
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied from the devices to the host since the run was created"""
         v = C.c_uint64(0)
@@ -871,6 +894,28 @@ def _inspect_fields(self, fn, name, origin, cell, n, columns, force_threshold):
         out[k] = np.zeros(rows if width == 1 else (rows, width), dtype)
         setattr(cols, k, out[k].ctypes.data if rows else C.addressof(grid))  # (named, never written: the grid is refused first)
     self._ck(fn(self.h, C.byref(grid), float(force_threshold), C.byref(cols)), name)
+    return out
+
+
+def _inspect_clusters(self, fn, name, force_threshold, summary, labels, table):
+    """the call both Context.inspect_clusters and Multi.inspect_clusters make.  One call: a table has at most one row per owner, so
+    arrays of that many rows always do; only the rows there are come to the host."""
+    out = {}
+    n_owners = int(self.n_owners)
+    summ = DemeClusterSummary() if summary else None
+    lab = np.full(n_owners, CLUSTER_NONE, np.uint32) if labels else None
+    rows, cols = C.c_size_t(0), DemeClusterColumns()
+    if table:
+        for k, (dtype, width) in CLUSTER_COLUMN_SHAPES.items():
+            out[k] = np.zeros(max(n_owners, 1) if width == 1 else (max(n_owners, 1), width), dtype)
+            setattr(cols, k, out[k].ctypes.data)
+    self._ck(fn(self.h, float(force_threshold), C.byref(summ) if summary else None, lab.ctypes.data if labels else None, n_owners,
+                C.byref(cols) if table else None, n_owners, C.byref(rows) if table else None), name)
+    out = {k: v[:int(rows.value)].copy() for k, v in out.items()}
+    if summary:
+        out["summary"] = {k: int(getattr(summ, k)) for k, _ in DemeClusterSummary._fields_}
+    if labels:
+        out["labels"] = lab
     return out
 
 
@@ -1306,6 +1351,21 @@ class Context:
         that number: clumps, sides uint32 (nCells,); mass, volume float64 (nCells,); momentum (nCells, 3); kinetic (nCells, 6: xx, yy,
         zz, xy, xz, yz); virial (nCells, 9: row-major).  The contact columns (sides, virial) need contact recording."""
         return _inspect_fields(self, self.lib.deme_inspect_fields, "deme_inspect_fields", origin, cell, n, columns, force_threshold)
+
+    def inspect_clusters(self, force_threshold=1e-12, summary=True, labels=True, table=True):
+        """deme_inspect_clusters: the connected components of the contact network -- vertices the own clumps, edges the counted
+        sphere-sphere rows between two of them -- labelled on the device.  A dict of what was asked: summary (a dict of vertices,
+        edges, clusters, singletons, largestSize, largestLabel); labels (uint32 per owner in the caller's numbering: the smallest
+        owner id of the owner's component, CLUSTER_NONE for an owner that is no clump); and the table's columns, one row per cluster,
+        labels ascending: label, size uint32 (n,), mass float64 (n,), moment float64 (n, 3) -- the centre is moment / mass."""
+        self.refresh_sizes()
+        return _inspect_clusters(self, self.lib.deme_inspect_clusters, "deme_inspect_clusters", force_threshold, summary, labels, table)
+
+    def clusters_link_retries(self):
+        """compare-and-swaps the link pass of the last inspect_clusters lost to another thread (a measurement)"""
+        v = C.c_uint64(0)
+        self._ck(self.lib.deme_clusters_link_retries(self.h, C.byref(v)), "deme_clusters_link_retries")
+        return int(v.value)
 
     def query_host_bytes(self):
         """bytes owner_contacts / owner_state calls have copied to the host since the context was created (count read-backs, hit

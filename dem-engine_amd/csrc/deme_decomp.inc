@@ -1875,6 +1875,153 @@ int deme_multi_inspect_fields(deme_multi* m, const DemeFieldGrid* grid, float th
     return DEME_OK;
 }
 
+// ---- connected components of the contact network of a decomposed run (deme_clusters.h) -------------------------------------------------
+// A slab sees its own clumps and the ghost copies beside them, so it can link what touches inside its reach and nothing more: a
+// cluster that crosses a cut is two (or more) local trees, each holding the ghost copy of the clump on the other side.  Every slab
+// hands down, per local owner, the pair (global id, global id of its local root); the host unites every pair in one array
+// union-find over the global ids -- the smaller root wins, as on the device -- and the label is the root.  A slab's table counts its
+// OWN clumps only, so a clump is counted once; its rows are added into their final label in slab order, local roots ascending.
+int deme_multi_inspect_clusters(deme_multi* m, float thr, DemeClusterSummary* summary, uint32_t* labels, size_t labelCap,
+                                const DemeClusterColumns* table, size_t tableCap, size_t* nClusters) {
+    const char* who = "deme_multi_inspect_clusters";
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    const uint32_t nOG = m->plan->nOwnersGlobal;
+    char msg[320];
+    if (int rc = clusters_args_refused(msg, who, summary, labels, labelCap, nOG, table, nClusters, thr))
+        return mfail(m, rc, "%s", msg);
+    std::vector<int> regions;
+    if (int rc = multi_contact_inspect_begin(m, who, m, nullptr, thr, regions))  // (pairsOnce; the wait; the slabs' books and records)
+        return rc;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            if (r.c->haveList && r.c->nContacts >= ((uint64_t)1 << 31))
+                return mfail(m, DEME_ERR_INVALID, "%s: a slab's list has %llu rows; the rows are indexed with 32 bits", who,
+                             (unsigned long long)r.c->nContacts);
+            return DEME_OK;
+        }))
+        return rc;
+    const bool askTable = table || nClusters || summary;  // (the summary's sizes come from the merged table)
+    const ClusterAsk ask{summary != nullptr, true, askTable, askTable};
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            deme_ctx* c = r.c;
+            if (int rc = clusters_launch(c, thr, (const uint32_t*)r.s->geo.ownerGid, ask))
+                return rc;
+            if (!c->nOwners)
+                return DEME_OK;
+            if (ensure(c, c->clPairs, (size_t)c->nOwners * 8))
+                return c->lastStatus;
+            hipLaunchKernelGGL(k_cluster_pairs, dim3(grid_for(c->nOwners)), dim3(256), 0, c->stream, c->nOwners, c->clLabel.as<uint32_t>(),
+                               (const uint32_t*)r.s->geo.ownerGid, c->clPairs.as<uint2>());
+            HIPCK(hipGetLastError());
+            return DEME_OK;
+        }))
+        return rc;
+    // the forest over the global ids
+    std::vector<uint32_t> parent(nOG, 0xFFFFFFFFu);
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) {
+            parent[x] = parent[parent[x]];
+            x = parent[x];
+        }
+        return x;
+    };
+    struct SlabRows {
+        std::vector<uint32_t> rootGid;  // of every row of the slab's table
+        ClusterRows rows{true, true, true, true, 0};
+    };
+    std::vector<SlabRows> perSlab;
+    uint64_t edges = 0;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            deme_ctx* c = r.c;
+            ClusterCtl ctl{};
+            DemeClusterSummary sum{};
+            if (int rc = clusters_fetch_head(c, ask.summary, &ctl, &sum))
+                return rc;
+            m->qHostBytes += sizeof ctl + (ask.summary ? sizeof sum : 0);
+            edges += sum.edges;
+            const size_t nO = c->nOwners, rows = ask.table ? (size_t)ctl.nRows : 0;
+            std::vector<uint2> pairs(nO);
+            perSlab.emplace_back();
+            SlabRows& s = perSlab.back();
+            s.rows = ClusterRows(true, true, true, true, rows);
+            if (nO)
+                HIPCK(hipMemcpyAsync(pairs.data(), c->clPairs.p, nO * 8, hipMemcpyDeviceToHost, c->stream));
+            if (int rc = clusters_fetch_rows(c, s.rows))
+                return rc;
+            HIPCK(hipStreamSynchronize(c->stream));
+            m->qHostBytes += 8ull * nO + s.rows.bytes;
+            for (const uint2& p : pairs) {
+                if (p.x >= nOG || p.y >= nOG)  // (no vertex)
+                    continue;
+                for (uint32_t g : {p.x, p.y})
+                    if (parent[g] == 0xFFFFFFFFu)
+                        parent[g] = g;
+                const uint32_t a = find(p.x), b = find(p.y);
+                if (a != b)
+                    parent[std::max(a, b)] = std::min(a, b);
+            }
+            s.rootGid.resize(rows);
+            for (size_t k = 0; k < rows; k++) {
+                const uint32_t l = s.rows.label[k];
+                if (l >= nO || pairs[l].x >= nOG)
+                    return mfail(m, DEME_ERR_INTERNAL, "%s: a slab's table names the local root %u, which is no vertex", who, l);
+                s.rootGid[k] = pairs[l].x;
+            }
+            return DEME_OK;
+        }))
+        return rc;
+    std::vector<uint32_t> label(nOG, 0xFFFFFFFFu);
+    for (uint32_t g = 0; g < nOG; g++)
+        if (parent[g] != 0xFFFFFFFFu)
+            label[g] = find(g);
+    // the merged table, by final label
+    std::vector<uint32_t> size(askTable ? nOG : 0, 0u);
+    std::vector<double> mass(size.size(), 0.0), moment(3 * size.size(), 0.0);
+    for (const SlabRows& s : perSlab)
+        for (size_t k = 0; k < s.rootGid.size(); k++) {
+            const uint32_t l = label[s.rootGid[k]];
+            size[l] += s.rows.size[k], mass[l] += s.rows.mass[k];
+            for (int j = 0; j < 3; j++)
+                moment[3 * (size_t)l + j] += s.rows.moment[3 * k + j];
+        }
+    DemeClusterSummary sum{0, edges, 0, 0, 0, 0xFFFFFFFFull};
+    size_t rows = 0;
+    for (uint32_t g = 0; g < (uint32_t)size.size(); g++) {
+        if (!size[g])
+            continue;
+        rows++;
+        sum.vertices += size[g], sum.clusters++, sum.singletons += size[g] == 1;
+        if (size[g] > sum.largestSize)  // (labels ascending: the first of the largest size stays)
+            sum.largestSize = size[g], sum.largestLabel = g;
+    }
+    if (nClusters)
+        *nClusters = rows;
+    if (table && tableCap < rows)
+        return mfail(m, DEME_ERR_INVALID, "%s: the table has %zu rows; room for %zu was given", who, rows, tableCap);
+    if (summary)
+        *summary = sum;
+    if (labels && nOG)
+        memcpy(labels, label.data(), (size_t)nOG * 4);
+    if (table) {
+        size_t k = 0;
+        for (uint32_t g = 0; g < (uint32_t)size.size(); g++) {
+            if (!size[g])
+                continue;
+            if (table->label)
+                table->label[k] = g;
+            if (table->size)
+                table->size[k] = size[g];
+            if (table->mass)
+                table->mass[k] = mass[g];
+            if (table->moment)
+                for (int j = 0; j < 3; j++)
+                    table->moment[3 * k + j] = moment[3 * (size_t)g + j];
+            k++;
+        }
+    }
+    return DEME_OK;
+}
+
 // ---- moving the slab boundaries (load balance of a bed that drifts or piles up) --------------------------------------------------------
 // deme_halo_group_migrate keeps the boundaries where the plan put them.  deme_multi_rebalance recomputes them from the clumps'
 // CURRENT coordinates -- equal counts again, snapped to bin faces like the plan's -- and lets the same migration move the clumps that

@@ -51,6 +51,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_contact_inspect.h"
 #include "deme_tri_loads.h"
 #include "deme_fields.h"
+#include "deme_clusters.h"
 #include "deme_sort.h"
 
 using namespace deme_dev;
@@ -142,6 +143,11 @@ struct deme_ctx {
     // field inspector (deme_fields.h): the cell of every owner slot, the (cell, slot) and (cell, side) pairs before and after their
     // sorts, the sorts' own scratch, the blocks' partials, the columns of every cell; kept likewise
     DevBuf fiCellOf, fiOwnKey[2], fiOwnVal[2], fiSideKey[2], fiSideVal[2], fiTmp, fiPartial, fiOut;
+    // cluster inspector (deme_clusters.h): parent, label, size, row flag and rank per caller id, the (label, slot) pairs before and
+    // after their sort, the sort's own scratch, the integer partials with the summary behind them, the partials of the table's sums,
+    // the table, the control words, a slab's (global id, global root) pairs; kept likewise
+    DevBuf clParent, clLabel, clSize, clFlag, clRank, clKey[2], clVal[2], clTmp, clStat, clPartial, clTable, clCtl, clPairs;
+    uint32_t clRetries = 0;  // compare-and-swaps the last call's link pass lost (deme_clusters_link_retries)
     std::map<std::string, int> regionBySource;  // deme_multi_inspect_contacts: a region string compiles once per slab context
     // detection scratch
     DevBuf sphFam;  // per sphere: its owner's family word, for the sweeps (written by k_sphere_prep when masks, margins or ghosts are in play)
@@ -1759,7 +1765,8 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut, &c->tlTri[0], &c->tlTri[1], &c->tlRow[0], &c->tlRow[1],
                      &c->tlTmp, &c->tlPartial, &c->tlForce, &c->tlCount, &c->fiCellOf, &c->fiOwnKey[0], &c->fiOwnKey[1], &c->fiOwnVal[0],
                      &c->fiOwnVal[1], &c->fiSideKey[0], &c->fiSideKey[1], &c->fiSideVal[0], &c->fiSideVal[1], &c->fiTmp, &c->fiPartial,
-                     &c->fiOut};
+                     &c->fiOut, &c->clParent, &c->clLabel, &c->clSize, &c->clFlag, &c->clRank, &c->clKey[0], &c->clKey[1], &c->clVal[0],
+                     &c->clVal[1], &c->clTmp, &c->clStat, &c->clPartial, &c->clTable, &c->clCtl, &c->clPairs};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
@@ -5213,6 +5220,204 @@ int deme_inspect_fields(deme_ctx* c, const DemeFieldGrid* grid, float thr, const
         return rc;
     c->qHostBytes += h.bytes;
     h.hand_over(out);
+    return DEME_OK;
+}
+
+// ---- connected components of the contact network (deme_clusters.h) ---------------------------------------------------------------------
+namespace {
+static_assert(sizeof(DemeClusterSummary) == sizeof(ClusterStat), "DemeClusterSummary is the device's ClusterStat");
+constexpr size_t CLUSTER_ROW_BYTES = 40;  // of clTable: label, size, mass and three moments a row
+struct ClusterAsk {
+    bool summary, labels, rows, table;  // rows: the row count of the table (asked with the table, or alone)
+};
+// what deme_inspect_clusters refuses of its arguments alone, in the order it does (the text goes to msg)
+int clusters_args_refused(char (&msg)[320], const char* who, const void* summary, const void* labels, size_t labelCap, size_t nOwners,
+                          const void* table, const void* nClusters, float thr) {
+    msg[0] = 0;
+    if (!summary && !labels && !table && !nClusters)
+        snprintf(msg, sizeof msg, "%s: null output (summary, labels, table and nClusters)", who);
+    else if (labels && labelCap < nOwners)
+        snprintf(msg, sizeof msg, "%s: buffer too small: need %zu labels", who, nOwners);
+    else if (!std::isfinite(thr) || thr < 0.f)
+        snprintf(msg, sizeof msg, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    return msg[0] ? DEME_ERR_INVALID : DEME_OK;
+}
+// what one context refuses of a question whose arguments are in order (the text is left in c->err)
+int clusters_ctx_refused(deme_ctx* c) {
+    if (int rc = records_refused(c))
+        return rc;
+    if (c->haveList && c->nContacts >= ((uint64_t)1 << 31))
+        return fail(c, DEME_ERR_INVALID, "the list has %llu rows; the rows are indexed with 32 bits", (unsigned long long)c->nContacts);
+    return DEME_OK;
+}
+// the columns of the table in clTable (nO rows at the most: a cluster has a counted owner)
+ClusterTableOut clusters_table(deme_ctx* c, size_t nO) {
+    char* b = c->clTable.as<char>();
+    ClusterTableOut o;
+    o.rank = c->clRank.as<uint32_t>();
+    o.label = reinterpret_cast<uint32_t*>(b), o.size = o.label + nO;
+    o.mass = reinterpret_cast<double*>(b + 8 * nO), o.moment = o.mass + nO;
+    return o;
+}
+// where the summary is left in clStat: behind the link pass's edge partials and the stats pass's partials
+ClusterStat* clusters_stat_partials(deme_ctx* c, unsigned gridL) { return reinterpret_cast<ClusterStat*>(c->clStat.as<char>() + (((size_t)gridL * 4 + 7) & ~(size_t)7)); }
+unsigned clusters_grid_link(deme_ctx* c) { return grid_for(c->haveList ? (size_t)c->nContacts : 0); }
+unsigned clusters_grid_stats(deme_ctx* c) { return grid_for(std::max<size_t>(std::max<size_t>(c->nOwners, clusters_grid_link(c)), 1)); }
+// The passes of one context, enqueued on its stream: labels in clLabel (per caller id), the summary in clStat, the row count in
+// clCtl, the table in clTable.  ownerGid: a slab of a decomposed run -- its ghost copies link, and an edge is counted by the slab
+// that owns the clump with the smaller global id.  Nothing the step reads is written.
+int clusters_launch(deme_ctx* c, float thr, const uint32_t* ownerGid, ClusterAsk ask) {
+    const size_t nO = c->nOwners, n = c->haveList ? (size_t)c->nContacts : 0;
+    const unsigned gridL = clusters_grid_link(c), gridS = clusters_grid_stats(c), gridT = grid_for(std::max<size_t>(nO, 1), FIELDS_BLOCK_ROWS);
+    if (ensure(c, c->clCtl, sizeof(ClusterCtl)) || ensure(c, c->clParent, nO * 4) || ensure(c, c->clLabel, nO * 4) || ensure(c, c->clSize, nO * 4) ||
+        ensure(c, c->clStat, (((size_t)gridL * 4 + 7) & ~(size_t)7) + ((size_t)gridS + 1) * sizeof(ClusterStat)))
+        return c->lastStatus;
+    if (ask.rows && (ensure(c, c->clFlag, nO * 4) || ensure(c, c->clRank, nO * 4) || ensure(c, c->clKey[0], nO * 4) || ensure(c, c->clVal[0], nO * 4)))
+        return c->lastStatus;
+    if (ask.table && (ensure(c, c->clKey[1], nO * 4) || ensure(c, c->clVal[1], nO * 4) || ensure(c, c->clTable, nO * CLUSTER_ROW_BYTES) ||
+                      ensure(c, c->clPartial, (size_t)gridT * 2 * sizeof(ClusterPartial))))
+        return c->lastStatus;
+    HIPCK(hipMemsetAsync(c->clCtl.p, 0, sizeof(ClusterCtl), c->stream));
+    ClusterCtl* ctl = c->clCtl.as<ClusterCtl>();
+    uint32_t *parent = c->clParent.as<uint32_t>(), *label = c->clLabel.as<uint32_t>(), *size = c->clSize.as<uint32_t>();
+    const OwnerRec* owners = c->owners.as<OwnerRec>();
+    {
+        ScopedTimer tm(c, "clusters_label", true);
+        if (nO)
+            hipLaunchKernelGGL(k_cluster_init, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, c->nOwnerClumps, owners, c->dp.o2e,
+                               ownerGid ? 1 : 0, parent, size);
+        if (nO && n) {
+            ClusterLinkArgs a{};
+            a.n = (uint32_t)n, a.nSlots = (uint32_t)nO, a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
+            a.t.spheres = c->spheres.as<SphereRec>(), a.t.tris = c->tris.as<TriRec>(), a.t.anal = c->anal.as<AnalObj>();
+            a.t.nSpheres = c->nSpheres, a.t.nTri = c->nTri, a.t.nAnal = c->nAnal, a.t.nOwners = c->nOwners;
+            a.owners = owners, a.o2e = c->dp.o2e, a.force = c->rec[0].as<float>(), a.thr2 = (double)thr * (double)thr;
+            a.parent = parent, a.ownerGid = ownerGid, a.edgePartial = c->clStat.as<uint32_t>(), a.ctl = ctl;
+            hipLaunchKernelGGL(k_cluster_link, dim3(gridL), dim3(256), 0, c->stream, a);
+        }
+        if (nO)
+            hipLaunchKernelGGL(k_cluster_flatten, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, owners, c->dp.o2e, parent, label, size, ctl);
+        if (ask.summary) {
+            ClusterStat* partial = clusters_stat_partials(c, gridL);
+            hipLaunchKernelGGL(k_cluster_stats, dim3(gridS), dim3(256), 0, c->stream, (uint32_t)nO, label, size, nO && n ? gridL : 0u,
+                               c->clStat.as<uint32_t>(), partial);
+            hipLaunchKernelGGL(k_cluster_stats_final, dim3(1), dim3(256), 0, c->stream, gridS, partial, partial + gridS);
+        }
+    }
+    if (!nO || !ask.rows) {
+        HIPCK(hipGetLastError());
+        return DEME_OK;
+    }
+    {
+        ScopedTimer tm(c, "clusters_sort", true);
+        hipLaunchKernelGGL(k_cluster_select, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, owners, c->dp.o2e, label, size,
+                           c->clKey[0].as<uint32_t>(), c->clVal[0].as<uint32_t>(), c->clFlag.as<uint32_t>());
+        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, c->stream, c->clFlag.as<uint32_t>(), c->clRank.as<uint32_t>(), (uint32_t)nO,
+                           &ctl->nRows);
+        if (ask.table) {
+            // (the key nO of the uncounted owners takes part: one value more than the labels)
+            const unsigned bits = bits_for((uint64_t)nO + 1, 32);
+            if (int rc = with_temp(c, c->clTmp, [&](void* tmp, size_t& bytes) {
+                    return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->clKey[0].as<uint32_t>(), c->clKey[1].as<uint32_t>(),
+                                                                  c->clVal[0].as<uint32_t>(), c->clVal[1].as<uint32_t>(), nO, nO, 0, bits,
+                                                                  DEME_SORT_OWN_FROM_RECORDS, c->stream);
+                }))
+                return rc;
+        }
+    }
+    if (ask.table) {
+        ScopedTimer tm(c, "clusters_sums", true);
+        const ClusterTableOut o = clusters_table(c, nO);
+        hipLaunchKernelGGL(k_cluster_sums, dim3(gridT), dim3(256), 0, c->stream, c->dp, (uint32_t)nO, c->clKey[1].as<uint32_t>(),
+                           c->clVal[1].as<uint32_t>(), owners, c->massProps.as<float4>(), o, c->clPartial.as<ClusterPartial>());
+        hipLaunchKernelGGL(k_cluster_final, dim3(1), dim3(256), 0, c->stream, 2u * gridT, (uint32_t)nO, c->clPartial.as<ClusterPartial>(), o);
+    }
+    HIPCK(hipGetLastError());
+    return DEME_OK;
+}
+// the control words and, if asked, the summary clusters_launch left; waits for the stream.  A bound that fired is an error.
+int clusters_fetch_head(deme_ctx* c, bool summary, ClusterCtl* ctl, DemeClusterSummary* sum) {
+    HIPCK(hipMemcpyAsync(ctl, c->clCtl.p, sizeof *ctl, hipMemcpyDeviceToHost, c->stream));
+    if (summary)
+        HIPCK(hipMemcpyAsync(sum, clusters_stat_partials(c, clusters_grid_link(c)) + clusters_grid_stats(c), sizeof *sum, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->clRetries = ctl->retries;
+    if (ctl->bound)
+        return fail(c, DEME_ERR_INTERNAL, "the cluster labelling ran into its bound of %u steps: the forest of parents is damaged (a defect of "
+                    "the library, not of the call)", c->nOwners);
+    return DEME_OK;
+}
+// the table's rows on the host, before they are handed to the caller
+struct ClusterRows {
+    std::vector<uint32_t> label, size;
+    std::vector<double> mass, moment;
+    uint64_t bytes = 0;
+    ClusterRows(bool l, bool s, bool m, bool mo, size_t rows) : label(l ? rows : 0), size(s ? rows : 0), mass(m ? rows : 0), moment(mo ? 3 * rows : 0) {
+        bytes = 4 * (uint64_t)(label.size() + size.size()) + 8 * (uint64_t)(mass.size() + moment.size());
+    }
+};
+// enqueues the copies of the asked columns of the first rows.label.size() ... rows; the caller waits
+int clusters_fetch_rows(deme_ctx* c, ClusterRows& h) {
+    const ClusterTableOut o = clusters_table(c, c->nOwners);
+    auto get = [&](auto& v, const void* src) -> hipError_t {
+        return v.empty() ? hipSuccess : hipMemcpyAsync(v.data(), src, v.size() * sizeof v[0], hipMemcpyDeviceToHost, c->stream);
+    };
+    HIPCK(get(h.label, o.label));
+    HIPCK(get(h.size, o.size));
+    HIPCK(get(h.mass, o.mass));
+    HIPCK(get(h.moment, o.moment));
+    return DEME_OK;
+}
+}  // namespace
+
+int deme_inspect_clusters(deme_ctx* c, float thr, DemeClusterSummary* summary, uint32_t* labels, size_t labelCap, const DemeClusterColumns* table,
+                          size_t tableCap, size_t* nClusters) {
+    if (int rc = check_ready(c))
+        return rc;
+    char msg[320];
+    if (int rc = clusters_args_refused(msg, "deme_inspect_clusters", summary, labels, labelCap, c->nOwners, table, nClusters, thr))
+        return fail(c, rc, "%s", msg);
+    if (int rc = clusters_ctx_refused(c))
+        return rc;
+    const ClusterAsk ask{summary != nullptr, labels != nullptr, table || nClusters, table != nullptr};
+    if (int rc = clusters_launch(c, thr, nullptr, ask))
+        return rc;
+    ClusterCtl ctl{};
+    DemeClusterSummary sum{};
+    if (int rc = clusters_fetch_head(c, ask.summary, &ctl, &sum))
+        return rc;
+    c->qHostBytes += sizeof ctl + (ask.summary ? sizeof sum : 0);
+    const size_t nO = c->nOwners, rows = ask.rows ? (size_t)ctl.nRows : 0;
+    if (nClusters)
+        *nClusters = rows;
+    if (table && tableCap < rows)
+        return fail(c, DEME_ERR_INVALID, "deme_inspect_clusters: the table has %zu rows; room for %zu was given", rows, tableCap);
+    std::vector<uint32_t> hl(labels ? nO : 0);  // (the caller's arrays are written once the call cannot fail any more)
+    ClusterRows h(table && table->label, table && table->size, table && table->mass, table && table->moment, rows);
+    if (!hl.empty())
+        HIPCK(hipMemcpyAsync(hl.data(), c->clLabel.p, nO * 4, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = clusters_fetch_rows(c, h))
+        return rc;
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->qHostBytes += 4ull * hl.size() + h.bytes;
+    if (summary)
+        *summary = sum;
+    if (!hl.empty())
+        memcpy(labels, hl.data(), nO * 4);
+    auto copy = [](auto* dst, const auto& v) {
+        if (dst && !v.empty())
+            memcpy(dst, v.data(), v.size() * sizeof v[0]);
+    };
+    if (table)
+        copy(table->label, h.label), copy(table->size, h.size), copy(table->mass, h.mass), copy(table->moment, h.moment);
+    return DEME_OK;
+}
+
+int deme_clusters_link_retries(const deme_ctx* c, uint64_t* retries) {
+    if (!c || !retries)
+        return DEME_ERR_INVALID;
+    *retries = c->clRetries;
     return DEME_OK;
 }
 

@@ -1612,8 +1612,12 @@ class DEMSolver {
     /// lower corner at origin (world frame) -- solid fraction, mean velocity, granular temperature, kinetic and contact stress,
     /// coordination -- summed on the device (deme_inspect_fields).  See DEMFieldInspector.
     std::shared_ptr<class DEMFieldInspector> CreateFieldInspector(float3 origin, float3 cellSize, unsigned nx, unsigned ny, unsigned nz);
+    /// Not in the reference: the connected components of the contact network -- agglomerates, fragments, rattlers -- labelled on the
+    /// device (deme_inspect_clusters).  See DEMClusterInspector.
+    std::shared_ptr<class DEMClusterInspector> CreateClusterInspector();
     friend class DEMInspector;
     friend class DEMFieldInspector;
+    friend class DEMClusterInspector;
     friend class DEMTracker;
 
     // ---- output (API.h:1096-1122, 1318-1324); formats of dT.cpp:1254-1405, 1491-1618, 1620-1848
@@ -3484,6 +3488,77 @@ class DEMFieldInspector {
     std::vector<double> m_mass, m_volume, m_momentum, m_kinetic, m_virial;
 };
 
+/// Not in the reference (GetClumpContacts hands the pairs to the script and leaves the graph work there): which clumps are joined to
+/// which (deme_inspect_clusters / deme_multi_inspect_clusters: the components are labelled and summed on the device; the summary,
+/// one label per owner and one row per cluster come to the host).  Two clumps are joined by a sphere-sphere contact between them
+/// whose force is at least force_thres; meshes and analytical objects join nothing, so a floor does not make the bed one cluster.
+/// A cluster's label is the smallest owner id in it.  Update() makes the one library call.
+///   GetNumClusters() / GetNumSingletons() / GetLargestClusterSize() / GetNumEdges()
+///   GetOwnerLabels()      per owner: its cluster's label; 0xFFFFFFFF for an owner that is no clump
+///   GetClusterLabels()    per cluster, ascending; the other per-cluster arrays are in this order
+///   GetClusterSizes()     clumps in the cluster
+///   GetClusterMasses()    their mass
+///   GetClusterCentres()   their centre of mass, world frame: 3 a cluster
+///   WriteCsv(path)        label, size, mass, x, y, z
+/// Needs the contact output content to include forces (the default), like "clump_virial".
+class DEMClusterInspector {
+  public:
+    explicit DEMClusterInspector(DEMSolver* sys) : m_sys(sys) {}
+    /// the components of the current contact list: one call into the library
+    void Update(float force_thres = DEME_TINY_FLOAT_HOST) {
+        if (!(m_sys->m_cnt_out_content & FORCE))  // (the sentence the library gives "clump_virial" then)
+            throw std::runtime_error("contact recording is off (deme_set_record_contacts)");
+        const size_t nO = m_sys->m_n_owners;  // (a table has at most one row per owner)
+        std::vector<uint32_t> owner(nO), label(nO), size(nO);
+        std::vector<double> mass(nO), moment(3 * nO);
+        DemeClusterSummary sum{};
+        DemeClusterColumns cols{label.data(), size.data(), mass.data(), moment.data()};
+        size_t rows = 0;
+        if (m_sys->decomposed())
+            m_sys->mcheck(deme_multi_inspect_clusters(m_sys->m_multi, force_thres, &sum, owner.data(), nO, &cols, nO, &rows));
+        else
+            m_sys->check(deme_inspect_clusters(m_sys->m_ctx, force_thres, &sum, owner.data(), nO, &cols, nO, &rows));
+        label.resize(rows), size.resize(rows), mass.resize(rows);
+        std::vector<double> centre(3 * rows, 0.0);
+        for (size_t r = 0; r < rows; r++)
+            for (int k = 0; k < 3; k++)
+                centre[3 * r + k] = mass[r] > 0.0 ? moment[3 * r + k] / mass[r] : 0.0;
+        m_owner.swap(owner), m_label.swap(label), m_size.swap(size), m_mass.swap(mass), m_centre.swap(centre);
+        m_sum = sum, m_updated = true;
+    }
+    size_t GetNumClusters() const { return updated(), (size_t)m_sum.clusters; }
+    size_t GetNumSingletons() const { return updated(), (size_t)m_sum.singletons; }
+    size_t GetLargestClusterSize() const { return updated(), (size_t)m_sum.largestSize; }
+    bodyID_t GetLargestClusterLabel() const { return updated(), (bodyID_t)m_sum.largestLabel; }
+    size_t GetNumEdges() const { return updated(), (size_t)m_sum.edges; }
+    const std::vector<uint32_t>& GetOwnerLabels() const { return updated(), m_owner; }
+    const std::vector<uint32_t>& GetClusterLabels() const { return updated(), m_label; }
+    const std::vector<uint32_t>& GetClusterSizes() const { return updated(), m_size; }
+    const std::vector<double>& GetClusterMasses() const { return updated(), m_mass; }
+    const std::vector<double>& GetClusterCentres() const { return updated(), m_centre; }
+    void WriteCsv(const std::string& outfilename) const {
+        updated();
+        std::ostringstream o;
+        o.precision(17);
+        o << "label,size,mass,x,y,z\n";
+        for (size_t r = 0; r < m_label.size(); r++)
+            o << m_label[r] << "," << m_size[r] << "," << m_mass[r] << "," << m_centre[3 * r] << "," << m_centre[3 * r + 1] << "," << m_centre[3 * r + 2]
+              << "\n";
+        m_sys->flush(outfilename, o);
+    }
+
+  private:
+    void updated() const {
+        if (!m_updated)
+            throw std::runtime_error("DEMClusterInspector: call Update() first");
+    }
+    DEMSolver* m_sys;
+    bool m_updated = false;
+    DemeClusterSummary m_sum{};
+    std::vector<uint32_t> m_owner, m_label, m_size;
+    std::vector<double> m_mass, m_centre;
+};
+
 /// Access to the state of the owners of one loaded object (a batch of clumps, an analytical object, a mesh):
 /// getters read the current device state, setters write it back (DEMTracker, AuxClasses.h:93-420).
 class DEMTracker {
@@ -3794,6 +3869,9 @@ class DEMTracker {
 
 inline std::shared_ptr<DEMFieldInspector> DEMSolver::CreateFieldInspector(float3 origin, float3 cellSize, unsigned nx, unsigned ny, unsigned nz) {
     return std::make_shared<DEMFieldInspector>(this, origin, cellSize, nx, ny, nz);
+}
+inline std::shared_ptr<DEMClusterInspector> DEMSolver::CreateClusterInspector() {
+    return std::make_shared<DEMClusterInspector>(this);
 }
 inline std::shared_ptr<DEMInspector> DEMSolver::CreateInspector(const std::string& quantity) {
     return std::make_shared<DEMInspector>(this, quantity);

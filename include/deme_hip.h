@@ -65,6 +65,7 @@ extern "C" {
 #define DEME_ERR_COMPILE 6
 #define DEME_ERR_PEER 7 /* a collective call gave up because ANOTHER rank of the halo group reported an error (its own message says which) */
 #define DEME_ERR_HALO 8 /* deme_multi_change_owner_sizes: the grown clumps would no longer fit the halo the slabs were cut with */
+#define DEME_ERR_INTERNAL 9 /* a bounded device loop ran into its bound (deme_inspect_clusters): a defect of the library, not of the call */
 
 /* ---- parameter block: replaces deme::DEMSimParams (DEM/Defines.h:194-265) - */
 typedef struct DemeParams {
@@ -590,11 +591,66 @@ typedef struct DemeFieldColumns { /* any may be NULL; nCells entries (times 3 / 
 #define DEME_FIELDS_MAX_CELLS (1u << 21)
 int deme_inspect_fields(deme_ctx* ctx, const DemeFieldGrid* grid, float forceThreshold, const DemeFieldColumns* out);
 unsigned deme_fields_block_rows(void);
+/* Cluster inspector (no counterpart in the reference, whose GetClumpContacts hands the pairs to the script): the connected components
+ * of the contact network, labelled on the device -- how many agglomerates or fragments there are, how large and heavy each is, where
+ * its centre lies, which clumps are rattlers outside the force network.
+ *   VERTICES.  A vertex is an own clump owner -- its caller id is < nOwnerClumps, the test deme_inspect_contacts makes -- that is no
+ *   ghost copy.  In a slab of a decomposed run the ghost copies of clumps are vertices too, for linking only: they are never counted.
+ *   Mesh and analytical owners are never vertices, so a floor does not join the bed into one cluster.
+ *   EDGES.  An edge is a row of the current list of class sphere-sphere that is counted by the test of deme_inspect_contacts --
+ *   record 0, (double)fx^2 + (double)fy^2 + (double)fz^2 >= (double)forceThreshold^2 -- whose two spheres belong to two DIFFERENT
+ *   owners that are both vertices.  With a threshold of 0 every such listed row is an edge, rows with zero force included.
+ *   LABEL.  The label of a vertex is the smallest caller owner id of its connected component: a pure function of the graph, whatever
+ *   the order the threads ran in.  An owner that is no vertex gets 0xFFFFFFFF.
+ *   SUMMARY.  vertices; edges: the counted rows that are edges (several rows between one pair of clumps count each); clusters;
+ *   singletons: the clusters of size 1; largestSize; largestLabel: the smallest label among the clusters of the largest size
+ *   (0xFFFFFFFF when there is no vertex).
+ *   CLUSTER TABLE.  One row per cluster that has at least one COUNTED owner -- an own clump that is no ghost copy --, labels
+ *   ascending:
+ *     label    uint32_t
+ *     size     uint32_t   the cluster's counted owners
+ *     mass     double     the sum of (double)m, m the mass of the owner's mass-property entry
+ *     moment   3 doubles  the sum of (double)m * P_k, P the owner's centre of mass in the world frame in fp64, decoded as
+ *                         deme_inspect_fields decodes it (decode_pos(...)_k + (double)LBF_k); the cluster's centre is moment / mass
+ *                         (the caller divides)
+ *   ORDER.  Within a cluster the terms are added owner slots ascending, down a tree of fixed shape; the integers are summed with
+ *   integer atomics or on a fixed grid: two calls on one state give the same bits.  No floating-point atomics.
+ * Any output may be NULL, and any column of the table.  *nClusters always receives the table's row count (also when table is NULL,
+ * and when the call returns for too small a tableCap); with tableCap < *nClusters no row is written and the call returns
+ * DEME_ERR_INVALID: ask with table NULL, size the arrays, ask again -- the protocol of deme_query_owner_contacts.  The caller's
+ * arrays are written once the call can no longer fail.
+ * Bytes that come to the host, all added to deme_query_host_bytes: 16 for the row count and the control words of every call that
+ * is not refused; 48 for the summary; 4 per owner for the labels; 4 + 4 + 8 + 24 per table row for the asked columns.
+ * Read-only: the list, the prescriptions and the step's buffers stay as they are.
+ * Refused with DEME_ERR_INVALID and nothing written (nClusters neither, no byte added), in this order: every output NULL; labels
+ * given with labelCap < nOwners; a threshold that is negative or not finite; recording off or a seeded list (the messages of
+ * deme_download_contact_records); a list of 2^31 rows or more.
+ * No loop on the device is unbounded: a find takes at most nOwners steps, a link at most nOwners retries; a bound that is passed
+ * sets a flag, and the call returns DEME_ERR_INTERNAL with nothing written.
+ * deme_clusters_link_retries: the compare-and-swaps the link pass of the last call lost to another thread (a measurement). */
+typedef struct DemeClusterSummary {
+    uint64_t vertices;
+    uint64_t edges;
+    uint64_t clusters;
+    uint64_t singletons;
+    uint64_t largestSize;
+    uint64_t largestLabel;
+} DemeClusterSummary;
+typedef struct DemeClusterColumns { /* any may be NULL; tableCap entries (times 3) each */
+    uint32_t* label;
+    uint32_t* size;
+    double* mass;
+    double* moment;
+} DemeClusterColumns;
+int deme_inspect_clusters(deme_ctx* ctx, float forceThreshold, DemeClusterSummary* summary, uint32_t* labels, size_t labelCap,
+                          const DemeClusterColumns* table, size_t tableCap, size_t* nClusters);
+int deme_clusters_link_retries(const deme_ctx* ctx, uint64_t* retries);
 
 /* timing of the kernels this library launched (HIP events on the context stream);
  * names: "calc_forces", "integrate", "detect", the passes of deme_inspect_tri_loads "tri_loads_select", "tri_loads_sort",
- * "tri_loads_sums", and those of deme_inspect_fields "fields_cells" (both select kernels), "fields_sort", "fields_sums"; returns avg
- * ms per launch since last reset */
+ * "tri_loads_sums", and those of deme_inspect_fields "fields_cells" (both select kernels), "fields_sort", "fields_sums", and those of deme_inspect_clusters
+ * "clusters_label" (init, link, flatten, summary), "clusters_sort" (select, scan, sort), "clusters_sums"; returns avg ms per launch
+ * since last reset */
 int deme_kernel_time_ms(deme_ctx* ctx, const char* name, double* avg_ms, uint64_t* launches);
 int deme_kernel_time_reset(deme_ctx* ctx);
 /* enable = 0: off; n > 0: every n-th launch of each timed kernel is bracketed with events (an event pair costs ~3 us of
@@ -855,6 +911,17 @@ int deme_multi_inspect_tri_loads(deme_multi* m, float forceThreshold, uint32_t f
  * deme_inspect_fields; when a contact column is asked also those of deme_multi_inspect_contacts (a run that evaluates every cross-cut
  * contact once; a slab whose list is a seed, as on the step after a migration). */
 int deme_multi_inspect_fields(deme_multi* m, const DemeFieldGrid* grid, float forceThreshold, const DemeFieldColumns* out);
+/* deme_inspect_clusters for a decomposed run: the same outputs in GLOBAL owner ids (labelCap counts global owners).  Every slab
+ * labels its own clumps and its ghost copies in its local ids and hands down, per local owner, the pair (global id, global id of
+ * its local root), and its table keyed by the local root and summed over its OWN clumps only (a clump is an own clump of one slab).
+ * The host unites the pairs in one array union-find with the same smaller-id-wins rule; the label is the root of the global id.  The
+ * slabs' table rows are added into their final label in slab order, within a slab local roots ascending: a fixed order.  An edge
+ * is counted by the slab that owns the clump with the smaller global id; the rest of the summary is computed from the merged table.
+ * The call waits for the run.  The refusals of deme_inspect_clusters' arguments, then those of deme_multi_inspect_contacts (a run
+ * that evaluates every cross-cut contact once; a slab without recording, or whose list is a seed as on the step after a migration).
+ * Bytes per slab, added to deme_multi_query_host_bytes: 16 + 48, 8 per local owner, 40 per row of the slab's table. */
+int deme_multi_inspect_clusters(deme_multi* m, float forceThreshold, DemeClusterSummary* summary, uint32_t* labels, size_t labelCap,
+                                const DemeClusterColumns* table, size_t tableCap, size_t* nClusters);
 /* deme_add_owner_acc by GLOBAL owner id: a clump's entry goes to the slab that owns it, a replicated owner's to every slab */
 int deme_multi_add_owner_acc(deme_multi* m, uint32_t owner, uint32_t n, const float* acc, const float* angAcc);
 /* the visible HIP devices (0 and DEME_OK where there is none: what the constructors check ids against) */
