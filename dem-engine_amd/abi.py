@@ -262,6 +262,7 @@ def load_library():
         "deme_scatter_owner_state": [_P, _P, C.c_size_t, C.POINTER(DemeOwnerState)],
         "deme_sort_pairs_u32": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P, _P],
         "deme_sort_keys_u64": [C.c_int, _P, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _P],
+        "deme_seg_sum_f64": [C.c_int, _P, _P, C.c_size_t, C.c_uint, C.c_uint32, _P, _P],
         "deme_change_owner_sizes": [_P, _P, _P, C.c_size_t], "deme_num_components": [_P, C.POINTER(C.c_uint32)],
         "deme_download_components": [_P, _P, _P, _P, _P, C.c_size_t], "deme_download_sphere_components": [_P, _P, C.c_size_t],
         "deme_set_template_components": [_P, C.c_uint32], "deme_multi_change_owner_sizes": [_P, _P, _P, C.c_size_t],
@@ -942,6 +943,19 @@ def sort_pairs_u32(keys, vals, begin_bit, end_bit, force_own=True, device=0):
     if rc:
         raise DemeError(f"deme_sort_pairs_u32 failed with code {rc}")
     return ko, vo
+
+
+def seg_sum_f64(keys, terms, n_keys, device=0):
+    """The inspectors' segmented sum alone: sums (n_keys x lanes) and counts (n_keys) of the rows of terms (n x lanes) by runs of
+    equal ascending uint32 keys; keys >= n_keys are uncounted and lie behind the others."""
+    keys, terms = np.ascontiguousarray(keys, np.uint32), np.ascontiguousarray(terms, np.float64)
+    assert keys.ndim == 1 and terms.ndim == 2 and terms.shape[0] == keys.size
+    lanes = terms.shape[1]
+    sums, counts = np.empty((n_keys, lanes), np.float64), np.empty(n_keys, np.uint32)
+    rc = load_library().deme_seg_sum_f64(device, _ptr(keys), _ptr(terms), keys.size, lanes, n_keys, _ptr(sums), _ptr(counts))
+    if rc:
+        raise DemeError(f"deme_seg_sum_f64 failed with code {rc}")
+    return sums, counts
 
 
 def sort_keys_u64(keys, begin_bit, end_bit, force_own=True, device=0):

@@ -12,12 +12,14 @@
 //   k_cluster_select    one thread per owner slot: the pair (label, slot) of a counted owner, key nIds for any other; and per id the
 //                       flag "a root with a counted owner", whose exclusive scan (k_scan_small) is the rank of the cluster's table row
 //   deme_radix_sort     the pairs by label.  Stable: the slots of a cluster stay ascending, the uncounted owners end up behind
-//   k_cluster_sums / _final    the segmented scan of deme_fields.h with four fp64 lanes (mass, three moments) and the count
+//   k_seg_sums<4> / k_seg_final<4>   the segmented sum of deme_seg_sum.h with four fp64 lanes (ClusterTerm: mass, three moments)
+//                       and the count; ClusterTableOut writes a finished cluster's row
 //   k_cluster_pairs     (a slab of a decomposed run) per local id the pair (global id, global id of its local root)
 // No floating-point atomics, and no workgroup waits for another: a thread of k_cluster_link that loses a compare-and-swap goes on
 // from the roots it finds next, it never waits for anybody.
 #pragma once
-#include "deme_fields.h"
+#include "deme_query.h"
+#include "deme_seg_sum.h"
 
 namespace deme_dev {
 
@@ -99,12 +101,12 @@ struct ClusterLinkArgs {
 
 // the two vertices (caller ids) and owner slots of row i if the row is an edge
 __device__ inline bool cluster_row_edge(const ClusterLinkArgs& a, uint32_t i, uint32_t& ia, uint32_t& ib, uint32_t& oA, uint32_t& oB) {
-    const size_t r = (size_t)i * 3;
-    const double fx = a.force[r], fy = a.force[r + 1], fz = a.force[r + 2];
+    double fx, fy, fz;
+    const bool counted = row_force_counted(a.force, i, a.thr2, fx, fy, fz);
     const uint64_t k = a.keys[i];
-    if (key_class(k) != DEME_KEY_CLASS_SS || !(fx * fx + fy * fy + fz * fz >= a.thr2))
+    if (key_class(k) != DEME_KEY_CLASS_SS || !counted)
         return false;
-    field_row_owners(a.t, k, oA, oB);  // owner slots, as k_contact_sums looks them up
+    row_owners(a.t, k, oA, oB);  // owner slots
     if (oA >= a.nSlots || oB >= a.nSlots || oA == oB)
         return false;
     ia = a.o2e ? a.o2e[oA] : oA, ib = a.o2e ? a.o2e[oB] : oB;
@@ -250,39 +252,19 @@ struct ClusterTableOut {  // nIds entries (times 3) each; rank: the exclusive sc
             moment[3 * (size_t)row + j] = v[1 + j];
     }
 };
-using ClusterPartial = FieldPartial<CLUSTER_LANES>;
-
-// keys / slots: the sorted pairs
-__global__ __launch_bounds__(256) void k_cluster_sums(const DevParams p, uint32_t n, const uint32_t* __restrict__ keys,
-                                                      const uint32_t* __restrict__ slots, const OwnerRec* __restrict__ owners,
-                                                      const float4* __restrict__ massProps, const ClusterTableOut out,
-                                                      ClusterPartial* __restrict__ partial) {
-    __shared__ FieldScanLds<CLUSTER_LANES> s;
-    const uint32_t t = threadIdx.x, e = blockIdx.x * FIELDS_BLOCK_ROWS + t;
-    if (keys[blockIdx.x * FIELDS_BLOCK_ROWS] >= n) {  // behind the counted owners (the block's first entry is one of the list)
-        if (t < 2)
-            partial[2 * blockIdx.x + t] = field_partial_zero<CLUSTER_LANES>(0xFFFFFFFFu);
-        return;
-    }
-    const uint32_t key = e < n ? keys[e] : 0xFFFFFFFFu;
-    double v[CLUSTER_LANES] = {0., 0., 0., 0.};
-    uint32_t cnt = 0;
-    if (key < n) {
+struct ClusterTerm {  // slots: the sorted owner slots
+    DevParams p;
+    const uint32_t* slots;
+    const OwnerRec* owners;
+    const float4* massProps;
+    __device__ uint32_t operator()(uint32_t e, double (&v)[CLUSTER_LANES]) const {
         const OwnerRec r = load_owner(owners, slots[e]);  // (a slot of k_cluster_select: < nSlots)
         const d3 P = decode_pos(r.voxelID, r.locX, r.locY, r.locZ, p);
         const double m = (double)massProps[r.inertiaOff].x;
         v[0] = m, v[1] = m * (P.x + (double)p.LBFX), v[2] = m * (P.y + (double)p.LBFY), v[3] = m * (P.z + (double)p.LBFZ);
-        cnt = 1;
+        return 1u;
     }
-    field_block_sums<CLUSTER_LANES>(s, n, key, v, cnt, out, partial);
-}
-
-__global__ __launch_bounds__(256) void k_cluster_final(uint32_t nPartials, uint32_t nIds, const ClusterPartial* __restrict__ partial,
-                                                       const ClusterTableOut out) {
-    __shared__ FieldScanLds<CLUSTER_LANES> s;
-    __shared__ ClusterPartial carryLds;
-    field_final_sums<CLUSTER_LANES>(s, carryLds, nPartials, nIds, partial, out);
-}
+};
 
 // ---- a slab of a decomposed run ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_cluster_pairs(uint32_t nIds, const uint32_t* __restrict__ label, const uint32_t* __restrict__ ownerGid,

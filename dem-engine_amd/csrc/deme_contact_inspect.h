@@ -71,22 +71,10 @@ __global__ __launch_bounds__(256) void k_contact_sums(const ContactSumArgs a) {
         clumps = a.mask[i] != 0.0f ? 1u : 0u;
     if (i < a.n) {
         const size_t r = (size_t)i * 3;
-        const double fx = a.force[r], fy = a.force[r + 1], fz = a.force[r + 2];
-        if (fx * fx + fy * fy + fz * fz >= a.thr2) {
-            const uint64_t k = a.keys[i];
-            const uint32_t cls = key_class(k), sa = key_a(k), sb = key_b(k);
-            uint32_t oA = 0xFFFFFFFFu, oB = 0xFFFFFFFFu;  // owner slots, as k_query_select looks them up
-            if (sa < a.t.nSpheres)
-                oA = load_sphere(a.t.spheres, sa).owner;
-            if (cls == DEME_KEY_CLASS_SS) {
-                if (sb < a.t.nSpheres)
-                    oB = load_sphere(a.t.spheres, sb).owner;
-            } else if (cls == DEME_KEY_CLASS_SM) {
-                if (sb < a.t.nTri)
-                    oB = a.t.tris[sb].owner;
-            } else if (sb < a.t.nAnal) {
-                oB = a.t.anal[sb].owner;
-            }
+        double fx, fy, fz;
+        if (row_force_counted(a.force, i, a.thr2, fx, fy, fz)) {
+            uint32_t oA, oB;  // owner slots
+            row_owners(a.t, a.keys[i], oA, oB);
             if (oA < a.nSlots && a.mask[oA] != 0.0f) {
                 sides++;
                 if (PER_OWNER)

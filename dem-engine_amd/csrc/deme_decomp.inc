@@ -1688,18 +1688,26 @@ int slab_region(deme_ctx* c, const char* code, int* id) {
     *id = it->second;
     return DEME_OK;
 }
+// A run that evaluates every cross-cut contact once cannot sum the sides of its pairs.  (Nothing sets pairsOnce on a deme_multi's
+// groups today, so the branch is not reached.)
+int multi_pairs_once_refused(deme_multi* m, const char* who) {
+    for (auto* g : m->groups)
+        if (g->pairsOnce)
+            return mfail(m, DEME_ERR_INVALID, "%s: the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab that "
+                         "does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
+    return DEME_OK;
+}
 // what both calls refuse before any slab is asked, and the slabs' regions (in slab order)
 int multi_contact_inspect_begin(deme_multi* m, const char* who, const void* out, const char* regionCode, float thr, std::vector<int>& regions) {
     if (!m || !m->plan)
         return DEME_ERR_INVALID;
     if (!out)
         return mfail(m, DEME_ERR_INVALID, "%s: null output", who);
-    if (!std::isfinite(thr) || thr < 0.f)
-        return mfail(m, DEME_ERR_INVALID, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
-    for (auto* g : m->groups)
-        if (g->pairsOnce)
-            return mfail(m, DEME_ERR_INVALID, "%s: the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab that "
-                         "does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
+    char msg[320];
+    if (threshold_refused(msg, who, thr))
+        return mfail(m, DEME_ERR_INVALID, "%s", msg);
+    if (int rc = multi_pairs_once_refused(m, who))
+        return rc;
     if (int rc = deme_multi_sync(m))
         return rc;
     if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
@@ -1788,7 +1796,7 @@ int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, flo
 // Triangles carry the same ids on every slab, and a row whose sphere belongs to a ghost copy is not counted: every sphere-triangle
 // pair is counted by the one slab that owns the sphere's clump.  All slabs' passes are enqueued first, each on its device, then the
 // host takes the asked range slab by slab and adds the arrays in slab order.  (The pairsOnce refusal mirrors the contact
-// inspectors'; nothing sets pairsOnce on a deme_multi's groups today, so the branch is not reached.)
+// inspectors'.)
 int deme_multi_inspect_tri_loads(deme_multi* m, float thr, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts) {
     const char* who = "deme_multi_inspect_tri_loads";
     if (!m || !m->plan)
@@ -1799,10 +1807,8 @@ int deme_multi_inspect_tri_loads(deme_multi* m, float thr, uint32_t firstTri, ui
         return mfail(m, rc, "%s", msg);
     if (!nTris)
         return DEME_OK;
-    for (auto* g : m->groups)
-        if (g->pairsOnce)
-            return mfail(m, DEME_ERR_INVALID, "%s: the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab that "
-                         "does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
+    if (int rc = multi_pairs_once_refused(m, who))
+        return rc;
     if (int rc = deme_multi_sync(m))
         return rc;
     if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
@@ -1847,10 +1853,8 @@ int deme_multi_inspect_fields(deme_multi* m, const DemeFieldGrid* grid, float th
         return mfail(m, rc, "%s", msg);
     const bool askOwner = fields_ask_owner(out), askContact = fields_ask_contact(out);
     if (askContact)
-        for (auto* g : m->groups)
-            if (g->pairsOnce)
-                return mfail(m, DEME_ERR_INVALID, "%s: the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab "
-                             "that does not evaluate a pair holds no record of it, so its side of the pair cannot be summed", who);
+        if (int rc = multi_pairs_once_refused(m, who))
+            return rc;
     if (int rc = deme_multi_sync(m))
         return rc;
     DemeFieldColumns perSlab = *out;  // (a slab with an empty list is not asked for its records: slab_records_refused)

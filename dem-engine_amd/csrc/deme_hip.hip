@@ -67,6 +67,11 @@ struct DevBuf {
     }
 };
 
+// the (key, value) pairs of one user of the segmented sum (seg_reserve, seg_sort, seg_sums): [0] as selected, [1] sorted
+struct SegPairs {
+    DevBuf key[2], val[2];
+};
+
 // One built contact list: what a detection's part 2 (detect_part2, build_legacy_lists) writes and the stepping kernels read, with
 // the host scalars that describe it.  A context holds two (deme_ctx::list): an asynchronous detection builds one while the steps
 // in flight read the other, and the pair is swapped by flipping an index.  Everything else a list refers to is shared by both
@@ -137,16 +142,22 @@ struct deme_ctx {
     // contact inspectors (deme_contact_inspect.h): the mask and the side counts per owner slot, the blocks' partials with the result
     // behind them, the counts in the caller's (or global) ids; allocated by the first call and kept
     DevBuf ciMask, ciCounts, ciPartial, ciOut;
-    // triangle loads (deme_tri_loads.h): the (triangle, row) pairs before and after the sort, the sort's own scratch (never the
-    // detection's: an asynchronous detection may be sorting), the blocks' partials, the sums and counts per triangle; kept likewise
-    DevBuf tlTri[2], tlRow[2], tlTmp, tlPartial, tlForce, tlCount;
+    // the segmented sums of the inspectors below (deme_seg_sum.h): the sort's own scratch (never the detection's: an asynchronous
+    // detection may be sorting) and the blocks' partials.  One pair for all of them: every inspector pass is enqueued on the
+    // context's own stream, so no two are in flight at once.  Kept likewise
+    DevBuf segTmp, segPartial;
+    // triangle loads (deme_tri_loads.h): the (triangle, row) pairs before and after the sort, the sums and counts per triangle
+    SegPairs tlPairs;
+    DevBuf tlForce, tlCount;
     // field inspector (deme_fields.h): the cell of every owner slot, the (cell, slot) and (cell, side) pairs before and after their
-    // sorts, the sorts' own scratch, the blocks' partials, the columns of every cell; kept likewise
-    DevBuf fiCellOf, fiOwnKey[2], fiOwnVal[2], fiSideKey[2], fiSideVal[2], fiTmp, fiPartial, fiOut;
+    // sorts, the columns of every cell
+    SegPairs fiOwn, fiSide;
+    DevBuf fiCellOf, fiOut;
     // cluster inspector (deme_clusters.h): parent, label, size, row flag and rank per caller id, the (label, slot) pairs before and
-    // after their sort, the sort's own scratch, the integer partials with the summary behind them, the partials of the table's sums,
-    // the table, the control words, a slab's (global id, global root) pairs; kept likewise
-    DevBuf clParent, clLabel, clSize, clFlag, clRank, clKey[2], clVal[2], clTmp, clStat, clPartial, clTable, clCtl, clPairs;
+    // after their sort, the integer partials with the summary behind them, the table, the control words, a slab's (global id, global
+    // root) pairs
+    SegPairs clSel;
+    DevBuf clParent, clLabel, clSize, clFlag, clRank, clStat, clTable, clCtl, clPairs;
     uint32_t clRetries = 0;  // compare-and-swaps the last call's link pass lost (deme_clusters_link_retries)
     std::map<std::string, int> regionBySource;  // deme_multi_inspect_contacts: a region string compiles once per slab context
     // detection scratch
@@ -459,6 +470,43 @@ inline unsigned bits_for(uint64_t n, unsigned cap) {
     while (b < cap && (1ull << b) < n)
         b++;
     return b;
+}
+
+// ---- the inspectors' segmented sum by key (deme_seg_sum.h): reserve, sort, sum ---------------------
+// Room for n pairs: both halves, or only the half a select kernel writes (sorted false: nothing will sort them).
+int seg_reserve(deme_ctx* c, SegPairs& p, size_t n, bool sorted = true) {
+    for (int k = 0; k < (sorted ? 2 : 1); k++)
+        if (ensure(c, p.key[k], n * 4) || ensure(c, p.val[k], n * 4))
+            return c->lastStatus;
+    return DEME_OK;
+}
+// The n pairs of half 0 into half 1, stably by keys 0 .. nKeys.
+int seg_sort(deme_ctx* c, SegPairs& p, size_t n, size_t nKeys) {
+    // (the key nKeys of the uncounted entries takes part: one value more than the keys)
+    const unsigned bits = bits_for((uint64_t)nKeys + 1, 32);
+    return with_temp(c, c->segTmp, [&](void* tmp, size_t& bytes) {
+        return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, p.key[0].as<uint32_t>(), p.key[1].as<uint32_t>(), p.val[0].as<uint32_t>(),
+                                                      p.val[1].as<uint32_t>(), n, n, 0, bits, DEME_SORT_OWN_FROM_RECORDS, c->stream);
+    });
+}
+// The sums of n sorted entries by key: term(e, v) reads what entry e adds (through the sorted values it holds), out.write stores a
+// finished key.  The caller has cleared the outputs; nothing is launched for an empty list (a block reads the first entry of its
+// range, so an empty list has no valid first block).
+template <int L, class Term, class Out>
+int seg_sums(deme_ctx* c, const uint32_t* keys, size_t n, size_t nKeys, const Term& term, const Out& out) {
+    if (!n)
+        return DEME_OK;
+    const unsigned grid = grid_for(n, SEG_BLOCK_ROWS);
+    if (ensure(c, c->segPartial, (size_t)grid * 2 * sizeof(SegPartial<L>)))
+        return c->lastStatus;
+    SegPartial<L>* partial = c->segPartial.as<SegPartial<L>>();
+    hipLaunchKernelGGL((k_seg_sums<L, Term, Out>), dim3(grid), dim3(256), 0, c->stream, (uint32_t)n, (uint32_t)nKeys, keys, term, out, partial);
+    hipLaunchKernelGGL((k_seg_final<L, Out>), dim3(1), dim3(256), 0, c->stream, 2u * grid, (uint32_t)nKeys, (const SegPartial<L>*)partial, out);
+    return DEME_OK;
+}
+template <int L, class Term, class Out>
+int seg_sums(deme_ctx* c, const SegPairs& p, size_t n, size_t nKeys, const Term& term, const Out& out) {
+    return seg_sums<L>(c, p.key[1].as<uint32_t>(), n, nKeys, term, out);
 }
 
 // ---- kernel timing (HIP events on the context stream) ------------------------------------------
@@ -1762,14 +1810,16 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
                      &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr, &c->qState,
-                     &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut, &c->tlTri[0], &c->tlTri[1], &c->tlRow[0], &c->tlRow[1],
-                     &c->tlTmp, &c->tlPartial, &c->tlForce, &c->tlCount, &c->fiCellOf, &c->fiOwnKey[0], &c->fiOwnKey[1], &c->fiOwnVal[0],
-                     &c->fiOwnVal[1], &c->fiSideKey[0], &c->fiSideKey[1], &c->fiSideVal[0], &c->fiSideVal[1], &c->fiTmp, &c->fiPartial,
-                     &c->fiOut, &c->clParent, &c->clLabel, &c->clSize, &c->clFlag, &c->clRank, &c->clKey[0], &c->clKey[1], &c->clVal[0],
-                     &c->clVal[1], &c->clTmp, &c->clStat, &c->clPartial, &c->clTable, &c->clCtl, &c->clPairs};
+                     &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut, &c->segTmp, &c->segPartial, &c->tlForce, &c->tlCount,
+                     &c->fiCellOf, &c->fiOut, &c->clParent, &c->clLabel, &c->clSize, &c->clFlag, &c->clRank, &c->clStat, &c->clTable,
+                     &c->clCtl, &c->clPairs};
     for (DevBuf* b : all)
         if (b->p)
             hipFree(b->p);
+    for (SegPairs* p : {&c->tlPairs, &c->fiOwn, &c->fiSide, &c->clSel})
+        for (DevBuf* b : {&p->key[0], &p->key[1], &p->val[0], &p->val[1]})
+            if (b->p)
+                hipFree(b->p);
     for (auto& kind : c->userWc)
         for (auto& b : kind)
             if (b.p)
@@ -4688,6 +4738,22 @@ int query_mark(deme_ctx* c, const std::vector<uint32_t>& ids, size_t nMarks) {
     }
     return DEME_OK;
 }
+// the tables a row's owners are looked up in (row_owners); s2e and o2e stay null: the inspectors work in owner slots
+QueryTables query_tables(const deme_ctx* c) {
+    QueryTables t{};
+    t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
+    t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
+    return t;
+}
+// The force threshold of the inspectors: what every one of them refuses of it (the text goes to msg), and the square the kernels
+// compare with (row_force_counted).
+bool threshold_refused(char (&msg)[320], const char* who, float thr) {
+    if (std::isfinite(thr) && thr >= 0.f)
+        return false;
+    snprintf(msg, sizeof msg, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    return true;
+}
+inline double threshold_sq(float thr) { return (double)thr * (double)thr; }
 // one context's selection: the hit count in nHit, the hits (and records) left in the context's scratch; passes: count read-backs
 // made.  bk: the books of a slab, null for a single context; who: the entry point, for the message.
 int query_select(deme_ctx* c, const SlabBooksDev* bk, const char* who, int withRecords, uint32_t& nHit, uint32_t& passes) {
@@ -4695,10 +4761,8 @@ int query_select(deme_ctx* c, const SlabBooksDev* bk, const char* who, int withR
     const size_t n = c->haveList ? (size_t)c->nContacts : 0;
     if (!n)
         return DEME_OK;
-    QueryTables t{};
-    t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
+    QueryTables t = query_tables(c);
     t.s2e = c->dp.s2e, t.o2e = c->dp.o2e;
-    t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
     size_t want = 256;  // rows of scratch a first query starts with
     for (int pass = 0;; pass++) {
         if (ensure(c, c->qHits, want * sizeof(QueryHit)) || (withRecords && ensure(c, c->qRecs, want * 48)))
@@ -4825,8 +4889,9 @@ int contact_inspect_refused(deme_ctx* c, const char* who, const void* out, int r
         return fail(c, DEME_ERR_INVALID, "%s: null output", who);
     if (region < -1 || region >= (int)c->regionFn.size())
         return fail(c, DEME_ERR_INVALID, "unknown inspection region %d", region);
-    if (!std::isfinite(thr) || thr < 0.f)
-        return fail(c, DEME_ERR_INVALID, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    char msg[320];
+    if (threshold_refused(msg, who, thr))
+        return fail(c, DEME_ERR_INVALID, "%s", msg);
     if (int rc = records_refused(c))
         return rc;
     return DEME_OK;
@@ -4855,11 +4920,9 @@ int contact_inspect_launch(deme_ctx* c, int region, float thr, bool perOwner, Co
     }
     ContactSumArgs a{};
     a.n = (uint32_t)n, a.nSlots = (uint32_t)nO, a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
-    a.t.spheres = c->spheres.as<SphereRec>(), a.t.tris = c->tris.as<TriRec>(), a.t.anal = c->anal.as<AnalObj>();
-    a.t.nSpheres = c->nSpheres, a.t.nTri = c->nTri, a.t.nAnal = c->nAnal, a.t.nOwners = c->nOwners;
-    a.owners = c->owners.as<OwnerRec>(), a.mask = c->ciMask.as<float>();
+    a.t = query_tables(c), a.owners = c->owners.as<OwnerRec>(), a.mask = c->ciMask.as<float>();
     a.force = c->rec[0].as<float>(), a.cpA = c->rec[2].as<float>(), a.cpB = c->rec[3].as<float>();
-    a.thr2 = (double)thr * (double)thr;
+    a.thr2 = threshold_sq(thr);
     a.partial = c->ciPartial.as<ContactSums>(), a.counts = c->ciCounts.as<uint32_t>();
     if (perOwner) {
         HIPCK(hipMemsetAsync(c->ciCounts.p, 0, std::max<size_t>(nO, 1) * 4, c->stream));
@@ -4923,9 +4986,9 @@ namespace {
 int tri_loads_args_refused(char (&msg)[320], const char* who, float thr, uint32_t firstTri, uint32_t nTris, uint32_t nTri, const void* force,
                            const void* contacts) {
     msg[0] = 0;
-    if (!std::isfinite(thr) || thr < 0.f)
-        snprintf(msg, sizeof msg, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
-    else if ((uint64_t)firstTri + nTris > nTri)
+    if (threshold_refused(msg, who, thr))
+        return DEME_ERR_INVALID;
+    if ((uint64_t)firstTri + nTris > nTri)
         snprintf(msg, sizeof msg, "%s: triangles [%u, %llu) were asked for; the scene has %u", who, firstTri,
                  (unsigned long long)firstTri + nTris, nTri);
     else if (nTris && !force && !contacts)
@@ -4936,45 +4999,33 @@ int tri_loads_args_refused(char (&msg)[320], const char* who, float thr, uint32_
 // tlCount.  Nothing the step reads is written.
 int tri_loads_launch(deme_ctx* c, float thr) {
     const size_t n = c->haveList ? (size_t)c->nContacts : 0, nT = c->nTri;
-    const unsigned grid = grid_for(std::max<size_t>(n, 1), TRI_LOADS_BLOCK_ROWS);
     if (ensure(c, c->tlForce, nT * 24) || ensure(c, c->tlCount, nT * 4))
         return c->lastStatus;
     HIPCK(hipMemsetAsync(c->tlForce.p, 0, nT * 24, c->stream));
     HIPCK(hipMemsetAsync(c->tlCount.p, 0, nT * 4, c->stream));
     if (!n)
         return DEME_OK;
-    for (int k = 0; k < 2; k++)
-        if (ensure(c, c->tlTri[k], n * 4) || ensure(c, c->tlRow[k], n * 4))
-            return c->lastStatus;
-    if (ensure(c, c->tlPartial, (size_t)grid * 2 * sizeof(TriPartial)))
-        return c->lastStatus;
+    if (int rc = seg_reserve(c, c->tlPairs, n))
+        return rc;
     TriSelectArgs a{};
     a.n = (uint32_t)n, a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
     a.spheres = c->spheres.as<SphereRec>(), a.owners = c->owners.as<OwnerRec>();
     a.nSpheres = c->nSpheres, a.nOwners = c->nOwners, a.nTri = c->nTri;
-    a.force = c->rec[0].as<float>(), a.thr2 = (double)thr * (double)thr;
-    a.tri = c->tlTri[0].as<uint32_t>(), a.row = c->tlRow[0].as<uint32_t>();
+    a.force = c->rec[0].as<float>(), a.thr2 = threshold_sq(thr);
+    a.tri = c->tlPairs.key[0].as<uint32_t>(), a.row = c->tlPairs.val[0].as<uint32_t>();
     {
         ScopedTimer t(c, "tri_loads_select", true);
         hipLaunchKernelGGL(k_tri_select, dim3(grid_for(n)), dim3(256), 0, c->stream, a);
     }
-    // (the key nTri of the uncounted rows takes part: one value more than the triangles)
-    const unsigned bits = bits_for((uint64_t)nT + 1, 32);
     {
         ScopedTimer t(c, "tri_loads_sort", true);
-        if (int rc = with_temp(c, c->tlTmp, [&](void* tmp, size_t& bytes) {
-                return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->tlTri[0].as<uint32_t>(), c->tlTri[1].as<uint32_t>(),
-                                                              c->tlRow[0].as<uint32_t>(), c->tlRow[1].as<uint32_t>(), n, n, 0, bits,
-                                                              DEME_SORT_OWN_FROM_RECORDS, c->stream);
-            }))
+        if (int rc = seg_sort(c, c->tlPairs, n, nT))
             return rc;
     }
     ScopedTimer t(c, "tri_loads_sums", true);
-    hipLaunchKernelGGL(k_tri_seg_sums, dim3(grid), dim3(256), 0, c->stream, (uint32_t)n, (uint32_t)nT, c->tlTri[1].as<uint32_t>(),
-                       c->tlRow[1].as<uint32_t>(), c->rec[0].as<float>(), c->tlForce.as<double>(), c->tlCount.as<uint32_t>(),
-                       c->tlPartial.as<TriPartial>());
-    hipLaunchKernelGGL(k_tri_seg_final, dim3(1), dim3(256), 0, c->stream, 2u * grid, (uint32_t)nT, c->tlPartial.as<TriPartial>(),
-                       c->tlForce.as<double>(), c->tlCount.as<uint32_t>());
+    if (int rc = seg_sums<TRI_LANES>(c, c->tlPairs, n, nT, TriTerm{c->tlPairs.val[1].as<uint32_t>(), c->rec[0].as<float>()},
+                                     TriOut{c->tlForce.as<double>(), c->tlCount.as<uint32_t>()}))
+        return rc;
     HIPCK(hipGetLastError());
     return DEME_OK;
 }
@@ -4989,7 +5040,7 @@ int tri_loads_fetch(deme_ctx* c, uint32_t firstTri, uint32_t nTris, double* forc
 }
 }  // namespace
 
-unsigned deme_tri_loads_block_rows(void) { return TRI_LOADS_BLOCK_ROWS; }
+unsigned deme_tri_loads_block_rows(void) { return SEG_BLOCK_ROWS; }
 
 int deme_inspect_tri_loads(deme_ctx* c, float thr, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts) {
     if (int rc = check_ready(c))
@@ -5040,8 +5091,8 @@ int fields_args_refused(char (&msg)[320], const char* who, const DemeFieldGrid* 
         snprintf(msg, sizeof msg, "%s: the grid has %u x %u x %u cells; at most %llu in all", who, g->n[0], g->n[1], g->n[2], (unsigned long long)cap);
     else if (!out->clumps && !out->mass && !out->volume && !out->momentum && !out->kinetic && !out->sides && !out->virial)
         snprintf(msg, sizeof msg, "%s: null output (every column)", who);
-    else if (!std::isfinite(thr) || thr < 0.f)
-        snprintf(msg, sizeof msg, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    else
+        threshold_refused(msg, who, thr);
     return msg[0] ? DEME_ERR_INVALID : DEME_OK;
 }
 inline bool fields_ask_owner(const DemeFieldColumns* o) { return o->clumps || o->mass || o->volume || o->momentum || o->kinetic; }
@@ -5089,71 +5140,47 @@ int fields_launch(deme_ctx* c, const DemeFieldGrid* g, float thr, bool askOwner,
     }
     if (!nO)
         return DEME_OK;
-    const unsigned gridO = grid_for(nO, FIELDS_BLOCK_ROWS), gridS = grid_for(std::max<size_t>(2 * n, 1), FIELDS_BLOCK_ROWS);
-    if (ensure(c, c->fiCellOf, nO * 4) ||
-        ensure(c, c->fiPartial, std::max((size_t)gridO * 2 * sizeof(FieldOwnerPartial), (size_t)gridS * 2 * sizeof(FieldSidePartial))))
+    if (ensure(c, c->fiCellOf, nO * 4) || seg_reserve(c, c->fiOwn, nO) || (n && seg_reserve(c, c->fiSide, 2 * n)))
         return c->lastStatus;
-    for (int k = 0; k < 2; k++)
-        if (ensure(c, c->fiOwnKey[k], nO * 4) || ensure(c, c->fiOwnVal[k], nO * 4) ||
-            (n && (ensure(c, c->fiSideKey[k], 2 * n * 4) || ensure(c, c->fiSideVal[k], 2 * n * 4))))
-            return c->lastStatus;
-    QueryTables t{};
-    t.spheres = c->spheres.as<SphereRec>(), t.tris = c->tris.as<TriRec>(), t.anal = c->anal.as<AnalObj>();
-    t.nSpheres = c->nSpheres, t.nTri = c->nTri, t.nAnal = c->nAnal, t.nOwners = c->nOwners;
+    const QueryTables t = query_tables(c);
     {
         ScopedTimer tm(c, "fields_cells", true);
         FieldCellArgs a{};
         a.nSlots = (uint32_t)nO, a.nClumps = c->nOwnerClumps, a.nCells = (uint32_t)nC, a.owners = c->owners.as<OwnerRec>();
         for (int k = 0; k < 3; k++)
             a.g.origin[k] = g->origin[k], a.g.cell[k] = g->cell[k], a.g.n[k] = g->n[k];
-        a.cellOf = c->fiCellOf.as<uint32_t>(), a.key = c->fiOwnKey[0].as<uint32_t>(), a.slot = c->fiOwnVal[0].as<uint32_t>();
+        a.cellOf = c->fiCellOf.as<uint32_t>(), a.key = c->fiOwn.key[0].as<uint32_t>(), a.slot = c->fiOwn.val[0].as<uint32_t>();
         hipLaunchKernelGGL(k_field_cells, dim3(grid_for(nO)), dim3(256), 0, c->stream, c->dp, a);
         if (n) {
             FieldSideSelectArgs s{};
             s.n = (uint32_t)n, s.nSlots = (uint32_t)nO, s.nCells = (uint32_t)nC, s.keys = c->keysSorted[c->keysCur].as<uint64_t>(), s.t = t;
-            s.cellOf = c->fiCellOf.as<uint32_t>(), s.force = c->rec[0].as<float>(), s.thr2 = (double)thr * (double)thr;
-            s.key = c->fiSideKey[0].as<uint32_t>(), s.val = c->fiSideVal[0].as<uint32_t>();
+            s.cellOf = c->fiCellOf.as<uint32_t>(), s.force = c->rec[0].as<float>(), s.thr2 = threshold_sq(thr);
+            s.key = c->fiSide.key[0].as<uint32_t>(), s.val = c->fiSide.val[0].as<uint32_t>();
             hipLaunchKernelGGL(k_field_side_select, dim3(grid_for(n)), dim3(256), 0, c->stream, s);
         }
     }
-    // (the key nCells of the uncounted entries takes part: one value more than the cells)
-    const unsigned bits = bits_for((uint64_t)nC + 1, 32);
     {
         ScopedTimer tm(c, "fields_sort", true);
         if (askOwner)
-            if (int rc = with_temp(c, c->fiTmp, [&](void* tmp, size_t& bytes) {
-                    return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->fiOwnKey[0].as<uint32_t>(), c->fiOwnKey[1].as<uint32_t>(),
-                                                                  c->fiOwnVal[0].as<uint32_t>(), c->fiOwnVal[1].as<uint32_t>(), nO, nO, 0, bits,
-                                                                  DEME_SORT_OWN_FROM_RECORDS, c->stream);
-                }))
+            if (int rc = seg_sort(c, c->fiOwn, nO, nC))
                 return rc;
         if (n)
-            if (int rc = with_temp(c, c->fiTmp, [&](void* tmp, size_t& bytes) {
-                    return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->fiSideKey[0].as<uint32_t>(), c->fiSideKey[1].as<uint32_t>(),
-                                                                  c->fiSideVal[0].as<uint32_t>(), c->fiSideVal[1].as<uint32_t>(), 2 * n, 2 * n, 0,
-                                                                  bits, DEME_SORT_OWN_FROM_RECORDS, c->stream);
-                }))
+            if (int rc = seg_sort(c, c->fiSide, 2 * n, nC))
                 return rc;
     }
     ScopedTimer tm(c, "fields_sums", true);
     if (askOwner) {
-        hipLaunchKernelGGL(k_field_owner_sums, dim3(gridO), dim3(256), 0, c->stream, (uint32_t)nO, (uint32_t)nC, c->fiOwnKey[1].as<uint32_t>(),
-                           c->fiOwnVal[1].as<uint32_t>(), c->owners.as<OwnerRec>(), c->massProps.as<float4>(),
-                           c->haveVolumes ? c->volumes.as<float>() : (const float*)nullptr, o.own, c->fiPartial.as<FieldOwnerPartial>());
-        hipLaunchKernelGGL(k_field_owner_final, dim3(1), dim3(256), 0, c->stream, 2u * gridO, (uint32_t)nC, c->fiPartial.as<FieldOwnerPartial>(),
-                           o.own);
+        const FieldOwnerTerm term{c->fiOwn.val[1].as<uint32_t>(), c->owners.as<OwnerRec>(), c->massProps.as<float4>(),
+                                  c->haveVolumes ? c->volumes.as<float>() : (const float*)nullptr};
+        if (int rc = seg_sums<FIELD_OWNER_LANES>(c, c->fiOwn, nO, nC, term, o.own))
+            return rc;
     }
-    if (n) {
-        FieldSideSumArgs s{};
-        s.n = (uint32_t)(2 * n), s.nCells = (uint32_t)nC, s.nSlots = (uint32_t)nO;
-        s.keys = c->fiSideKey[1].as<uint32_t>(), s.vals = c->fiSideVal[1].as<uint32_t>(), s.list = c->keysSorted[c->keysCur].as<uint64_t>();
-        s.t = t, s.owners = c->owners.as<OwnerRec>();
-        s.force = c->rec[0].as<float>(), s.cpA = c->rec[2].as<float>(), s.cpB = c->rec[3].as<float>();
-        s.out = o.side, s.partial = c->fiPartial.as<FieldSidePartial>();
-        hipLaunchKernelGGL(k_field_side_sums, dim3(gridS), dim3(256), 0, c->stream, s);
-        hipLaunchKernelGGL(k_field_side_final, dim3(1), dim3(256), 0, c->stream, 2u * gridS, (uint32_t)nC, c->fiPartial.as<FieldSidePartial>(),
-                           o.side);
-    }
+    FieldSideTerm side{};  // (no launch for an empty list: seg_sums)
+    side.nSlots = (uint32_t)nO, side.vals = c->fiSide.val[1].as<uint32_t>(), side.list = c->keysSorted[c->keysCur].as<uint64_t>();
+    side.t = t, side.owners = c->owners.as<OwnerRec>();
+    side.force = c->rec[0].as<float>(), side.cpA = c->rec[2].as<float>(), side.cpB = c->rec[3].as<float>();
+    if (int rc = seg_sums<FIELD_SIDE_LANES>(c, c->fiSide, 2 * n, nC, side, o.side))
+        return rc;
     HIPCK(hipGetLastError());
     return DEME_OK;
 }
@@ -5202,7 +5229,7 @@ int fields_fetch(deme_ctx* c, size_t nC, FieldHost& h) {
 }
 }  // namespace
 
-unsigned deme_fields_block_rows(void) { return FIELDS_BLOCK_ROWS; }
+unsigned deme_fields_block_rows(void) { return SEG_BLOCK_ROWS; }
 
 int deme_inspect_fields(deme_ctx* c, const DemeFieldGrid* grid, float thr, const DemeFieldColumns* out) {
     if (int rc = check_ready(c))
@@ -5238,8 +5265,8 @@ int clusters_args_refused(char (&msg)[320], const char* who, const void* summary
         snprintf(msg, sizeof msg, "%s: null output (summary, labels, table and nClusters)", who);
     else if (labels && labelCap < nOwners)
         snprintf(msg, sizeof msg, "%s: buffer too small: need %zu labels", who, nOwners);
-    else if (!std::isfinite(thr) || thr < 0.f)
-        snprintf(msg, sizeof msg, "%s: the force threshold is %g; it must be finite and >= 0", who, (double)thr);
+    else
+        threshold_refused(msg, who, thr);
     return msg[0] ? DEME_ERR_INVALID : DEME_OK;
 }
 // what one context refuses of a question whose arguments are in order (the text is left in c->err)
@@ -5268,14 +5295,14 @@ unsigned clusters_grid_stats(deme_ctx* c) { return grid_for(std::max<size_t>(std
 // that owns the clump with the smaller global id.  Nothing the step reads is written.
 int clusters_launch(deme_ctx* c, float thr, const uint32_t* ownerGid, ClusterAsk ask) {
     const size_t nO = c->nOwners, n = c->haveList ? (size_t)c->nContacts : 0;
-    const unsigned gridL = clusters_grid_link(c), gridS = clusters_grid_stats(c), gridT = grid_for(std::max<size_t>(nO, 1), FIELDS_BLOCK_ROWS);
+    const unsigned gridL = clusters_grid_link(c), gridS = clusters_grid_stats(c);
     if (ensure(c, c->clCtl, sizeof(ClusterCtl)) || ensure(c, c->clParent, nO * 4) || ensure(c, c->clLabel, nO * 4) || ensure(c, c->clSize, nO * 4) ||
         ensure(c, c->clStat, (((size_t)gridL * 4 + 7) & ~(size_t)7) + ((size_t)gridS + 1) * sizeof(ClusterStat)))
         return c->lastStatus;
-    if (ask.rows && (ensure(c, c->clFlag, nO * 4) || ensure(c, c->clRank, nO * 4) || ensure(c, c->clKey[0], nO * 4) || ensure(c, c->clVal[0], nO * 4)))
+    // (the sorted half of the pairs is reserved only when the table is asked)
+    if (ask.rows && (ensure(c, c->clFlag, nO * 4) || ensure(c, c->clRank, nO * 4) || seg_reserve(c, c->clSel, nO, ask.table)))
         return c->lastStatus;
-    if (ask.table && (ensure(c, c->clKey[1], nO * 4) || ensure(c, c->clVal[1], nO * 4) || ensure(c, c->clTable, nO * CLUSTER_ROW_BYTES) ||
-                      ensure(c, c->clPartial, (size_t)gridT * 2 * sizeof(ClusterPartial))))
+    if (ask.table && ensure(c, c->clTable, nO * CLUSTER_ROW_BYTES))
         return c->lastStatus;
     HIPCK(hipMemsetAsync(c->clCtl.p, 0, sizeof(ClusterCtl), c->stream));
     ClusterCtl* ctl = c->clCtl.as<ClusterCtl>();
@@ -5289,9 +5316,7 @@ int clusters_launch(deme_ctx* c, float thr, const uint32_t* ownerGid, ClusterAsk
         if (nO && n) {
             ClusterLinkArgs a{};
             a.n = (uint32_t)n, a.nSlots = (uint32_t)nO, a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
-            a.t.spheres = c->spheres.as<SphereRec>(), a.t.tris = c->tris.as<TriRec>(), a.t.anal = c->anal.as<AnalObj>();
-            a.t.nSpheres = c->nSpheres, a.t.nTri = c->nTri, a.t.nAnal = c->nAnal, a.t.nOwners = c->nOwners;
-            a.owners = owners, a.o2e = c->dp.o2e, a.force = c->rec[0].as<float>(), a.thr2 = (double)thr * (double)thr;
+            a.t = query_tables(c), a.owners = owners, a.o2e = c->dp.o2e, a.force = c->rec[0].as<float>(), a.thr2 = threshold_sq(thr);
             a.parent = parent, a.ownerGid = ownerGid, a.edgePartial = c->clStat.as<uint32_t>(), a.ctl = ctl;
             hipLaunchKernelGGL(k_cluster_link, dim3(gridL), dim3(256), 0, c->stream, a);
         }
@@ -5311,26 +5336,18 @@ int clusters_launch(deme_ctx* c, float thr, const uint32_t* ownerGid, ClusterAsk
     {
         ScopedTimer tm(c, "clusters_sort", true);
         hipLaunchKernelGGL(k_cluster_select, dim3(grid_for(nO)), dim3(256), 0, c->stream, (uint32_t)nO, owners, c->dp.o2e, label, size,
-                           c->clKey[0].as<uint32_t>(), c->clVal[0].as<uint32_t>(), c->clFlag.as<uint32_t>());
+                           c->clSel.key[0].as<uint32_t>(), c->clSel.val[0].as<uint32_t>(), c->clFlag.as<uint32_t>());
         hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(DEME_SCAN_T), 0, c->stream, c->clFlag.as<uint32_t>(), c->clRank.as<uint32_t>(), (uint32_t)nO,
                            &ctl->nRows);
-        if (ask.table) {
-            // (the key nO of the uncounted owners takes part: one value more than the labels)
-            const unsigned bits = bits_for((uint64_t)nO + 1, 32);
-            if (int rc = with_temp(c, c->clTmp, [&](void* tmp, size_t& bytes) {
-                    return deme_radix_sort<DemeRadixCfg<8>, true>(tmp, bytes, c->clKey[0].as<uint32_t>(), c->clKey[1].as<uint32_t>(),
-                                                                  c->clVal[0].as<uint32_t>(), c->clVal[1].as<uint32_t>(), nO, nO, 0, bits,
-                                                                  DEME_SORT_OWN_FROM_RECORDS, c->stream);
-                }))
+        if (ask.table)
+            if (int rc = seg_sort(c, c->clSel, nO, nO))
                 return rc;
-        }
     }
     if (ask.table) {
         ScopedTimer tm(c, "clusters_sums", true);
-        const ClusterTableOut o = clusters_table(c, nO);
-        hipLaunchKernelGGL(k_cluster_sums, dim3(gridT), dim3(256), 0, c->stream, c->dp, (uint32_t)nO, c->clKey[1].as<uint32_t>(),
-                           c->clVal[1].as<uint32_t>(), owners, c->massProps.as<float4>(), o, c->clPartial.as<ClusterPartial>());
-        hipLaunchKernelGGL(k_cluster_final, dim3(1), dim3(256), 0, c->stream, 2u * gridT, (uint32_t)nO, c->clPartial.as<ClusterPartial>(), o);
+        if (int rc = seg_sums<CLUSTER_LANES>(c, c->clSel, nO, nO, ClusterTerm{c->dp, c->clSel.val[1].as<uint32_t>(), owners, c->massProps.as<float4>()},
+                                             clusters_table(c, nO)))
+            return rc;
     }
     HIPCK(hipGetLastError());
     return DEME_OK;
@@ -5586,6 +5603,60 @@ int deme_sort_pairs_u32(int device, const uint32_t* keys, const uint32_t* vals, 
 int deme_sort_keys_u64(int device, const uint64_t* keys, size_t n, unsigned beginBit, unsigned endBit, int forceOwn, uint64_t* keysOut) {
     return sort_host_arrays<DemeRadixCfg<8>, false>(device, keys, nullptr, n, beginBit, endBit, forceOwn ? 0 : DEME_SORT_OWN_FROM_KEYS64, keysOut,
                                                     nullptr);
+}
+
+// ---- the segmented sum alone, on host arrays (tests/test_seg_sum.py) ------------------------------
+namespace {
+struct CtxHeld {  // a context of one call's own (its stream, segPartial), destroyed however the call ends
+    deme_ctx* c = nullptr;
+    ~CtxHeld() {
+        if (c)
+            deme_ctx_destroy(c);
+    }
+};
+template <int L>
+int seg_sum_host_arrays(int device, const uint32_t* keys, const double* terms, size_t n, uint32_t nKeys, double* sums, uint32_t* counts) {
+    CtxHeld h;
+    if (int rc = deme_ctx_create(device, &h.c))
+        return rc;
+    deme_ctx* c = h.c;
+    SortScratch s;
+    uint32_t *dKeys = s.room<uint32_t>(n), *dCounts = s.room<uint32_t>(nKeys);
+    double *dTerms = s.room<double>(n * L), *dSums = s.room<double>((size_t)nKeys * L);
+    if (!dKeys || !dCounts || !dTerms || !dSums)
+        return DEME_ERR_HIP;
+    if (n) {
+        HIPCK(hipMemcpyAsync(dKeys, keys, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpyAsync(dTerms, terms, n * L * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCK(hipMemsetAsync(dSums, 0, (size_t)nKeys * L * 8, c->stream));
+    HIPCK(hipMemsetAsync(dCounts, 0, (size_t)nKeys * 4, c->stream));
+    if (int rc = seg_sums<L>(c, dKeys, n, nKeys, SegArrayTerm<L>{dTerms}, SegArrayOut<L>{dSums, dCounts}))
+        return rc;
+    HIPCK(hipGetLastError());
+    if (nKeys) {
+        HIPCK(hipMemcpyAsync(sums, dSums, (size_t)nKeys * L * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipMemcpyAsync(counts, dCounts, (size_t)nKeys * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+}  // namespace
+
+int deme_seg_sum_f64(int device, const uint32_t* keys, const double* terms, size_t n, unsigned lanes, uint32_t nKeys, double* sums,
+                     uint32_t* counts) {
+    if (n >= ((size_t)1 << 31) || (n && (!keys || !terms)) || (nKeys && (!sums || !counts)))
+        return DEME_ERR_INVALID;
+    for (size_t i = 1; i < n; i++)  // (this input comes from outside: the kernels rely on the ascent)
+        if (keys[i] < keys[i - 1])
+            return DEME_ERR_INVALID;
+    switch (lanes) {  // the instantiated widths: the inspectors'
+        case TRI_LANES: return seg_sum_host_arrays<TRI_LANES>(device, keys, terms, n, nKeys, sums, counts);
+        case CLUSTER_LANES: return seg_sum_host_arrays<CLUSTER_LANES>(device, keys, terms, n, nKeys, sums, counts);
+        case FIELD_SIDE_LANES: return seg_sum_host_arrays<FIELD_SIDE_LANES>(device, keys, terms, n, nKeys, sums, counts);
+        case FIELD_OWNER_LANES: return seg_sum_host_arrays<FIELD_OWNER_LANES>(device, keys, terms, n, nKeys, sums, counts);
+    }
+    return DEME_ERR_INVALID;
 }
 
 #include "deme_decomp.inc"

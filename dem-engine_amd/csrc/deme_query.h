@@ -38,6 +38,31 @@ struct QueryTables {  // what a row's owners are looked up in (counts: a row tha
     uint32_t nSpheres, nTri, nAnal, nOwners;
 };
 
+// the owner slots of both sides of a row (0xFFFFFFFF: the row names something beyond the tables)
+__device__ inline void row_owners(const QueryTables& t, uint64_t k, uint32_t& oA, uint32_t& oB) {
+    const uint32_t cls = key_class(k), sa = key_a(k), sb = key_b(k);
+    oA = oB = 0xFFFFFFFFu;
+    if (sa < t.nSpheres)
+        oA = load_sphere(t.spheres, sa).owner;
+    if (cls == DEME_KEY_CLASS_SS) {
+        if (sb < t.nSpheres)
+            oB = load_sphere(t.spheres, sb).owner;
+    } else if (cls == DEME_KEY_CLASS_SM) {
+        if (sb < t.nTri)
+            oB = t.tris[sb].owner;
+    } else if (sb < t.nAnal) {
+        oB = t.anal[sb].owner;
+    }
+}
+
+// The threshold test of the inspectors: row i's recorded force (record 0, 3 floats a row) as doubles, and whether its squared norm
+// reaches thr2 = (double)thr^2.  >=, so a row with a NaN force is never counted.
+__device__ inline bool row_force_counted(const float* __restrict__ force, uint32_t i, double thr2, double& fx, double& fy, double& fz) {
+    const size_t r = (size_t)i * 3;
+    fx = force[r], fy = force[r + 1], fz = force[r + 2];
+    return fx * fx + fy * fy + fz * fz >= thr2;
+}
+
 __global__ __launch_bounds__(256) void k_query_mark(uint32_t n, const uint32_t* __restrict__ ids, uint8_t* __restrict__ mark) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)
@@ -98,18 +123,8 @@ __global__ __launch_bounds__(256) void k_query_select(uint32_t n, const uint64_t
     if (i < n) {
         const uint64_t k = keys[i];
         const uint32_t cls = key_class(k), a = key_a(k), b = key_b(k);
-        uint32_t oA = 0xFFFFFFFFu, oB = 0xFFFFFFFFu;
-        if (a < t.nSpheres)
-            oA = load_sphere(t.spheres, a).owner;
-        if (cls == DEME_KEY_CLASS_SS) {
-            if (b < t.nSpheres)
-                oB = load_sphere(t.spheres, b).owner;
-        } else if (cls == DEME_KEY_CLASS_SM) {
-            if (b < t.nTri)
-                oB = t.tris[b].owner;
-        } else if (b < t.nAnal) {
-            oB = t.anal[b].owner;
-        }
+        uint32_t oA, oB;
+        row_owners(t, k, oA, oB);
         if (oA < t.nOwners && oB < t.nOwners) {
             if (t.o2e)  // (a context with ghosts keeps the order it is uploaded in: null on a slab today)
                 oA = t.o2e[oA], oB = t.o2e[oB];

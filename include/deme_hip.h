@@ -348,6 +348,13 @@ int deme_sort_pairs_u32(int device, const uint32_t* keys, const uint32_t* vals, 
                         uint32_t* keysOut, uint32_t* valsOut);
 int deme_sort_keys_u64(int device, const uint64_t* keys, size_t n, unsigned beginBit, unsigned endBit, int forceOwn, uint64_t* keysOut);
 unsigned deme_sort_tile_keys(void);
+/* The inspectors' segmented sum alone, on host arrays (tests): fp64 sums and counts by runs of equal keys, every addition in the
+ * fixed order of deme_seg_sum.h.  keys: n ascending keys, the entries with a key >= nKeys (uncounted) behind the counted ones;
+ * terms: n x lanes, row-major; sums: nKeys x lanes; counts: nKeys.  A key without a run gives zeros.  No sort inside.
+ * Refused with DEME_ERR_INVALID: lanes other than an inspector's width (3, 4, 9, 11); n >= 2^31; a null array while n (keys,
+ * terms) or nKeys (sums, counts) is not zero; keys that do not ascend. */
+int deme_seg_sum_f64(int device, const uint32_t* keys, const double* terms, size_t n, unsigned lanes, uint32_t nKeys, double* sums,
+                     uint32_t* counts);
 /* per-sphere world position (LBF-shifted frame, as kT sees it) and inflated radius */
 int deme_download_sphere_geometry(deme_ctx* ctx, double* X, double* Y, double* Z, float* R, size_t cap);
 

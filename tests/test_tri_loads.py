@@ -240,7 +240,7 @@ def flat_bed(pkg, cells, n):
 @pytest.mark.gpu
 @pytest.mark.parametrize("cells,n", [(1, 40000), (20, 80000)])
 def test_more_partials_than_one_round_of_the_last_pass_takes(pkg, cells, n):
-    """k_tri_seg_final takes the blocks' partials 256 at a round and carries the open run from one round to the next: that needs
+    """k_seg_final (deme_seg_sum.h) takes the blocks' partials 256 at a round and carries the open run from one round to the next: that needs
     more than 128 blocks with counted rows, more than 32 768 counted rows.  A bed a few layers high, asked with thr = 0:
     on the two-triangle plate both runs span dozens of blocks and the second one crosses from the first round into the second; on
     the 20 x 20 plate the rounds meet in the middle of the list, among runs of a few dozen rows.  The same list at the shell's
