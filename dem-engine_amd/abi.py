@@ -251,6 +251,12 @@ def load_library():
         "deme_multi_inspect_contact_counts": [_P, C.c_char_p, C.c_float, _P, C.c_size_t],
         "deme_inspect_tri_loads": [_P, C.c_float, C.c_uint32, C.c_uint32, _P, _P],
         "deme_multi_inspect_tri_loads": [_P, C.c_float, C.c_uint32, C.c_uint32, _P, _P],
+        "deme_tri_wear_enable": [_P, C.c_int], "deme_multi_tri_wear_enable": [_P, C.c_int],
+        "deme_tri_wear_sample": [_P, C.c_float, C.c_double, C.POINTER(C.c_int)],
+        "deme_multi_tri_wear_sample": [_P, C.c_float, C.c_double, C.POINTER(C.c_int)],
+        "deme_tri_wear_read": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.POINTER(C.c_double)],
+        "deme_multi_tri_wear_read": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.POINTER(C.c_double)],
+        "deme_tri_wear_reset": [_P], "deme_multi_tri_wear_reset": [_P],
         "deme_inspect_fields": [_P, C.POINTER(DemeFieldGrid), C.c_float, C.POINTER(DemeFieldColumns)],
         "deme_multi_inspect_fields": [_P, C.POINTER(DemeFieldGrid), C.c_float, C.POINTER(DemeFieldColumns)],
         "deme_inspect_clusters": [_P, C.c_float, C.POINTER(DemeClusterSummary), _P, C.c_size_t, C.POINTER(DemeClusterColumns), C.c_size_t,
@@ -516,9 +522,57 @@ def device_count():
     return int(n.value)
 
 
-class Multi:
+TRI_WEAR_COLUMNS = ("impulse", "normalImpulse", "slidingWork", "shearWork", "rows")  # in the order of deme_tri_wear_read
+
+
+class _TriWear:
+    """deme_tri_wear_* / deme_multi_tri_wear_*: the calls Context and Multi share (self._wear_prefix names the family)"""
+
+    def _wear(self, what):
+        name = self._wear_prefix + what
+        return getattr(self.lib, name), name
+
+    def tri_wear_enable(self, on=True):
+        """56 bytes of accumulators per mesh triangle on the device, cleared; enabling twice keeps the sums, on=False frees them"""
+        fn, name = self._wear("enable")
+        self._ck(fn(self.h, int(bool(on))), name)
+
+    def tri_wear_sample(self, force_threshold=1e-12, weight=0.0):
+        """one sample of weight `weight` seconds added to every triangle's sums, enqueued behind the steps (no host wait).  False:
+        the list is a seed and nothing was added -- carry the weight to the next sample."""
+        fn, name = self._wear("sample")
+        got = C.c_int(-1)
+        self._ck(fn(self.h, float(force_threshold), float(weight), C.byref(got)), name)
+        return bool(got.value)
+
+    def tri_wear_read(self, first=0, count=None, columns=TRI_WEAR_COLUMNS):
+        """the sums of the triangles [first, first + count) (count None: to the last one): a dict of the asked columns -- impulse
+        (n, 3), normalImpulse, slidingWork, shearWork (n,) float64, rows (n,) uint64 -- and sampledTime, the sum of the weights"""
+        fn, name = self._wear("read")
+        unknown = [k for k in columns if k not in TRI_WEAR_COLUMNS]
+        if unknown:
+            raise ValueError(f"{name}: unknown columns {unknown}; known: {TRI_WEAR_COLUMNS}")
+        if count is None:
+            if getattr(self, "n_tri", None) is None:
+                raise ValueError(f"{name}: count is needed (this object has not seen the scene's triangle count)")
+            count = self.n_tri - int(first)
+        n = max(int(count), 0)
+        out = {k: np.zeros((n, 3) if k == "impulse" else n, np.uint64 if k == "rows" else np.float64) for k in columns}
+        t = C.c_double(0.0)
+        self._ck(fn(self.h, int(first), int(count), *[_ptr(out.get(k)) for k in TRI_WEAR_COLUMNS], C.byref(t)), name)
+        out["sampledTime"] = float(t.value)
+        return out
+
+    def tri_wear_reset(self):
+        """exact zeros in every accumulator, sampledTime 0"""
+        fn, name = self._wear("reset")
+        self._ck(fn(self.h), name)
+
+
+class Multi(_TriWear):
     """deme_multi_*: one process, several devices -- what the C++ shell's DEMSolver(nGPUs / device ids) opens.  One device with
     several slabs exercises every step of it on a single GPU (the slabs exchange by sends to self)."""
+    _wear_prefix = "deme_multi_tri_wear_"
 
     def __init__(self, devices=(0,)):
         self.lib = load_library()
@@ -981,8 +1035,9 @@ def jit_probe(src, wildcard_names=(), prerequisites="", owner_wildcards=(), geo_
     return rc == 0, log.value.decode(errors="replace")
 
 
-class Context:
+class Context(_TriWear):
     """One GPU context (mirrors what kT+dT own in the reference)."""
+    _wear_prefix = "deme_tri_wear_"
 
     def __init__(self, device=0):
         self.lib = load_library()

@@ -1839,6 +1839,114 @@ int deme_multi_inspect_tri_loads(deme_multi* m, float thr, uint32_t firstTri, ui
     return DEME_OK;
 }
 
+// ---- mesh wear of a decomposed run (deme_tri_wear.h) -------------------------------------------------------------------------------------
+// Every slab samples its own list on its own device into its own accumulators; a pair is counted by the one slab that owns sphere
+// A's clump (ghost rows are not counted).  A sample is all or nothing: the slabs are asked first, and if any slab's list is a seed
+// -- the step after a migration -- no slab adds anything.  A read adds the slabs' arrays in slab order.
+namespace {
+bool multi_wear_enabled(deme_multi* m) {
+    bool on = true;
+    multi_slabs(m, [&](const SlabRef& r) -> int {
+        on = on && r.c->twOn;
+        return DEME_OK;
+    });
+    return on;
+}
+}  // namespace
+
+int deme_multi_tri_wear_enable(deme_multi* m, int on) {
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    if (on)
+        if (int rc = multi_pairs_once_refused(m, "deme_multi_tri_wear_enable"))
+            return rc;
+    return multi_slabs(m, [&](const SlabRef& r) -> int { return deme_tri_wear_enable(r.c, on); });
+}
+
+int deme_multi_tri_wear_reset(deme_multi* m) {
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    if (!multi_wear_enabled(m))
+        return mfail(m, DEME_ERR_INVALID, "deme_multi_tri_wear_reset: mesh wear accumulation is not enabled (deme_multi_tri_wear_enable)");
+    return multi_slabs(m, [&](const SlabRef& r) -> int { return deme_tri_wear_reset(r.c); });
+}
+
+int deme_multi_tri_wear_sample(deme_multi* m, float thr, double weight, int* sampled) {
+    const char* who = "deme_multi_tri_wear_sample";
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    char msg[320];
+    if (int rc = tri_wear_sample_refused(msg, who, multi_wear_enabled(m), thr, weight))
+        return mfail(m, rc, "%s", msg);
+    if (int rc = multi_pairs_once_refused(m, who))
+        return rc;
+    bool seed = false;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+            if (!r.c->record)
+                return mfail(m, DEME_ERR_INVALID, "%s: contact recording is off (deme_set_record_contacts)", who);
+            seed = seed || tri_wear_list_unevaluated(r.c);
+            return DEME_OK;
+        }))
+        return rc;
+    if (sampled)
+        *sampled = 0;
+    if (seed)
+        return DEME_OK;
+    if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int { return tri_wear_launch(r.c, thr, weight); }))
+        return rc;
+    if (sampled)
+        *sampled = 1;
+    return DEME_OK;
+}
+
+int deme_multi_tri_wear_read(deme_multi* m, uint32_t firstTri, uint32_t nTris, double* impulse, double* normalImpulse, double* slidingWork,
+                             double* shearWork, uint64_t* rows, double* sampledTime) {
+    const char* who = "deme_multi_tri_wear_read";
+    if (!m || !m->plan)
+        return DEME_ERR_INVALID;
+    const SlabRef head = multi_slab(m, 0);
+    char msg[320];
+    const bool any = impulse || normalImpulse || slidingWork || shearWork || rows || sampledTime;
+    if (int rc = tri_wear_read_refused(msg, who, multi_wear_enabled(m), firstTri, nTris, head.c ? head.c->nTri : 0u, any))
+        return mfail(m, rc, "%s", msg);
+    if (int rc = multi_pairs_once_refused(m, who))
+        return rc;
+    if (nTris) {
+        if (int rc = deme_multi_sync(m))
+            return rc;
+        void* dst[5] = {impulse, normalImpulse, slidingWork, shearWork, rows};
+        const bool want[5] = {impulse != nullptr, normalImpulse != nullptr, slidingWork != nullptr, shearWork != nullptr, rows != nullptr};
+        std::vector<char> h;
+        std::vector<double> sum[4];
+        std::vector<uint64_t> sumRows(rows ? nTris : 0, 0ull);
+        for (int j = 0; j < 4; j++)
+            sum[j].assign(want[j] ? WEAR_COL_BYTES[j] / 8 * nTris : 0, 0.0);
+        if (int rc = multi_slabs(m, [&](const SlabRef& r) -> int {
+                if (int rc = tri_wear_fetch(r.c, firstTri, nTris, want, h))
+                    return rc;
+                m->qHostBytes += h.size();
+                for (int j = 0; j < 4; j++) {
+                    const double* col = (const double*)tri_wear_column(h, nTris, want, j);
+                    for (size_t i = 0; i < sum[j].size(); i++)
+                        sum[j][i] += col[i];
+                }
+                const uint64_t* col = (const uint64_t*)tri_wear_column(h, nTris, want, 4);
+                for (size_t i = 0; i < sumRows.size(); i++)
+                    sumRows[i] += col[i];
+                return DEME_OK;
+            }))
+            return rc;
+        for (int j = 0; j < 4; j++)
+            if (want[j])
+                memcpy(dst[j], sum[j].data(), sum[j].size() * 8);
+        if (rows)
+            memcpy(rows, sumRows.data(), sumRows.size() * 8);
+    }
+    if (sampledTime)
+        *sampledTime = head.c ? head.c->twTime : 0.0;
+    return DEME_OK;
+}
+
 // ---- per-cell sums on a grid of a decomposed run (deme_fields.h) ------------------------------------------------------------------------
 // Every slab holds its clumps in the world frame and counts its own clumps only (ghost copies never count), so a clump, and every
 // side it carries, is counted by one slab.  All slabs' passes are enqueued first, each on its device, then the host takes the asked

@@ -50,6 +50,7 @@ using DemeRadixCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim
 #include "deme_query.h"
 #include "deme_contact_inspect.h"
 #include "deme_tri_loads.h"
+#include "deme_tri_wear.h"
 #include "deme_fields.h"
 #include "deme_clusters.h"
 #include "deme_sort.h"
@@ -149,6 +150,12 @@ struct deme_ctx {
     // triangle loads (deme_tri_loads.h): the (triangle, row) pairs before and after the sort, the sums and counts per triangle
     SegPairs tlPairs;
     DevBuf tlForce, tlCount;
+    // mesh wear (deme_tri_wear.h): six doubles and one uint64_t count per triangle, summed from sample to sample on the device; the
+    // pairs of a sample are tlPairs (the same select on the same stream).  twTri: the triangles the arrays were cleared for
+    bool twOn = false;
+    DevBuf twAcc, twRows, twOut;  // (twOut: the asked columns packed for deme_tri_wear_read)
+    uint32_t twTri = 0;
+    double twTime = 0;  // the sum of the weights of the samples taken
     // field inspector (deme_fields.h): the cell of every owner slot, the (cell, slot) and (cell, side) pairs before and after their
     // sorts, the columns of every cell
     SegPairs fiOwn, fiSide;
@@ -1810,7 +1817,7 @@ void deme_ctx_destroy(deme_ctx* c) {
                      &c->scanTmp, &c->sortTmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->rec[3], &c->stage, &c->sharedIds,
                      &c->sharedBuf, &c->keysMid, &c->ownersSnap, &c->rsMark, &c->rsKeys[0], &c->rsKeys[1], &c->rsRuns,
                      &c->rsUKeys, &c->rsIdx, &c->rsOldR, &c->rsUses, &c->rsRemap, &c->qMark, &c->qHits, &c->qRecs, &c->qCtr, &c->qState,
-                     &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut, &c->segTmp, &c->segPartial, &c->tlForce, &c->tlCount,
+                     &c->ciMask, &c->ciCounts, &c->ciPartial, &c->ciOut, &c->segTmp, &c->segPartial, &c->tlForce, &c->tlCount, &c->twAcc, &c->twRows, &c->twOut,
                      &c->fiCellOf, &c->fiOut, &c->clParent, &c->clLabel, &c->clSize, &c->clFlag, &c->clRank, &c->clStat, &c->clTable,
                      &c->clCtl, &c->clPairs};
     for (DevBuf* b : all)
@@ -2028,6 +2035,10 @@ static int sphere_scratch_for_counts(deme_ctx* c, size_t nS) {
     return DEME_OK;
 }
 
+namespace {
+int tri_wear_clear(deme_ctx* c);  // (mesh wear, below: a scene with another triangle count clears the sums)
+}
+
 int deme_upload_scene(deme_ctx* c, const DemeScene* s) {
     if (!c || !s)
         return DEME_ERR_INVALID;
@@ -2184,6 +2195,9 @@ int deme_upload_scene(deme_ctx* c, const DemeScene* s) {
     if (int rc = grow_incidence_arena(c, std::max<size_t>(8 * nS, 4096)))
         return rc;
     c->nTri = s->nTri;  // before the contact arena: its mesh work-list buffers exist only when triangles do
+    if (c->twOn && c->twTri != c->nTri)  // the wear sums of another mesh mean nothing for this one: cleared at the new size
+        if (int rc = tri_wear_clear(c))
+            return rc;
     if (int rc = grow_contact_arena(c, std::max<size_t>(6 * nS, 4096)))
         return rc;
     // triangles
@@ -5063,6 +5077,190 @@ int deme_inspect_tri_loads(deme_ctx* c, float thr, uint32_t firstTri, uint32_t n
         memcpy(force, hf.data(), hf.size() * 8);
     if (contacts)
         memcpy(contacts, hn.data(), hn.size() * 4);
+    return DEME_OK;
+}
+
+// ---- mesh wear: impulse and sliding work per triangle, summed over the samples of a run (deme_tri_wear.h) -----------------------------
+namespace {
+// the accumulators of nTri triangles, cleared (enqueued; the context keeps them until the feature is disabled)
+int tri_wear_clear(deme_ctx* c) {
+    const size_t nT = c->nTri;
+    if (ensure(c, c->twAcc, nT * WEAR_LANES * 8) || ensure(c, c->twRows, nT * 8))
+        return c->lastStatus;
+    HIPCK(hipMemsetAsync(c->twAcc.p, 0, std::max<size_t>(nT * WEAR_LANES * 8, 1), c->stream));
+    HIPCK(hipMemsetAsync(c->twRows.p, 0, std::max<size_t>(nT * 8, 1), c->stream));
+    c->twTri = c->nTri, c->twTime = 0;
+    return DEME_OK;
+}
+// what deme_tri_wear_sample refuses before it looks at the list, in the order it does (the text goes to msg)
+int tri_wear_sample_refused(char (&msg)[320], const char* who, bool enabled, float thr, double weight) {
+    msg[0] = 0;
+    if (!enabled)
+        snprintf(msg, sizeof msg, "%s: mesh wear accumulation is not enabled (deme_tri_wear_enable)", who);
+    else if (threshold_refused(msg, who, thr))
+        ;
+    else if (!(std::isfinite(weight) && weight >= 0.0))
+        snprintf(msg, sizeof msg, "%s: the weight is %g; it must be finite and >= 0", who, weight);
+    return msg[0] ? DEME_ERR_INVALID : DEME_OK;
+}
+// A list the force pass has not evaluated: a seed, or one that was just put in force -- by deme_detect_contacts, or by an
+// asynchronous detection whose cycle ended with the call -- so that the records in memory are those of the list before it and say
+// nothing of its rows.  (conValid: the contributions in memory are those of the list in force.)
+inline bool tri_wear_list_unevaluated(const deme_ctx* c) { return c->haveList && (c->seeded || !c->conValid); }
+// The passes of one sample of one context, enqueued on its stream behind the steps already there; no read-back, no wait.  n is the
+// host's count of the list; the key nTri of the rows that do not count does the compaction (deme_tri_loads.h).  Nothing the step
+// reads is written.
+int tri_wear_launch(deme_ctx* c, float thr, double weight) {
+    const size_t n = c->haveList ? (size_t)c->nContacts : 0, nT = c->nTri;
+    c->twTime += weight;
+    if (!n || !nT)
+        return DEME_OK;
+    if (int rc = seg_reserve(c, c->tlPairs, n))
+        return rc;
+    TriSelectArgs a{};
+    a.n = (uint32_t)n, a.keys = c->keysSorted[c->keysCur].as<uint64_t>();
+    a.spheres = c->spheres.as<SphereRec>(), a.owners = c->owners.as<OwnerRec>();
+    a.nSpheres = c->nSpheres, a.nOwners = c->nOwners, a.nTri = c->nTri;
+    a.force = c->rec[0].as<float>(), a.thr2 = threshold_sq(thr);
+    a.tri = c->tlPairs.key[0].as<uint32_t>(), a.row = c->tlPairs.val[0].as<uint32_t>();
+    {
+        ScopedTimer t(c, "tri_wear_select", true);
+        hipLaunchKernelGGL(k_tri_select, dim3(grid_for(n)), dim3(256), 0, c->stream, a);
+    }
+    {
+        ScopedTimer t(c, "tri_wear_sort", true);
+        if (int rc = seg_sort(c, c->tlPairs, n, nT))
+            return rc;
+    }
+    ScopedTimer t(c, "tri_wear_sums", true);
+    const WearTerm term{c->tlPairs.val[1].as<uint32_t>(), (uint32_t)n, a.keys, query_tables(c), a.owners, c->rec[0].as<float>(),
+                        c->rec[2].as<float>(), c->rec[3].as<float>(), weight};
+    if (int rc = seg_sums<WEAR_LANES>(c, c->tlPairs, n, nT, term, WearOut{c->twAcc.as<double>(), c->twRows.as<uint64_t>()}))
+        return rc;
+    HIPCK(hipGetLastError());
+    return DEME_OK;
+}
+// what deme_tri_wear_read refuses of its arguments, in the order it does (the text goes to msg)
+int tri_wear_read_refused(char (&msg)[320], const char* who, bool enabled, uint32_t firstTri, uint32_t nTris, uint32_t nTri, bool anyOutput) {
+    msg[0] = 0;
+    if (!enabled)
+        snprintf(msg, sizeof msg, "%s: mesh wear accumulation is not enabled (deme_tri_wear_enable)", who);
+    else if ((uint64_t)firstTri + nTris > nTri)
+        snprintf(msg, sizeof msg, "%s: triangles [%u, %llu) were asked for; the scene has %u", who, firstTri,
+                 (unsigned long long)firstTri + nTris, nTri);
+    else if (nTris && !anyOutput)
+        snprintf(msg, sizeof msg, "%s: null output (every column and sampledTime)", who);
+    return msg[0] ? DEME_ERR_INVALID : DEME_OK;
+}
+// The columns of deme_tri_wear_read in its order -- impulse, normalImpulse, slidingWork, shearWork, rows -- and their bytes a triangle
+constexpr size_t WEAR_COL_BYTES[5] = {24, 8, 8, 8, 8};
+inline size_t tri_wear_bytes(uint32_t nTris, const bool (&want)[5]) {
+    size_t b = 0;
+    for (int j = 0; j < 5; j++)
+        b += want[j] ? WEAR_COL_BYTES[j] * nTris : 0;
+    return b;
+}
+// The asked columns of the asked range, packed one behind the other on the device (k_tri_wear_gather) and copied to h in one piece:
+// tri_wear_bytes of them, no more.  Waits for the stream.
+int tri_wear_fetch(deme_ctx* c, uint32_t firstTri, uint32_t nTris, const bool (&want)[5], std::vector<char>& h) {
+    const size_t bytes = tri_wear_bytes(nTris, want);
+    h.resize(bytes);
+    if (!bytes)
+        return DEME_OK;
+    if (int rc = ensure(c, c->twOut, bytes))
+        return rc;
+    char* at[5];
+    size_t off = 0;
+    for (int j = 0; j < 5; j++) {
+        at[j] = want[j] ? (char*)c->twOut.p + off : nullptr;
+        off += want[j] ? WEAR_COL_BYTES[j] * nTris : 0;
+    }
+    const WearGatherArgs a{firstTri, nTris, c->twAcc.as<double>(), c->twRows.as<uint64_t>(), (double*)at[0], (double*)at[1], (double*)at[2],
+                           (double*)at[3], (uint64_t*)at[4]};
+    hipLaunchKernelGGL(k_tri_wear_gather, dim3(grid_for(nTris)), dim3(256), 0, c->stream, a);
+    HIPCK(hipMemcpyAsync(h.data(), c->twOut.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return DEME_OK;
+}
+// column j of a fetched block
+inline const char* tri_wear_column(const std::vector<char>& h, uint32_t nTris, const bool (&want)[5], int j) {
+    size_t off = 0;
+    for (int k = 0; k < j; k++)
+        off += want[k] ? WEAR_COL_BYTES[k] * nTris : 0;
+    return h.data() + off;
+}
+}  // namespace
+
+int deme_tri_wear_enable(deme_ctx* c, int on) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (!on) {
+        if (c->twOn)
+            HIPCK(hipStreamSynchronize(c->stream));  // (a sample may still be adding)
+        for (DevBuf* b : {&c->twAcc, &c->twRows, &c->twOut})
+            if (b->p) {
+                HIPCK(hipFree(b->p));
+                *b = DevBuf{};
+            }
+        c->twOn = false, c->twTri = 0, c->twTime = 0;
+        return DEME_OK;
+    }
+    if (c->twOn)
+        return DEME_OK;  // (the sums stay)
+    if (int rc = tri_wear_clear(c))
+        return rc;
+    c->twOn = true;
+    return DEME_OK;
+}
+
+int deme_tri_wear_reset(deme_ctx* c) {
+    if (int rc = check_ready(c))
+        return rc;
+    if (!c->twOn)
+        return fail(c, DEME_ERR_INVALID, "deme_tri_wear_reset: mesh wear accumulation is not enabled (deme_tri_wear_enable)");
+    return tri_wear_clear(c);
+}
+
+int deme_tri_wear_sample(deme_ctx* c, float thr, double weight, int* sampled) {
+    if (int rc = check_ready(c))
+        return rc;
+    char msg[320];
+    if (int rc = tri_wear_sample_refused(msg, "deme_tri_wear_sample", c->twOn, thr, weight))
+        return fail(c, rc, "%s", msg);
+    if (!c->record)
+        return fail(c, DEME_ERR_INVALID, "deme_tri_wear_sample: contact recording is off (deme_set_record_contacts)");
+    if (sampled)
+        *sampled = 0;
+    if (tri_wear_list_unevaluated(c))  // the caller carries the weight to its next sample
+        return DEME_OK;
+    if (int rc = tri_wear_launch(c, thr, weight))
+        return rc;
+    if (sampled)
+        *sampled = 1;
+    return DEME_OK;
+}
+
+int deme_tri_wear_read(deme_ctx* c, uint32_t firstTri, uint32_t nTris, double* impulse, double* normalImpulse, double* slidingWork,
+                       double* shearWork, uint64_t* rows, double* sampledTime) {
+    if (int rc = check_ready(c))
+        return rc;
+    char msg[320];
+    const bool any = impulse || normalImpulse || slidingWork || shearWork || rows || sampledTime;
+    if (int rc = tri_wear_read_refused(msg, "deme_tri_wear_read", c->twOn, firstTri, nTris, c->nTri, any))
+        return fail(c, rc, "%s", msg);
+    if (nTris) {
+        void* dst[5] = {impulse, normalImpulse, slidingWork, shearWork, rows};
+        const bool want[5] = {impulse != nullptr, normalImpulse != nullptr, slidingWork != nullptr, shearWork != nullptr, rows != nullptr};
+        std::vector<char> h;  // (the caller's arrays are written once the call cannot fail any more)
+        if (int rc = tri_wear_fetch(c, firstTri, nTris, want, h))
+            return rc;
+        c->qHostBytes += h.size();
+        for (int j = 0; j < 5; j++)
+            if (want[j])
+                memcpy(dst[j], tri_wear_column(h, nTris, want, j), WEAR_COL_BYTES[j] * nTris);
+    }
+    if (sampledTime)
+        *sampledTime = c->twTime;
     return DEME_OK;
 }
 

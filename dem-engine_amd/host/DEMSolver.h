@@ -1111,12 +1111,65 @@ class DEMSolver {
             for (size_t k = 0; k < total_f; k++)
                 o << count[k] << std::endl;
         }
+        if (m_mesh_wear) {  // EnableMeshWearAccumulation: the sums of the run so far
+            const std::vector<double> w = mesh_wear(0, (uint32_t)total_f);
+            if (!m_mesh_face_loads)
+                o << "\n\nCELL_DATA " << total_f;
+            o << "\nVECTORS wear_impulse float" << std::endl;
+            for (size_t j = 0; j < total_f; j++)
+                o << (float)w[6 * j] << " " << (float)w[6 * j + 1] << " " << (float)w[6 * j + 2] << std::endl;
+            for (int lane : {4, 5}) {
+                o << "\nSCALARS " << (lane == 4 ? "wear_sliding_work" : "wear_shear_work") << " float 1\nLOOKUP_TABLE default" << std::endl;
+                for (size_t j = 0; j < total_f; j++)
+                    o << (float)w[6 * j + lane] << std::endl;
+            }
+        }
         flush(outfilename, o);
     }
     /// Not in the reference: WriteMeshFile appends CELL_DATA with the contact force on every face (world frame), the contact
     /// pressure |F . n| / A and the number of contacts (deme_inspect_tri_loads, summed on the device).  Call before Initialize():
     /// it turns contact recording on.  Off by default, and the file is then what it always was.
     void EnableMeshFaceLoadOutput(bool on = true) { m_mesh_face_loads = on; }
+    /// Not in the reference: contact impulse, normal impulse, Archard sliding work |Fn| |v_slide| dt and shear work of every mesh
+    /// face, summed over the run on the device (deme_tri_wear_*; the statement is in include/deme_hip.h).  Call before Initialize():
+    /// it turns contact recording on.  DoDynamics then cuts its chunks at the multiples of everyNSteps of the global step count and
+    /// takes a sample after each -- the rectangle rule with the sample at the end of its interval, weight everyNSteps * h.  A sample
+    /// that found a list not evaluated yet (the step after a migration or a renewed order) carries its weight to the next one.  The
+    /// trackers' GetMeshFace... getters and WriteMeshFile (CELL_DATA wear_impulse, wear_sliding_work, wear_shear_work) read the sums.
+    void EnableMeshWearAccumulation(unsigned everyNSteps = 10, float force_thres = DEME_TINY_FLOAT_HOST) {
+        if (everyNSteps == 0)
+            throw std::runtime_error("EnableMeshWearAccumulation: everyNSteps must be at least 1");
+        if (m_initialized)
+            throw std::runtime_error("EnableMeshWearAccumulation must be called before Initialize()");
+        m_mesh_wear = true, m_wear_every = everyNSteps, m_wear_thres = force_thres;
+    }
+    /// every face's sums and the sampled time back to zero
+    void ResetMeshWear() {
+        wear_required("ResetMeshWear");
+        if (m_multi)
+            mcheck(deme_multi_tri_wear_reset(m_multi));
+        else
+            check(deme_tri_wear_reset(m_ctx));
+        m_wear_base.clear(), m_wear_base_time = 0, m_wear_carry = 0;
+    }
+    /// the time the samples taken so far stand for, seconds: the sum of their weights
+    double GetMeshWearSampledTime() {
+        wear_required("GetMeshWearSampledTime");
+        double t = 0;
+        wear_device_read(0, 0, nullptr, &t);
+        return t + m_wear_base_time;
+    }
+    /// six doubles a face of the faces [first, first + n) of the scene's numbering -- impulse xyz, normal impulse, sliding work, shear
+    /// work -- as they stand now
+    std::vector<double> mesh_wear(uint32_t first, uint32_t n) {
+        wear_required("the mesh wear getters");
+        std::vector<double> lanes(6 * (size_t)n);
+        wear_device_read(first, n, lanes.data(), nullptr);
+        if (!m_wear_base.empty())
+            for (size_t i = 0; i < lanes.size(); i++)
+                lanes[i] += m_wear_base[6 * (size_t)first + i];
+        return lanes;
+    }
     /// |F . n| / A of a face with world nodes a, b, c under the force F (3 doubles); 0 for a degenerate face
     static float face_pressure(const float3& a, const float3& b, const float3& c, const double* F) {
         const double ux = (double)b.x - a.x, uy = (double)b.y - a.y, uz = (double)b.z - a.z;
@@ -2487,6 +2540,65 @@ class DEMSolver {
     unsigned int m_out_content = QUAT | ABSV;                                      // API.h:1418
     unsigned int m_cnt_out_content = OWNER | GEO_ID | FORCE | CNT_POINT | CNT_WILDCARD;  // API.h:1422-1424
     bool m_mesh_face_loads = false;  // EnableMeshFaceLoadOutput
+    // EnableMeshWearAccumulation: a sample every m_wear_every steps of the global count; the weight of samples that found an
+    // unevaluated list; what the slabs of a decomposed run had summed before the scene was cut anew (their contexts go with them)
+    bool m_mesh_wear = false;
+    unsigned m_wear_every = 10;
+    float m_wear_thres = DEME_TINY_FLOAT_HOST;
+    uint64_t m_steps_done = 0;
+    double m_wear_carry = 0, m_wear_base_time = 0;
+    std::vector<double> m_wear_base;  // 6 a face, or empty
+    size_t m_wear_faces = 0;          // the faces the accumulators were enabled for
+    void wear_required(const char* call) const {
+        if (!m_mesh_wear || !m_initialized)
+            throw std::runtime_error(std::string(call) + " needs EnableMeshWearAccumulation() before Initialize()");
+    }
+    // the device's sums of faces [first, first + n), six a face, and the time they stand for (either may be null)
+    void wear_device_read(uint32_t first, uint32_t n, double* lanes, double* time) {
+        std::vector<double> imp(3 * (size_t)n), nrm(n), sld(n), shr(n);
+        double* const p[4] = {lanes ? imp.data() : nullptr, lanes ? nrm.data() : nullptr, lanes ? sld.data() : nullptr, lanes ? shr.data() : nullptr};
+        if (m_multi)
+            mcheck(deme_multi_tri_wear_read(m_multi, first, n, p[0], p[1], p[2], p[3], nullptr, time));
+        else
+            check(deme_tri_wear_read(m_ctx, first, n, p[0], p[1], p[2], p[3], nullptr, time));
+        for (size_t i = 0; lanes && i < n; i++) {
+            lanes[6 * i] = imp[3 * i], lanes[6 * i + 1] = imp[3 * i + 1], lanes[6 * i + 2] = imp[3 * i + 2];
+            lanes[6 * i + 3] = nrm[i], lanes[6 * i + 4] = sld[i], lanes[6 * i + 5] = shr[i];
+        }
+    }
+    size_t total_faces() const {
+        size_t n = 0;
+        for (auto& m : m_meshes)
+            n += m->faces.size();
+        return n;
+    }
+    void wear_enable() {
+        if (m_multi)
+            mcheck(deme_multi_tri_wear_enable(m_multi, 1));
+        else
+            check(deme_tri_wear_enable(m_ctx, 1));
+    }
+    // the slabs of a decomposed run are about to be dropped: their sums move to the host (the same faces only: a scene whose mesh
+    // changed starts anew, as deme_upload_scene does on one context)
+    void wear_stash(size_t facesBefore) {
+        double t = 0;
+        std::vector<double> now(6 * facesBefore);
+        wear_device_read(0, (uint32_t)facesBefore, now.data(), &t);
+        if (m_wear_base.size() != now.size())
+            m_wear_base.assign(now.size(), 0.0);
+        for (size_t i = 0; i < now.size(); i++)
+            m_wear_base[i] += now[i];
+        m_wear_base_time += t;
+    }
+    void wear_sample() {
+        const double w = (double)m_wear_every * (double)m_h + m_wear_carry;
+        int sampled = 0;
+        if (m_multi)
+            mcheck(deme_multi_tri_wear_sample(m_multi, m_wear_thres, w, &sampled));
+        else
+            check(deme_tri_wear_sample(m_ctx, m_wear_thres, w, &sampled));
+        m_wear_carry = sampled ? 0.0 : w;
+    }
     bool m_all_volumes = false;      // every clump template declared a volume (DEMFieldInspector asks the volume column then)
     struct Keep {  // scene arrays the writers need after Initialize
         std::vector<uint32_t> sphOwner, objOwner, triOwner;
@@ -2722,14 +2834,19 @@ class DEMSolver {
             uint32_t k = n;
             if (m_multi && m_replan_every)
                 k = (uint32_t)std::min<uint64_t>(n, m_replan_every - std::min<uint64_t>(m_steps_since_replan, m_replan_every - 1u));
+            if (m_mesh_wear)  // a chunk ends where a sample is due
+                k = (uint32_t)std::min<uint64_t>(k, m_wear_every - m_steps_done % m_wear_every);
             if (m_multi)
                 mcheck(deme_multi_step(m_multi, k));
             else
                 check(deme_step(m_ctx, k));
             m_time += (double)k * (double)m_h;
             m_steps_since_replan += k;
+            m_steps_done += k;
             state_changed();
             n -= k;
+            if (m_mesh_wear && m_steps_done % m_wear_every == 0)
+                wear_sample();
             if (m_multi && m_replan_every && m_steps_since_replan >= m_replan_every)
                 ReplanSlabs();  // (after the steps: what a script queued for its next step -- AddAcc -- has been consumed by then)
         }
@@ -3074,8 +3191,11 @@ class DEMSolver {
                 freeOwner = freeOwner || !(m_family_flags[fam[o]] & (DEME_FAMILY_FIXED | DEME_FAMILY_PRESCRIBED));
             uint32_t built = 0;
             deme_multi_num_slabs(m_multi, &built);
-            if (built)  // a scene re-upload (UpdateClumps, ResortClumps): the old slabs go, the new scene is cut anew
+            if (built) {  // a scene re-upload (UpdateClumps, ResortClumps): the old slabs go, the new scene is cut anew
+                if (m_mesh_wear && m_initialized)
+                    wear_stash(m_wear_faces);
                 mcheck(deme_multi_reset(m_multi));
+            }
             mcheck(deme_multi_build(m_multi, &p, &s, m_slabs_per_device, -1, (double)m_slab_halo, freeOwner ? DEME_DECOMP_SHARED_FREE : 0u, -1,
                                     p.forceModel == DEME_FORCE_HERTZIAN ? 7u : 0u));
             mcheck(deme_multi_set_migration(m_multi, m_migrate_every));
@@ -3183,8 +3303,14 @@ class DEMSolver {
             snprintf(nm, sizeof nm, "%04d", (int)i);
             m_keep.templateName[m_templates[i]->mark] = m_templates[i]->m_name.empty() ? std::string(nm) : m_templates[i]->m_name;
         }
-        if ((m_cnt_out_content & (FORCE | CNT_POINT | NORMAL | TORQUE)) || m_mesh_face_loads)
+        if ((m_cnt_out_content & (FORCE | CNT_POINT | NORMAL | TORQUE)) || m_mesh_face_loads || m_mesh_wear)
             each_ctx([&](deme_ctx* c) { return deme_set_record_contacts(c, 1); });
+        if (m_mesh_wear) {
+            if (m_wear_base.size() != 6 * total_faces())  // (another mesh: the sums of the old one mean nothing for it)
+                m_wear_base.clear(), m_wear_base_time = 0;
+            m_wear_faces = total_faces();
+            wear_enable();
+        }
         // restart: existing sphere-sphere contacts of the batches (geometry ids are batch-relative, Structs.h:857)
         {
             std::vector<uint32_t> a, b;
@@ -3774,6 +3900,52 @@ class DEMTracker {
             out[i] = DEMSolver::face_pressure(nodes[(size_t)faces[i][0]], nodes[(size_t)faces[i][1]], nodes[(size_t)faces[i][2]], &f[3 * i]);
         return out;
     }
+    /// Not in the reference: the sums DEMSolver::EnableMeshWearAccumulation keeps for every face of the tracked mesh, one entry per
+    /// face in the mesh's face order.  The impulse ON the face, N s, world frame
+    std::vector<float3> GetMeshFaceImpulses() {
+        const std::vector<double> w = face_wear("GetMeshFaceImpulses");
+        std::vector<float3> out(w.size() / 6);
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = make_float3((float)w[6 * i], (float)w[6 * i + 1], (float)w[6 * i + 2]);
+        return out;
+    }
+    /// ... the normal impulse INT |Fn| dt, N s
+    std::vector<double> GetMeshFaceNormalImpulses() { return wear_lane("GetMeshFaceNormalImpulses", 3); }
+    /// ... the Archard sliding work INT |Fn| |v_slide| dt, J: normal load times sliding distance
+    std::vector<double> GetMeshFaceSlidingWork() { return wear_lane("GetMeshFaceSlidingWork", 4); }
+    /// ... the shear work INT |Ft| |v_slide| dt, J
+    std::vector<double> GetMeshFaceShearWork() { return wear_lane("GetMeshFaceShearWork", 5); }
+    /// ... Archard's wear depth k/H * slidingWork / A per face, m (k_over_H in 1/Pa; 0 for a degenerate face)
+    std::vector<double> GetMeshFaceWearDepth(double k_over_H) {
+        std::vector<double> out = wear_lane("GetMeshFaceWearDepth", 4);
+        const std::vector<double> A = face_areas();
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = A[i] > 0.0 ? k_over_H * out[i] / A[i] : 0.0;
+        return out;
+    }
+    /// ... and the mean contact pressure over the sampled time, normalImpulse / (A * sampledTime), Pa (0 when no time was sampled)
+    std::vector<double> GetMeshFaceMeanPressure() {
+        std::vector<double> out = wear_lane("GetMeshFaceMeanPressure", 3);
+        const std::vector<double> A = face_areas();
+        const double t = m_sys->GetMeshWearSampledTime();
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = A[i] > 0.0 && t > 0.0 ? out[i] / (A[i] * t) : 0.0;
+        return out;
+    }
+    /// the area of every face of the tracked mesh from its owner-local nodes as they stand (a rigid motion keeps it), m^2
+    std::vector<double> face_areas() {
+        const auto& v = GetMesh()->vertices;
+        const auto& faces = GetMesh()->faces;
+        std::vector<double> A(faces.size());
+        for (size_t i = 0; i < A.size(); i++) {
+            const float3 &a = v[(size_t)faces[i][0]], &b = v[(size_t)faces[i][1]], &c = v[(size_t)faces[i][2]];
+            const double ux = (double)b.x - a.x, uy = (double)b.y - a.y, uz = (double)b.z - a.z;
+            const double vx = (double)c.x - a.x, vy = (double)c.y - a.y, vz = (double)c.z - a.z;
+            const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+            A[i] = 0.5 * std::sqrt(nx * nx + ny * ny + nz * nz);
+        }
+        return A;
+    }
     /// the mesh a mesh tracker follows (AuxClasses.h:310)
     std::shared_ptr<DEMMeshConnected>& GetMesh() {
         if (m_kind != 2)
@@ -3819,6 +3991,17 @@ class DEMTracker {
         std::vector<double> f(3 * GetMesh()->faces.size());
         m_sys->tri_loads((uint32_t)m_sys->mesh_first_face(m_index), (uint32_t)(f.size() / 3), f.data(), nullptr);
         return f;
+    }
+    std::vector<double> face_wear(const char* call) {  // 6 doubles per face of the tracked mesh
+        mesh_only(call);
+        return m_sys->mesh_wear((uint32_t)m_sys->mesh_first_face(m_index), (uint32_t)GetMesh()->faces.size());
+    }
+    std::vector<double> wear_lane(const char* call, int lane) {
+        const std::vector<double> w = face_wear(call);
+        std::vector<double> out(w.size() / 6);
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = w[6 * i + lane];
+        return out;
     }
     std::vector<bodyID_t> all_owner_ids() const { return first_owner_ids(m_n); }
     std::vector<bodyID_t> first_owner_ids(size_t n) const {  // the first min(n, all) tracked owners

@@ -545,6 +545,59 @@ int deme_inspect_contact_counts(deme_ctx* ctx, int regionId, float forceThreshol
 int deme_inspect_tri_loads(deme_ctx* ctx, float forceThreshold, uint32_t firstTri, uint32_t nTris, double* force /* 3 per triangle, or NULL */,
                            uint32_t* contacts /* 1 per triangle, or NULL */);
 unsigned deme_tri_loads_block_rows(void);
+/* Mesh wear (no counterpart in the reference): contact impulse and sliding work per mesh triangle, summed over the samples of a run
+ * on the device -- the time integrals deme_inspect_tri_loads gives one instant of; Archard's law is V = k/H * INT |Fn| |v_slide| dt.
+ * The accumulators live on the device from sample to sample: a sample costs device passes only, no read-back and no host wait, and
+ * the numbers come to the host when deme_tri_wear_read asks.  Everything below is fp64 over the fp32 values as stored.
+ *   WHICH ROWS COUNT.  The rows are those deme_download_contacts / deme_download_contact_records give.  A row is COUNTED exactly as
+ *   deme_inspect_tri_loads counts it: its class is sphere-mesh (DEME_SPHERE_MESH_CONTACT); B is a triangle id < nTri; sphere A is <
+ *   nSpheres and A's owner is a valid slot and no ghost copy; (double)fx^2 + (double)fy^2 + (double)fz^2 >= (double)forceThreshold^2,
+ *   f the recorded force (record 0).
+ *   QUANTITIES OF A COUNTED ROW.  oA: the owner of sphere A; oB: the owner of triangle B.  R(q)v = v + 2w(u x v) + 2u x (u x v), u =
+ *   (qx, qy, qz): the rotation of deme_inspect_contacts, with the stored quaternion as it stands (not renormalised).
+ *     rA = R(qA) cpA, rB = R(qB) cpB                     (records 2 and 3)
+ *     wA = R(qA) (omgBarX, omgBarY, omgBarZ)_A, wB alike (the stored angular velocity is in the body frame)
+ *     vA = v_A + wA x rA, vB = v_B + wB x rB
+ *     u  = vA - vB            the velocity of the sphere's contact point relative to the face's
+ *     g  = -f                 the force ON the triangle, the sign of deme_inspect_tri_loads
+ *     N  = R(qB) ((n2 - n1) x (n3 - n1))   from the triangle's owner-local nodes as they stand (deme_update_tri_nodes may have moved them)
+ *     if N.N > 0:  nh = N / sqrt(N.N), Fn = g.nh, gt = g - Fn nh, ut = u - (u.nh) nh;  otherwise (a degenerate face) lanes 3 to 5 add 0
+ *   THE SIX LANES of a sample of weight w (seconds), each w times:
+ *     0..2  g_x, g_y, g_z     N s   the impulse on the face
+ *     3     |Fn|              N s   the normal impulse
+ *     4     |Fn| * |ut|       J     the Archard sliding work: normal load times sliding distance
+ *     5     |gt| * |ut|       J     the shear work
+ *   and a counted row adds 1 to the triangle's rows, a uint64_t.
+ *   WHICH STATE A SAMPLE PAIRS.  The state as it stands: the records of the last force pass with the owners' CURRENT records (velocity,
+ *   angular velocity, orientation) and the triangles' current nodes -- as deme_inspect_contacts pairs the records with the current
+ *   quaternion.  After deme_step(n) that is the force at the start of the last step with the state at its end.
+ *   ORDER OF ADDITIONS.  Within a triangle and a sample the terms are added in list order down the fixed tree of the segmented sum;
+ *   the sample's sum is then added once to the accumulator, by the one thread that finishes that triangle.  No floating-point
+ *   atomics: two runs of the same sequence of steps and samples give the same bits.
+ * deme_tri_wear_enable(on != 0) allocates and clears 56 bytes a triangle; enabling twice keeps the sums; on == 0 frees them.  It needs
+ * an uploaded scene; a scene without triangles is fine, and every call then does nothing.  A deme_upload_scene that changes nTri clears
+ * the accumulators and the sampled time at the new size; one that keeps nTri keeps them.
+ * deme_tri_wear_sample adds one sample and returns once its passes are enqueued on the context's stream, behind the steps already
+ * there: no host wait, and no bytes counted by deme_query_host_bytes.  Refused with DEME_ERR_INVALID and nothing changed, in this
+ * order: not enabled; a threshold that is negative or not finite; a weight that is negative or not finite; recording off (the
+ * message of deme_download_contact_records).  A list whose contacts have NOT BEEN EVALUATED is no error: a seeded list
+ * (deme_seed_contacts, or the engine's order was just renewed), or a list that was just put in force -- by deme_detect_contacts, or by
+ * an asynchronous detection (deme_set_async_detection) whose cycle ended with the last deme_step call -- while the records in memory
+ * are still those of the list before it.  The call then returns DEME_OK with *sampled = 0 and adds nothing; the caller carries the
+ * weight to its next sample.  Otherwise *sampled = 1 and the sampled time grows by the weight, also when the list or the mesh is
+ * empty.  sampled may be NULL.  A weight of 0 counts rows and adds zeros.
+ * deme_tri_wear_read waits for the stream and copies only the asked range [firstTri, firstTri + nTris) and the asked columns (any
+ * may be NULL): 24 / 8 / 8 / 8 / 8 bytes per asked triangle for impulse / normalImpulse / slidingWork / shearWork / rows, all added
+ * to deme_query_host_bytes.  sampledTime (one number: the sum of the weights since the last clear) comes from the host's own sum.
+ * nTris == 0 launches nothing.  Refused: not enabled; a range beyond the scene's triangles; every output NULL while nTris > 0.
+ * deme_tri_wear_reset clears the accumulators and the sampled time.
+ * Nothing the step reads is written: the list, the prescriptions and the step's buffers stay as they are, with an asynchronous
+ * detection too.  Event timers (deme_kernel_time_ms): "tri_wear_select", "tri_wear_sort", "tri_wear_sums". */
+int deme_tri_wear_enable(deme_ctx* ctx, int on);
+int deme_tri_wear_sample(deme_ctx* ctx, float forceThreshold, double weight, int* sampled /* or NULL */);
+int deme_tri_wear_read(deme_ctx* ctx, uint32_t firstTri, uint32_t nTris, double* impulse /* 3 per triangle */, double* normalImpulse,
+                       double* slidingWork, double* shearWork, uint64_t* rows, double* sampledTime /* one number: the sum of the weights */);
+int deme_tri_wear_reset(deme_ctx* ctx);
 /* Field inspector (no counterpart in the reference): per-cell sums on a regular grid -- what solid fraction, mean velocity, granular
  * temperature, contact stress and coordination are derived from, cell by cell -- summed on the device.
  *   GRID.  nCells = n[0] * n[1] * n[2]; the id of cell (ix, iy, iz) is ix + n[0] * (iy + n[1] * iz); every per-cell array is in that
@@ -912,6 +965,18 @@ int deme_multi_inspect_contact_counts(deme_multi* m, const char* regionCode, flo
  * (deme_halo_group_set_cross_contacts) would be refused too; no call of this interface puts a deme_multi into that mode today, so
  * that refusal cannot be met yet.  Bytes, added to deme_multi_query_host_bytes: 24 + 4 per asked triangle and slab. */
 int deme_multi_inspect_tri_loads(deme_multi* m, float forceThreshold, uint32_t firstTri, uint32_t nTris, double* force, uint32_t* contacts);
+/* deme_tri_wear_* for a decomposed run.  Every slab samples its own list on its own device into its own accumulators; since a row
+ * whose sphere belongs to a ghost copy is not counted, a pair is counted by the one slab that owns sphere A's clump.  A sample is all
+ * or nothing: if any slab's list is a seed -- the step after a migration -- no slab adds anything and *sampled = 0.  It waits for
+ * nothing.  _read waits for the run and adds the slabs' arrays in slab order; bytes per slab and asked triangle as
+ * deme_tri_wear_read, added to deme_multi_query_host_bytes.  The refusals of the single-context calls; _enable(on), _sample and _read
+ * are refused too while the run evaluates every cross-cut contact once (deme_halo_group_set_cross_contacts): the slab that does not
+ * evaluate a pair holds no record of it. */
+int deme_multi_tri_wear_enable(deme_multi* m, int on);
+int deme_multi_tri_wear_sample(deme_multi* m, float forceThreshold, double weight, int* sampled);
+int deme_multi_tri_wear_read(deme_multi* m, uint32_t firstTri, uint32_t nTris, double* impulse, double* normalImpulse, double* slidingWork,
+                             double* shearWork, uint64_t* rows, double* sampledTime);
+int deme_multi_tri_wear_reset(deme_multi* m);
 /* deme_inspect_fields for a decomposed run.  Every slab sums over its OWN clumps on its device (a clump is an own clump of one slab
  * only, ghost copies never count); all slabs' passes are enqueued first, then the host takes the asked columns slab by slab and adds
  * them in slab order: the asked columns' bytes per cell and slab, added to deme_multi_query_host_bytes.  The refusals of
